@@ -18,11 +18,15 @@ row asc) and verifies its own frames. Per-GPU work is constant as N grows (weak 
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N`; a bare `python bench.py --gpus N`
 starts exactly that as a child process (before anything touches the GPU) and exits with its code.
 
-One JSON line on rank 0. `roofline` is for the dominant kernel (the matcher's DB pass); `cpu_baseline` times the CPU
-oracle on a bounded sample of the same workload; `repeats` = the timed region run several times (value = the median);
-`chained`, `configs` (C1, C2, C4, C5 single-GPU share), `adapter_path` (one frame at a time through the host-buffer
-calls the ecto cells make), `hbm_regime` and `n4` (the 2D-only verifier and the LSH mode at the headline frame shape) are
-measured after the timed region, at N=1 only.
+One JSON line on rank 0. A plain run sets up, warms up (--warmup steps), times exactly --steps steps and prints the headline
+(`value`, `ms_per_step` = milliseconds per timed step); `roofline` is for the dominant kernel (the matcher's DB pass), from
+HIP events around its launches in the timed steps. --dump-outputs DIR writes what the last timed step computed
+(dump_outputs). Everything else runs with --full only: `repeats` = the timed region run several times (value = the
+median; 3 by default with --full); the other matcher engines on the same launch; at N>1 the sharded step-0 check against
+an unsharded replica; and at N=1, after the timed region, `chained`, `configs` (C1, C2, C4, C5 single-GPU share),
+`adapter_path` (one frame at a time through the host-buffer calls the ecto cells make), `hbm_regime`, `n4` (the 2D-only
+verifier and the LSH mode at the headline frame shape) and `cpu_baseline` (the CPU oracle on a bounded sample of the same
+workload).
 """
 import argparse
 import json
@@ -66,7 +70,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="steps per timed region (200 x 32 frames at ~2.6 ms: 0.5 s per region)")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3, help="the timed region of --steps steps is run this many times; value = median")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: the other matcher engines on the same launch, "
+                         "the --extras blocks and the CPU baseline (N=1), the sharded step-0 check (N>1); default repeats 3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (ORB keypoints and descriptors, matches, "
+                         "poses of rank 0's frames) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region of --steps steps is run this many times; value = median "
+                    "(default 1, with --full 3)")
     ap.add_argument("--objects", type=int, default=200, help="objects of 5000 descriptors (200 -> 1M rows)")
     ap.add_argument("--nq", type=int, default=1000)
     ap.add_argument("--k", type=int, default=2)
@@ -108,11 +119,18 @@ def parse():
                     "(todhip_set_cu_partition): ORB and verifier kernels then never share a SIMD with the matcher's DB pass")
     ap.add_argument("--iterations", type=int, default=2500, help="n_ransac_iterations (conf/detection.ork:38)")
     ap.add_argument("--min-inliers", type=int, default=8, help="min_inliers (conf/detection.ork:39)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--extras", default="chained,configs,adapter,hbm,n4", help="N=1 only, after the timed region: comma list of "
-                    "chained,configs,adapter,hbm,n4 ('' = none)")
-    return ap.parse_args()
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--extras", default=None, help="--full, N=1 only, after the timed region: comma list of "
+                    "chained,configs,adapter,hbm,n4 ('' = none; default all)")
+    args = ap.parse_args()
+    if args.extras is None:
+        args.extras = "chained,configs,adapter,hbm,n4" if args.full else ""
+    elif args.extras.strip(",") and not args.full:
+        ap.error("--extras %s: the extra blocks run with --full only" % args.extras)
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 def spawn_ranks(args):
@@ -214,6 +232,8 @@ class SyntheticPipeline:
         self.vctxs = [capi.Context(device, s.cuda_stream) for s in self.vstreams]
         self.orb_out = [(torch.empty((B, nq, 2), device="cuda"), torch.empty((B, nq, 4), device="cuda"),
                          torch.empty((B, nq, 32), dtype=torch.uint8, device="cuda")) for _ in self.octxs]
+        self.orb_n = [None] * len(self.octxs)                            # keypoints per frame of each ORB output set's last batch
+        self.poses = [None] * self.D                                     # the verifier's poses of the step that used outs[i % D]
         self.n_levels = n_levels
         self.match_fn = match_fn or self._match_local
         self.pipe = StagePipeline(torch, orb=self._orb if do_orb else None, match=lambda i, n_steps: self.match_fn(self, i, n_steps),
@@ -225,6 +245,7 @@ class SyntheticPipeline:
         o = self.orb_out[i % len(self.octxs)]
         n = self.octxs[i % len(self.octxs)].orb_batch_device(self.IMG_B[i % self.period].data_ptr(), self.B, self.H * self.W, self.H, self.W, self.W,
                                        self.nq, self.n_levels, 1.2, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), self.nq)
+        self.orb_n[i % len(self.octxs)] = n
         return sum(n)
 
     @staticmethod
@@ -242,6 +263,7 @@ class SyntheticPipeline:
                                               self.CLOUD_B[i % self.period].data_ptr(), self.H, self.W, o["counts"].data_ptr(),
                                               o["matches"].data_ptr(), o["xyz"].data_ptr(), self.k, self.spans, self.min_inliers,
                                               self.iterations, 0.01, rngs)
+        self.poses[i % self.D] = poses
         return sum(len(p) for p in poses)
 
     def close(self):
@@ -262,6 +284,53 @@ def timed_regions(torch, run, fence, steps, repeats, reduce_max=None):
         dt = time.perf_counter() - t0
         out.append(reduce_max(dt) if reduce_max else dt)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, sp, i):
+    """--dump-outputs: what step i (the last one run) handed its caller, as DIR/<name>.npy in float32 / float64 (integers
+    exactly): per frame of the batch the ORB keypoints and descriptors, the matches in the matcher's fixed-stride form and
+    the verifier's poses. The inputs are seeded, so two builds can be compared array for array. Slots past a frame's ORB
+    count or a query's match count hold whatever an earlier step left there and are written as 0. When the whole batch
+    exceeds 64 MB, its first frames are written (`frames` says how many)."""
+    torch = sp.torch
+    torch.cuda.synchronize()
+    B, nq, k = sp.B, sp.nq, sp.k
+    out = {}
+    if sp.octxs:
+        j = i % len(sp.octxs)
+        kp_xy, kp_aux, desc = (t.cpu().numpy() for t in sp.orb_out[j])
+        valid = np.arange(nq)[None, :] < np.asarray(sp.orb_n[j])[:, None]           # [B, nq]
+        out["orb_counts"] = np.asarray(sp.orb_n[j], np.float64)
+        out["orb_kp_xy"] = np.where(valid[..., None], kp_xy, 0).astype(np.float32)
+        out["orb_kp_aux"] = np.where(valid[..., None], kp_aux, 0).astype(np.float32)
+        out["orb_desc"] = np.where(valid[..., None], desc, 0).astype(np.float32)
+    o = sp.outs[i % sp.D]
+    counts = o["counts"].cpu().numpy().astype(np.int64)
+    m = o["matches"].cpu().numpy().reshape(B, nq, k, 4)
+    keep = (np.arange(k)[None, :] < counts[:, None]).reshape(B, nq, k, 1)
+    out["match_counts"] = counts.reshape(B, nq).astype(np.float64)
+    out["match_query_train_img"] = np.where(keep, m[..., :3], 0).astype(np.float64)        # todhip_dmatch's three int32 fields
+    out["match_distance"] = np.where(keep[..., 0], m.view(np.float32)[..., 3], 0).astype(np.float32)
+    out["match_xyz"] = np.where(keep, o["xyz"].cpu().numpy().reshape(B, nq, k, 3), 0).astype(np.float32)
+    per_frame = sum(a.nbytes for a in out.values()) / B
+    frames = max(1, min(B, int((DUMP_LIMIT_BYTES // 2) // per_frame)))             # half the limit: room for the poses
+    out = {name: a[:frames] for name, a in out.items()}
+    if sp.vctxs:
+        poses = [(f, p) for f, fp in enumerate(sp.poses[i % sp.D]) if f < frames for p in fp]
+        out["pose_frame"] = np.array([f for f, _ in poses], np.float64)
+        out["pose_object"] = np.array([p["object"] for _, p in poses], np.float64)
+        out["pose_R"] = np.array([p["R"] for _, p in poses], np.float32).reshape(-1, 3, 3)
+        out["pose_t"] = np.array([p["t"] for _, p in poses], np.float32).reshape(-1, 3)
+        out["pose_inlier_counts"] = np.array([len(p["inliers"]) for _, p in poses], np.float64)
+        out["pose_inliers"] = np.concatenate([np.asarray(p["inliers"], np.float64) for _, p in poses] or [np.zeros(0)])
+    out["frames"] = np.array([frames], np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    progress("outputs of step %d (%d frames, %.1f MB) written to %s" % (i, frames, sum(a.nbytes for a in out.values()) / 1e6, path))
 
 
 def launch_ms(c0, c1):
@@ -822,6 +891,7 @@ def main():
         cstream = torch.cuda.Stream(priority=int(os.environ.get("TOD_BENCH_COMM_PRIO", "-1"))) if overlap else stream
         ops = sharded.GpuOps(sp.ctx, stream, cstream, backend, k, args.radius)
         sm_box["sm"] = sharded.ShardedMatcher(ops, world, rank, B, nq, k, exchange=args.exchange, overlap=overlap)
+    if sharded_db and args.full:
         # self-check before anything is timed: step 0's merged matches of THIS rank's frames == the result of a replica that
         # holds the whole DB (every rank checks its own frames; the verdict is reduced over the ranks)
         sm = sm_box["sm"]
@@ -877,9 +947,12 @@ def main():
         world_q0 = 1 if (args.replicas or not use_dist) else world
         engine_used = "mfma" if (world_q0 * B * nq >= 64 and world_q0 * B * nq * info["shard_rows"] >= (1 << 24)) else "valu"
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sp, args.steps - 1)
+
     # outside the timed region, single device only: the other engine on the same launch, and (vector engine) the dense schedule
     other = {}
-    if world == 1 and not use_dist:
+    if world == 1 and not use_dist and args.full:
         o = sp.outs[0]
         for eng, radius in (("valu", args.radius), ("valu_dense", 256), ("mfma", args.radius)):
             sp.ctx.set_matcher_engine(eng.split("_")[0])
@@ -1006,7 +1079,7 @@ def main():
             if "n4" in extras:
                 out["n4"] = run_n4(torch, capi, local_rank, desc, pts, off, frames[:8], args)
                 progress("n4 done")
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(desc, pts, off, frames, k, args.radius, args.cpu_seconds, stages,
                                                    args.iterations, args.min_inliers)
         print(json.dumps(out))

@@ -4,7 +4,7 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out
-ARGS="bench.py --steps 10 --warmup 2 --no-cpu-baseline --stages match"
+ARGS="bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --stages match"
 rocprofv3 --pmc SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES SQC_DCACHE_MISSES_DUPLICATE SQC_TC_STALL SQC_DCACHE_BUSY_CYCLES --output-format csv -d $OUT/prof_k4_s1 -- python3 $ARGS > $OUT/prof_k4_s1.log 2>&1
 rocprofv3 --pmc SQ_INST_CYCLES_SALU SQ_INST_CYCLES_SMEM SQ_INSTS_BRANCH SQ_INST_LEVEL_SMEM SQ_IFETCH SQ_IFETCH_LEVEL SQ_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d $OUT/prof_k4_s2 -- python3 $ARGS > $OUT/prof_k4_s2.log 2>&1
 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_THREAD_CYCLES_VALU SQ_LEVEL_WAVES --output-format csv -d $OUT/prof_k4_s3 -- python3 $ARGS > $OUT/prof_k4_s3.log 2>&1

@@ -14,7 +14,7 @@ stats = newest(glob.glob(os.path.join(out, "prof_k4_trace", "**", "*kernel_stats
 assert stats, "no kernel_stats.csv"
 shutil.copy(stats[0], os.path.join(root, "profiles", "%s_%s_kernel_stats.csv" % (tag, name)))
 # the timed launches = the instantiation of the engine's kernel with the most calls (k = 2, radius 35; which query-block count
-# the launcher picked is part of the name; bench.py also runs a few launches of the other engine afterwards)
+# the launcher picked is part of the name; bench.py --full also runs a few launches of the other engine afterwards)
 KERNEL, avg_ns, calls = None, None, 0
 for row in csv.DictReader(open(stats[0])):
     if ("hamming_topk_mfma<" if mfma else "hamming_topk_tiles<") in row["Name"] and int(row["Calls"]) > calls:
