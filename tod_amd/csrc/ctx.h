@@ -30,9 +30,15 @@
 // bytes todhip_db_load allocates behind the last descriptor row: hamming_topk_mfma loads whole 32-row steps without a per-lane clamp
 constexpr size_t kDbSlackBytes = 2048;
 
+// A buffer frees itself with its owner and is never copied (release() is for freeing early on purpose). Nothing that holds one may
+// have static storage duration: its destructor would call hipFree after the runtime has shut down.
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) (void)hipFree(p);
@@ -59,6 +65,10 @@ struct DevBuf {
 struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() { release(); }
   hipError_t reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) (void)hipHostFree(p);
@@ -123,6 +133,15 @@ struct todhip_ctx {
   void* pnp_ws = nullptr;
   void* lsh_ws = nullptr;
 };
+
+// glibc random_r TYPE_3 (see include/todhip.h, decision D4)
+inline uint32_t rng_next(todhip_rng& r) {
+  r.s[r.f] += r.s[r.b];
+  const uint32_t out = r.s[r.f] >> 1;
+  r.f = r.f == 30u ? 0u : r.f + 1u; r.b = r.b == 30u ? 0u : r.b + 1u;
+  ++r.draws;
+  return out;
+}
 
 // capi.hip: a stream of the given kind (todhip_stream_create), honouring the process's CU partition
 extern "C" hipError_t tod_stream_create(hipStream_t* out, int device, int kind);

@@ -506,9 +506,6 @@ __global__ __launch_bounds__(256) void l2_finalize_kernel(const uint64_t* __rest
 void tod_l2_ws_free(todhip_ctx* ctx) {
   if (!ctx->l2_ws) return;
   L2Ws* ws = reinterpret_cast<L2Ws*>(ctx->l2_ws);
-  DevBuf* bufs[] = {&ws->db_bf16, &ws->db_norm, &ws->q_bf16, &ws->q_eps, &ws->part, &ws->thr, &ws->slots, &ws->slot_cnt, &ws->cand, &ws->cand_cnt, &ws->keys,
-                    &ws->scal};
-  for (DevBuf* b : bufs) b->release();
   delete ws;
   ctx->l2_ws = nullptr;
 }

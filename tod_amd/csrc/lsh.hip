@@ -169,8 +169,6 @@ int launch_query(todhip_ctx* ctx, LshWs* ws, const void* d_q, uint32_t nq, uint6
 void tod_lsh_ws_free(todhip_ctx* ctx) {
   LshWs* ws = reinterpret_cast<LshWs*>(ctx->lsh_ws);
   if (!ws) return;
-  DevBuf* bufs[] = {&ws->pos, &ws->masks, &ws->off, &ws->rows, &ws->cursor, &ws->scan_tmp};
-  for (DevBuf* b : bufs) b->release();
   delete ws;
   ctx->lsh_ws = nullptr;
 }

@@ -623,13 +623,8 @@ int tod_orb_device(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask
 void tod_orb_ws_free(todhip_ctx* ctx) {
   if (!ctx->orb_ws) return;
   OrbWs* ws = reinterpret_cast<OrbWs*>(ctx->orb_ws);
-  DevBuf* bufs[] = {&ws->pyr, &ws->blur, &ws->tmp, &ws->score, &ws->cand, &ws->eq, &ws->sel1, &ws->sel2,
-                    &ws->small, &ws->pattern, &ws->in_img, &ws->kp_xy, &ws->kp_aux, &ws->desc, &ws->o_xy, &ws->o_aux, &ws->o_desc,
-                    &ws->maskbuf};
-  for (DevBuf* b : bufs) b->release();
-  if (ws->graph_exec) (void)hipGraphExecDestroy(ws->graph_exec);
+  if (ws->graph_exec) (void)hipGraphExecDestroy(ws->graph_exec);   // the captured graph goes before the buffers it refers to
   if (ws->graph) (void)hipGraphDestroy(ws->graph);
-  ws->h_out.release(); ws->h_kp.release();
   delete ws;
   ctx->orb_ws = nullptr;
 }

@@ -427,22 +427,11 @@ __global__ __launch_bounds__(256) void pnp_active_kernel(const uint32_t* __restr
 
 struct PnpWs { DevBuf objs, kp, q_idx, X, best, flags, results, hist, goff, err, spans, seeds, na; };
 
-inline uint32_t rng_next(todhip_rng& r) {                            // glibc random_r TYPE_3, as in verify.hip
-  r.s[r.f] += r.s[r.b];
-  const uint32_t out = r.s[r.f] >> 1;
-  r.f = r.f == 30u ? 0u : r.f + 1u; r.b = r.b == 30u ? 0u : r.b + 1u;
-  ++r.draws;
-  return out;
-}
-
 }  // namespace
 
 void tod_pnp_ws_free(todhip_ctx* ctx) {
   PnpWs* ws = reinterpret_cast<PnpWs*>(ctx->pnp_ws);
   if (!ws) return;
-  DevBuf* bufs[] = {&ws->objs, &ws->kp, &ws->q_idx, &ws->X, &ws->best, &ws->flags, &ws->results, &ws->hist, &ws->goff, &ws->err, &ws->spans,
-                    &ws->seeds, &ws->na};
-  for (DevBuf* b : bufs) b->release();
   delete ws;
   ctx->pnp_ws = nullptr;
 }

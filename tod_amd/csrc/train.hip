@@ -212,9 +212,6 @@ int todhip_model_begin(todhip_ctx* ctx, uint32_t capacity_rows, todhip_model** o
 void todhip_model_free(todhip_ctx* ctx, todhip_model* m) {
   if (!m) return;
   if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
-  DevBuf* bufs[] = {&m->desc, &m->pts, &m->kp_xy, &m->kp_aux, &m->kp_desc, &m->img, &m->mask, &m->er_tmp, &m->er, &m->depth,
-                    &m->flags, &m->offs, &m->small};
-  for (DevBuf* b : bufs) b->release();
   delete m;
 }
 
@@ -287,8 +284,7 @@ int todhip_rescale_depth(todhip_ctx* ctx, const void* depth_in, int depth_is_u16
   if (rc == TODHIP_OK && hipMemcpyAsync(in.p, depth_in, in_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = TODHIP_EHIP;
   if (rc == TODHIP_OK) rc = todhip_rescale_depth_device(ctx, in.p, depth_is_u16, dH, dW, out.p, H, W, nearest);
   if (rc == TODHIP_OK && hipMemcpyAsync(depth_out, out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = TODHIP_EHIP;
-  (void)hipStreamSynchronize(ctx->stream);
-  in.release(); out.release();
+  (void)hipStreamSynchronize(ctx->stream);                    // (in and out are freed on return, after the copies)
   return rc;
 }
 

@@ -1717,129 +1717,18 @@ __global__ __launch_bounds__(64) void small_prep_kernel(H S) {
 }
 
 // ------------------------------------------------------------------------------------------------ K_c
-// ClusterPerObject (adjacency_ransac.cpp:176-205) for device-resident inputs. Matches arrive in the matcher's
-// fixed-stride layout (k slots per query, counts[q] used); the flat order (query asc, rank asc) is what the
-// reference's push_back order produces, and grouping by object is stable, so query_indices_ stays
-// non-decreasing per object (App. A Q4).
-struct LookupArgs {
-  const float* kp_xy; uint32_t nq; const float* cloud; const void* depth; int depth_is_u16; uint32_t H, Wimg;
-  float fx, fy, cx, cy; const uint32_t* counts; uint32_t* kept; float* qpt; uint32_t* err;
-};
-// cloud != nullptr: the query point is read from the H x W x 3 cloud (adjacency_ransac.cpp:184-185).
-// Otherwise N3: the reference back-projects the WHOLE registered depth image to an H x W x 3 cloud
-// (ecto_opencv DepthTo3d, python/object_recognition_tod/detector.py:26,62,66-69) and then reads Q points of it.
-// Here the Q points are computed directly: same pixel truncation, same pinhole back-projection as cv::depthTo3d
-// (x = (u - cx) z / fx, y = (v - cy) z / fy), uint16 depth in millimetres with 0 = no measurement -> NaN as
-// cv::rescaleDepth does (third-party conventions, recalled; parity unpinned).
-__global__ __launch_bounds__(256) void cluster_lookup_kernel(Slots<LookupArgs> SL) {
-  TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  const LookupArgs& a = SL.a[blockIdx.y];
-  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
-  if (q >= a.nq) return;
-  const int row = (int)a.kp_xy[2 * q + 1], col = (int)a.kp_xy[2 * q];    // float -> int truncation (:185)
-  if (row < 0 || col < 0 || (uint32_t)row >= a.H || (uint32_t)col >= a.Wimg) {
-    atomicExch(a.err, 1u);
-    a.kept[q] = 0;
-    return;
-  }
-  float x, y, z;
-  if (a.cloud) {
-    const float* p = a.cloud + 3 * ((size_t)row * a.Wimg + col);
-    x = p[0]; y = p[1]; z = p[2];
-  } else {
-    if (a.depth_is_u16) {
-      const uint16_t d = reinterpret_cast<const uint16_t*>(a.depth)[(size_t)row * a.Wimg + col];
-      z = d == 0 ? __builtin_nanf("") : (float)d * 0.001f;
-    } else {
-      z = reinterpret_cast<const float*>(a.depth)[(size_t)row * a.Wimg + col];
-    }
-    x = ((float)col - a.cx) * z / a.fx; y = ((float)row - a.cy) * z / a.fy;
-  }
-  a.qpt[3 * q] = x; a.qpt[3 * q + 1] = y; a.qpt[3 * q + 2] = z;
-  a.kept[q] = isnan(x) ? 0u : a.counts[q];                               // only .x is tested (:189)
-}
-
-// exclusive scan of kept[0..nq) into offs[0..nq], one block
-struct ScanArgs { const uint32_t* kept; uint32_t nq; uint32_t* offs; };
-__global__ __launch_bounds__(256) void cluster_scan_kernel(Slots<ScanArgs> SL) {
-  TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  const uint32_t* __restrict__ kept = SL.a[blockIdx.x].kept;
-  const uint32_t nq = SL.a[blockIdx.x].nq;
-  uint32_t* const offs = SL.a[blockIdx.x].offs;
-  __shared__ uint32_t part[256];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t chunk = (nq + 255u) / 256u;
-  const uint32_t lo = min(nq, tid * chunk), hi = min(nq, lo + chunk);
-  uint32_t s = 0;
-  for (uint32_t i = lo; i < hi; ++i) s += kept[i];
-  part[tid] = s;
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t acc = 0;
-    for (uint32_t i = 0; i < 256u; ++i) { const uint32_t c = part[i]; part[i] = acc; acc += c; }
-    offs[nq] = acc;
-  }
-  __syncthreads();
-  uint32_t acc = part[tid];
-  for (uint32_t i = lo; i < hi; ++i) { offs[i] = acc; acc += kept[i]; }
-}
-
-struct ScatterArgs {
-  const float* kp_xy; uint32_t nq, k; const todhip_dmatch* matches; const float* mxyz; const uint32_t* kept;
-  const uint32_t* offs; const float* qpt; uint32_t n_objs; uint32_t* obj_of; uint32_t* hist; float* ftrain; float* fquery;
-  uint32_t* fqidx; float* fkp; uint32_t* err;
-};
-__global__ __launch_bounds__(256) void cluster_scatter_kernel(Slots<ScatterArgs> SL) {
-  TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  const ScatterArgs& a = SL.a[blockIdx.y];
-  const float* __restrict__ kp_xy = a.kp_xy; const uint32_t nq = a.nq, k = a.k, n_objs = a.n_objs;
-  const todhip_dmatch* __restrict__ matches = a.matches; const float* __restrict__ mxyz = a.mxyz;
-  const uint32_t* __restrict__ kept = a.kept; const uint32_t* __restrict__ offs = a.offs; const float* __restrict__ qpt = a.qpt;
-  uint32_t* const obj_of = a.obj_of; uint32_t* const hist = a.hist; float* const ftrain = a.ftrain; float* const fquery = a.fquery;
-  uint32_t* const fqidx = a.fqidx; float* const fkp = a.fkp; uint32_t* const err = a.err;
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  const uint32_t q = t / k, j = t % k;
-  if (q >= nq || j >= kept[q]) return;
-  const uint32_t f = offs[q] + j;
-  const todhip_dmatch m = matches[(size_t)q * k + j];
-  uint32_t o = (uint32_t)m.imgIdx;
-  if (m.imgIdx < 0 || o >= n_objs) { atomicExch(err, 2u); o = 0; }
-  obj_of[f] = o;
-  atomicAdd(&hist[o], 1u);
-  for (int c = 0; c < 3; ++c) { ftrain[3 * f + c] = mxyz[((size_t)q * k + j) * 3 + c]; fquery[3 * f + c] = qpt[3 * q + c]; }
-  fqidx[f] = q;
-  fkp[2 * f] = kp_xy[2 * q]; fkp[2 * f + 1] = kp_xy[2 * q + 1];
-}
-
-// stable grouping by object: destination = group offset + number of earlier matches of the same object
-struct GroupArgs {
-  uint32_t n_all; const uint32_t* obj_of; const uint32_t* goff; const float* ftrain; const float* fquery;
-  const uint32_t* fqidx; const float* fkp; float* train; float* query; uint32_t* qidx; float* kpxy;
-};
-__global__ __launch_bounds__(256) void cluster_group_kernel(Slots<GroupArgs> SL) {
-  TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  const GroupArgs& a = SL.a[blockIdx.y];
-  const uint32_t n_all = a.n_all;
-  const uint32_t* __restrict__ obj_of = a.obj_of; const uint32_t* __restrict__ goff = a.goff;
-  const float* __restrict__ ftrain = a.ftrain; const float* __restrict__ fquery = a.fquery;
-  const uint32_t* __restrict__ fqidx = a.fqidx; const float* __restrict__ fkp = a.fkp;
-  float* const train = a.train; float* const query = a.query; uint32_t* const qidx = a.qidx; float* const kpxy = a.kpxy;
-  const uint32_t f = blockIdx.x * 256u + threadIdx.x;
-  if (f >= n_all) return;
-  const uint32_t o = obj_of[f];
-  uint32_t rank = 0;
-  for (uint32_t g = 0; g < f; ++g) rank += obj_of[g] == o;
-  const uint32_t d = goff[o] + rank;
-  for (int c = 0; c < 3; ++c) { train[3 * d + c] = ftrain[3 * f + c]; query[3 * d + c] = fquery[3 * f + c]; }
-  qidx[d] = fqidx[f];
-  kpxy[2 * d] = fkp[2 * f]; kpxy[2 * d + 1] = fkp[2 * f + 1];
-}
-
-// ClusterPerObject of one frame in ONE launch of one block (the four kernels above are its parts, kept for the launch-group of a
-// frame whose match list does not fit one block's patience: none today): lookup -> scan -> scatter + histogram -> object offsets
-// -> stable grouping, with the histogram and the frame's totals written straight into the slot's mailbox. Inside the pipeline
-// every dependent launch waits for wave slots beside the matcher's resident grid: five dependent launches and a host round trip
-// between the scatter and the grouping were 0.4-0.5 ms per batch there (45 us alone).
+// ClusterPerObject (adjacency_ransac.cpp:176-205) of one frame, for device-resident inputs, in ONE launch of one block: lookup ->
+// scan -> scatter + histogram -> object offsets -> stable grouping, with the histogram and the frame's totals written straight into
+// the slot's mailbox. Matches arrive in the matcher's fixed-stride layout (k slots per query, counts[q] used); the flat order
+// (query asc, rank asc) is what the reference's push_back order produces, and grouping by object is stable, so query_indices_
+// stays non-decreasing per object (App. A Q4).
+// The keypoint's 3D point: with cloud != nullptr it is read from the H x W x 3 cloud (adjacency_ransac.cpp:184-185). Otherwise N3
+// (SURVEY 8(f)): the reference back-projects the WHOLE registered depth image to an H x W x 3 cloud (ecto_opencv DepthTo3d,
+// python/object_recognition_tod/detector.py:26,62,66-69) and then reads Q points of it. Here the Q points are computed directly:
+// same pixel truncation, same pinhole back-projection as cv::depthTo3d (x = (u - cx) z / fx, y = (v - cy) z / fy), uint16 depth
+// in millimetres with 0 = no measurement -> NaN as cv::rescaleDepth does (third-party conventions, recalled; parity unpinned).
+// Inside the pipeline every dependent launch waits for wave slots beside the matcher's resident grid: five dependent launches and
+// a host round trip between the scatter and the grouping were 0.4-0.5 ms per batch there (45 us alone).
 struct ClusterArgs {
   const float* kp_xy; const float* cloud; const void* depth; const uint32_t* counts; const todhip_dmatch* matches; const float* mxyz;
   uint32_t nq, k, H, Wimg, n_objs, qidx_add; int depth_is_u16; float fx, fy, cx, cy;   // qidx_add: added to the keypoint index stored per match
@@ -1855,7 +1744,7 @@ __global__ __launch_bounds__(256) void cluster_frame_kernel(Slots<ClusterArgs> S
   if (tid == 0) s_err = 0u;
   for (uint32_t o = tid; o < n_objs; o += 256u) { a.hist[o] = 0u; a.cnt[o] = 0u; }
   __syncthreads();
-  // ---- the keypoint's 3D point (adjacency_ransac.cpp:184-189), see cluster_lookup_kernel
+  // ---- the keypoint's 3D point (adjacency_ransac.cpp:184-189): cloud lookup, or the depth pixel back-projected (see above)
   for (uint32_t q = tid; q < nq; q += 256u) {
     const int row = (int)a.kp_xy[2 * q + 1], col = (int)a.kp_xy[2 * q];    // float -> int truncation (:185)
     const bool lookup = a.cloud || a.depth;                                // neither: the 2D-only branch (GuessGenerator.cpp:147-152), no 3D point
@@ -1967,21 +1856,13 @@ __global__ __launch_bounds__(256) void cluster_frame_kernel(Slots<ClusterArgs> S
 
 // ------------------------------------------------------------------------------------------------ host side
 struct VerifyWs {
-  DevBuf train, query, qidx, kpxy, phys, samp, bits, sampdeg, nvalid, rnd, table, iter_samples, counts, gate_m,
-      small, deferred, stacks, kp_bits, clique_adj, adjc_scratch, c_kept, c_offs, c_qpt, c_obj, c_hist, c_goff, f_train,
-      f_query, f_qidx, f_kp, sprint_status, sprint_stack, c_src, c_cnt;
+  DevBuf train, query, qidx, kpxy, phys, samp, bits, sampdeg, nvalid, table, iter_samples, counts, gate_m,
+      small, deferred, stacks, kp_bits, clique_adj, adjc_scratch, c_kept, c_offs, c_qpt, c_obj, c_hist, c_goff,
+      sprint_status, sprint_stack, c_src, c_cnt;
   // the slot's mailbox: pinned host memory that kernels read and write directly (see copy_words_kernel)
-  HostBuf m_small, m_hist, m_goff, m_rnd, m_pos, m_counts, m_kp, m_nvalid;
+  HostBuf m_small, m_hist, m_pos, m_counts, m_kp, m_nvalid;
   HostBuf m_sprint, m_sprint_out, m_sprint_kp;              // sprint_kernel: the object list in, records and keypoint lists out
   HostBuf h_small;                                          // staging of the test hooks
-  void release() {
-    DevBuf* bufs[] = {&train, &query, &qidx, &kpxy, &phys, &samp, &bits, &sampdeg, &nvalid, &rnd, &table, &iter_samples, &counts, &gate_m,
-                      &small, &deferred, &stacks, &kp_bits, &clique_adj, &adjc_scratch, &c_kept, &c_offs, &c_qpt, &c_obj, &c_hist,
-                      &c_goff, &f_train, &f_query, &f_qidx, &f_kp, &sprint_status, &sprint_stack, &c_src, &c_cnt};
-    for (DevBuf* b : bufs) b->release();
-    HostBuf* hb[] = {&m_small, &m_hist, &m_goff, &m_rnd, &m_pos, &m_counts, &m_kp, &m_nvalid, &h_small, &m_sprint, &m_sprint_out, &m_sprint_kp};
-    for (HostBuf* b : hb) b->release();
-  }
 };
 
 // one workspace per frame slot of a batch; slot 0 also serves the single-frame entry points and the test hooks
@@ -2055,15 +1936,6 @@ VerifyWs* ws_of(todhip_ctx* ctx, size_t slot = 0) {
   return p->slots[slot];
 }
 
-// glibc random_r TYPE_3 (see include/todhip.h, decision D4)
-inline uint32_t rng_next(todhip_rng& r) {
-  r.s[r.f] += r.s[r.b];
-  const uint32_t out = r.s[r.f] >> 1;
-  r.f = r.f == 30u ? 0u : r.f + 1u; r.b = r.b == 30u ? 0u : r.b + 1u;
-  ++r.draws;
-  return out;
-}
-
 // The rand() stream of a frame, generated once and shared: every round of every object reads a window of it, and
 // frames that start from the same generator state (a harness restarting rand() per frame, decision D4) share one
 // copy. Snapshots of the generator every kSnap draws give the state at any position without replaying the stream.
@@ -2113,28 +1985,55 @@ struct StreamCache {
   }
 };
 
+// ransac.h:121-130 with libm: k = log(1 - 0.99) / log(1 - w^3), w = n_best / |valid|. The host's replay and the device's table
+// (VerifyPool::kceil) must be this one sequence of double operations: round traces are compared bit for bit on iteration counts.
+inline double ransac_k(double w) {
+  double p_no_outliers = 1.0 - std::pow(w, 3.0);
+  p_no_outliers = std::max(std::numeric_limits<double>::epsilon(), p_no_outliers);
+  p_no_outliers = std::min(1.0 - std::numeric_limits<double>::epsilon(), p_no_outliers);
+  return std::log(1.0 - 0.99) / std::log(p_no_outliers);
+}
+
+// launch(kernel, extent) with eval_kernel's instantiation for the objects' width (wide: more than 512 matches) and the blocks one
+// argument set needs: its iterations, or its deferred ones. H: Slots<EvalArgs> (launch_list) or SlotsPtr<EvalArgs> (launch_many).
+template <class H, class Launch>
+bool pick_eval(bool wide, bool deferred, Launch launch) {
+  auto extent = [deferred](const EvalArgs& a) { return dim3(deferred ? a.n_deferred : a.it_end - a.it_begin); };
+  return wide ? launch(eval_kernel<true, H>, extent) : launch(eval_kernel<false, H>, extent);
+}
+
 int set_big_lds_once(todhip_ctx* ctx) {
   static std::atomic<bool> done{false};                   // contexts may be driven from several host threads
   if (!done.load(std::memory_order_acquire)) {
-    TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kEvalLdsBig));
-    TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kEvalLdsBig));
-    TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_kernel<false, SlotsPtr<EvalArgs>>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBig));
-    TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(eval_kernel<true, SlotsPtr<EvalArgs>>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBig));
-    TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(clique_test_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBig));
-    TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(clique_test_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBig));
-    TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kEvalLdsBig));
+    const void* const big[] = {reinterpret_cast<const void*>(eval_kernel<false>), reinterpret_cast<const void*>(eval_kernel<true>),
+                               reinterpret_cast<const void*>(eval_kernel<false, SlotsPtr<EvalArgs>>),
+                               reinterpret_cast<const void*>(eval_kernel<true, SlotsPtr<EvalArgs>>),
+                               reinterpret_cast<const void*>(clique_test_kernel<false>), reinterpret_cast<const void*>(clique_test_kernel<true>),
+                               reinterpret_cast<const void*>(chain_kernel)};
+    for (const void* f : big) TOD_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBig));
     TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sprint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kSprintLds));
     done.store(true, std::memory_order_release);
   }
   return TODHIP_OK;
+}
+
+// the first-pass evaluation of iterations [it_lo, it_hi) of `job` out of the slot's buffers (ws->stacks is reserved by the caller)
+EvalArgs eval_args(const ObjJob& job, VerifyWs* ws, int32_t* counts, uint32_t it_lo, uint32_t it_hi, uint32_t lds_bytes) {
+  uint32_t* d_small = ws->small.as<uint32_t>();
+  EvalArgs A;
+  A.job = job; A.iter_samples = ws->iter_samples.as<uint32_t>(); A.it_begin = it_lo; A.it_end = it_hi;
+  A.counts = counts; A.gate_m = ws->gate_m.as<uint32_t>(); A.work = d_small + 8;
+  A.status = d_small + 12; A.deferred = ws->deferred.as<uint32_t>(); A.stacks = ws->stacks.as<uint16_t>();
+  A.stack_cap = kStackCap; A.lds_bytes = lds_bytes; A.from_deferred = 0u; A.n_deferred = 0u;
+  A.adjc_scratch = nullptr; A.dbg = nullptr; A.dbg_stride = 0; A.stop_level = 0; A.n_items_dev = nullptr;
+  return A;
+}
+// the part of cluster_frame_kernel's arguments that is the slot's own scratch, whoever receives the grouped outputs
+void cluster_scratch(ClusterArgs& ca, VerifyWs* ws) {
+  ca.kept = ws->c_kept.as<uint32_t>(); ca.offs = ws->c_offs.as<uint32_t>(); ca.obj_of = ws->c_obj.as<uint32_t>();
+  ca.src = ws->c_src.as<uint32_t>(); ca.cnt = ws->c_cnt.as<uint32_t>(); ca.qpt = ws->c_qpt.as<float>();
+  ca.query = ws->query.as<float>(); ca.kpxy = ws->kpxy.as<float>(); ca.m_hist = ws->m_hist.as<uint32_t>();
 }
 
 struct ObjSpan {
@@ -2153,7 +2052,7 @@ struct DepthInput { const void* d_depth; int is_u16; float fx, fy, cx, cy; };
 // advanced together: a TICK lets every live slot issue the kernels of its next phase into per-kernel lists, launches
 // each non-empty list once (all slots in one grid), synchronizes once, and lets every slot consume its results
 // (the ransac.h:95-135 bookkeeping is replayed on the host so that pow/log are libm's).
-enum Phase { PH_CLUSTER, PH_CLUSTER_WAIT, PH_GROUP, PH_PREPALL, PH_PREPALL_WAIT, PH_OBJECT, PH_ROUND, PH_PREP_WAIT, PH_DRAW,
+enum Phase { PH_CLUSTER, PH_CLUSTER_WAIT, PH_PREPALL, PH_PREPALL_WAIT, PH_OBJECT, PH_ROUND, PH_PREP_WAIT, PH_DRAW,
              PH_DRAW_WAIT, PH_EVAL2, PH_EVAL2_WAIT, PH_GROWTH, PH_GROWTH_WAIT, PH_SPRINT_WAIT, PH_DONE };
 
 struct RoundState {                                       // computeModel (ransac.h:80-143) in flight
@@ -2195,7 +2094,6 @@ struct Slot {
   std::vector<ObjSpan> objs;
   size_t oi = 0;
   ObjJob job = {};
-  uint32_t n_all = 0;
   bool pending_invalidate = false;
   bool in_flight = false;                                 // its current tick runs on a side stream (run_ticks)
   // window-size hint for the next object's first draw window: what the previous objects of this frame consumed when their
@@ -2210,7 +2108,6 @@ struct Slot {
 
 struct Launches {
   std::vector<CopyArgs> copy_in, zero, copy_out;
-  std::vector<LookupArgs> lookup; std::vector<ScanArgs> scan; std::vector<ScatterArgs> scatter; std::vector<GroupArgs> group;
   std::vector<InvArgs> inval, inval_after; std::vector<JobArgs> finite; std::vector<AdjArgs> adj; std::vector<PrepArgs> prep, prep_after;   // *_after: behind the growth kernels
   std::vector<DrawArgs> draw, draw_small; std::vector<ChainArgs> chain;
   // the rnd pointers of the draw lists are resolved at launch time: a later slot of the same tick may grow (move)
@@ -2272,6 +2169,21 @@ struct Engine {
   }
   u64* obj_bits(const Slot& s) const { return s.ws->bits.as<u64>() + s.objs[s.oi].bits_off; }
 
+  // the trace of the round of object `obj` that starts at the stream position the completed rounds have reached
+  void begin_trace(Slot& s, uint32_t obj) {
+    s.tr = todhip_round_trace();
+    s.tr.object = obj; s.tr.draws_before = s.start_draws + s.abs_pos; s.tr.best_count = -INT_MAX;
+  }
+  // the first round of object o = s.objs[s.oi], from the statistics of the all-objects preparation: -> PH_DRAW, or the host decides
+  // it without a kernel (fewer than 3 valid matches, or triangle-free) and round_done has moved on to the next object
+  void first_round(Slot& s, const ObjSpan& o) {
+    s.job = make_job(s, o);
+    ctx->counters.last_objects_verified += 1;
+    s.pending_invalidate = false;
+    begin_trace(s, o.obj);
+    start_round(s, o.nvalid, o.degsum, o.triangle);
+  }
+
   // one AdjacencyRansac::Ransac call starts with |valid| known (adjacency_ransac.cpp:234-241)
   void start_round(Slot& s, uint32_t nvalid, uint32_t degsum, uint32_t triangle) {
     VerifyWs* ws = s.ws;
@@ -2313,18 +2225,12 @@ struct Engine {
     VerifyWs* ws = s.ws;
     uint32_t* d_small = ws->small.as<uint32_t>();
     RoundState& r = s.r;
-    EvalArgs A;
-    A.job = s.job; A.iter_samples = ws->iter_samples.as<uint32_t>(); A.it_begin = it_lo; A.it_end = it_hi;
-    A.counts = ws->m_counts.as<int32_t>(); A.gate_m = ws->gate_m.as<uint32_t>(); A.work = d_small + 8;
-    A.status = d_small + 12; A.deferred = ws->deferred.as<uint32_t>();
-    A.stack_cap = kStackCap; A.lds_bytes = second ? kEvalLdsBig : eval_lds_small(s.job.n); A.from_deferred = second ? 1u : 0u;
-    A.n_deferred = second ? r.n_def : 0u;
     SLOT_HIP(ws->stacks.reserve((size_t)std::max(std::max(it_hi - it_lo, r.n_def), 64u) * kStackCap * sizeof(uint16_t)));
-    A.stacks = ws->stacks.as<uint16_t>();
-    A.adjc_scratch = nullptr; A.dbg = nullptr; A.dbg_stride = 0; A.stop_level = 0; A.n_items_dev = n_items_dev;
+    EvalArgs A = eval_args(s.job, ws, ws->m_counts.as<int32_t>(), it_lo, it_hi, eval_lds_small(s.job.n));
+    A.n_items_dev = n_items_dev;
     if (second) {
       SLOT_HIP(ws->adjc_scratch.reserve((size_t)r.n_def * kAdjcScratchWords * sizeof(u64)));
-      A.adjc_scratch = ws->adjc_scratch.as<u64>();
+      A.lds_bytes = kEvalLdsBig; A.from_deferred = 1u; A.n_deferred = r.n_def; A.adjc_scratch = ws->adjc_scratch.as<u64>();
       L.zero.push_back({nullptr, d_small + 8, 1u});
       L.eval_big.push_back(A);
       return;
@@ -2349,22 +2255,12 @@ struct Engine {
       ca.kp_xy = s.d_kp_xy; ca.cloud = s.use_depth ? nullptr : s.d_cloud; ca.depth = s.dep.d_depth; ca.counts = s.d_counts;
       ca.matches = s.d_matches; ca.mxyz = s.d_mxyz; ca.nq = nq; ca.k = k; ca.H = H; ca.Wimg = Wimg; ca.n_objs = n_objs; ca.qidx_add = 0u;
       ca.depth_is_u16 = s.dep.is_u16; ca.fx = s.dep.fx; ca.fy = s.dep.fy; ca.cx = s.dep.cx; ca.cy = s.dep.cy;
-      ca.kept = ws->c_kept.as<uint32_t>(); ca.offs = ws->c_offs.as<uint32_t>(); ca.obj_of = ws->c_obj.as<uint32_t>();
-      ca.src = ws->c_src.as<uint32_t>(); ca.hist = ws->c_hist.as<uint32_t>(); ca.goff = ws->c_goff.as<uint32_t>();
-      ca.cnt = ws->c_cnt.as<uint32_t>(); ca.qpt = ws->c_qpt.as<float>();
-      ca.train = ws->train.as<float>(); ca.query = ws->query.as<float>(); ca.kpxy = ws->kpxy.as<float>(); ca.qidx = ws->qidx.as<uint32_t>();
-      ca.m_hist = ws->m_hist.as<uint32_t>(); ca.m_ctl = mail(s) + 60;
+      cluster_scratch(ca, ws);
+      ca.hist = ws->c_hist.as<uint32_t>(); ca.goff = ws->c_goff.as<uint32_t>();
+      ca.train = ws->train.as<float>(); ca.qidx = ws->qidx.as<uint32_t>(); ca.m_ctl = mail(s) + 60;
       L.cluster.push_back(ca);
       s.ph = PH_CLUSTER_WAIT;
       return;
-    }
-    if (s.ph == PH_GROUP) {
-      L.copy_in.push_back({ws->m_goff.as<uint32_t>(), ws->c_goff.as<uint32_t>(), n_objs});
-      GroupArgs ga = {s.n_all, ws->c_obj.as<uint32_t>(), ws->c_goff.as<uint32_t>(), ws->f_train.as<float>(), ws->f_query.as<float>(),
-                      ws->f_qidx.as<uint32_t>(), ws->f_kp.as<float>(), ws->train.as<float>(), ws->query.as<float>(),
-                      ws->qidx.as<uint32_t>(), ws->kpxy.as<float>()};
-      L.group.push_back(ga);
-      s.ph = PH_PREPALL;
     }
     if (s.ph == PH_PREPALL) {
       // FillAdjacency and the first round's validity/degree pass of EVERY object of the frame in this one tick: they
@@ -2392,13 +2288,7 @@ struct Engine {
       while (s.oi < s.objs.size() && s.objs[s.oi].n < 3) ++s.oi;
       if (s.oi >= s.objs.size()) { s.ph = PH_DONE; return; }
       if (sprint_on() && sprint_live(s.objs[s.oi])) { issue_sprint(s); return; }
-      const ObjSpan& o = s.objs[s.oi];
-      s.job = make_job(s, o);
-      ctx->counters.last_objects_verified += 1;
-      s.pending_invalidate = false;
-      s.tr = todhip_round_trace();
-      s.tr.object = o.obj; s.tr.draws_before = s.start_draws + s.abs_pos; s.tr.best_count = -INT_MAX;
-      start_round(s, o.nvalid, o.degsum, o.triangle);       // -> PH_DRAW, or straight on to the next object
+      first_round(s, s.objs[s.oi]);                         // -> PH_DRAW, or straight on to the next object
     }
     if (s.ph == PH_ROUND) {                                 // one AdjacencyRansac::Ransac call (GuessGenerator.cpp:192-231)
       if (s.pending_invalidate) {
@@ -2408,8 +2298,7 @@ struct Engine {
       L.zero.push_back({nullptr, d_small, 64u});
       L.prep.push_back({s.job, d_small + 5, nullptr, 0u});   // words 5..7: |valid|, degree sum, triangle (1..4 = ChainOut)
       export_small(s);
-      s.tr = todhip_round_trace();
-      s.tr.object = s.objs[s.oi].obj; s.tr.draws_before = s.start_draws + s.abs_pos; s.tr.best_count = -INT_MAX;
+      begin_trace(s, s.objs[s.oi].obj);
       s.ph = PH_PREP_WAIT;
       return;
     }
@@ -2534,14 +2423,8 @@ struct Engine {
       if (!touched) break;                                   // the wave stopped before this object: PH_OBJECT takes it from here
       // the objects the host decides without a kernel on the way (first round: fewer than 3 valid matches, or triangle-free)
       while (s.oi < idx) {
-        const ObjSpan& t = s.objs[s.oi];
-        if (t.n < 3u) { ++s.oi; continue; }
-        s.job = make_job(s, t);
-        ctx->counters.last_objects_verified += 1;
-        s.pending_invalidate = false;
-        s.tr = todhip_round_trace();
-        s.tr.object = t.obj; s.tr.draws_before = s.start_draws + s.abs_pos; s.tr.best_count = -INT_MAX;
-        start_round(s, t.nvalid, t.degsum, t.triangle);      // -> round_done: ++s.oi
+        if (s.objs[s.oi].n < 3u) { ++s.oi; continue; }
+        first_round(s, s.objs[s.oi]);                        // -> round_done: ++s.oi
         if (s.ph == PH_DONE) return;                         // (a failure)
       }
       ObjSpan& o = s.objs[idx];
@@ -2550,26 +2433,13 @@ struct Engine {
         const uint32_t* rec = out + kSprintHdrWords + (size_t)ri * kSprintRecWords;
         if (rec[0] != m) break;
         const uint64_t consumed = ((uint64_t)rec[5] << 32) | rec[4];
-        todhip_round_trace tr = todhip_round_trace();
-        tr.object = o.obj; tr.draws_before = s.start_draws + s.abs_pos;
-        tr.iterations = rec[1]; tr.best_iteration = rec[2]; tr.best_count = (int32_t)rec[3];
+        begin_trace(s, o.obj);
+        s.tr.iterations = rec[1]; s.tr.best_iteration = rec[2]; s.tr.best_count = (int32_t)rec[3];
         s.abs_pos += consumed;
         const uint32_t n_kp = rec[7] ? rec[6] : 0u;
-        ctx->counters.last_rounds += 1;
-        tr.draws_after = s.start_draws + s.abs_pos; tr.n_inlier_kp = n_kp; tr.accepted = n_kp >= prm->min_inliers;
-        s.traces.push_back(tr);
-        if (n_kp >= prm->min_inliers) {                      // GuessGenerator.cpp:205-230
+        if (close_round(s, n_kp)) {
           if (rec[20] + n_kp > kSprintMaxRecs * kSprintN) { fail(s, TODHIP_ESCRATCH); return; }
-          todhip_pose p;
-          std::memset(&p, 0, sizeof(p));
-          p.object = o.obj;
-          std::memcpy(p.R, rec + 8, sizeof(p.R));
-          std::memcpy(p.t, rec + 17, sizeof(p.t));
-          p.inlier_begin = (uint32_t)s.inliers.size();
-          s.inliers.insert(s.inliers.end(), kp_out + rec[20], kp_out + rec[20] + n_kp);
-          p.inlier_end = (uint32_t)s.inliers.size();
-          s.poses.push_back(p);
-          ctx->counters.last_poses += 1;
+          push_pose(s, o.obj, rec + 8, rec + 17, kp_out + rec[20], n_kp);
         }
       }
       if (!complete) {                                       // relaunch from this object; the kernel recomputes its statistics
@@ -2637,11 +2507,7 @@ struct Engine {
       if (n_count > r.n_best) {
         r.n_best = n_count;
         r.best_it = (uint32_t)r.iterations;
-        const double w = (double)r.n_best / (double)r.nvalid;
-        double p_no_outliers = 1.0 - std::pow(w, 3.0);
-        p_no_outliers = std::max(std::numeric_limits<double>::epsilon(), p_no_outliers);
-        p_no_outliers = std::min(1.0 - std::numeric_limits<double>::epsilon(), p_no_outliers);
-        r.k = std::log(1.0 - 0.99) / std::log(p_no_outliers);
+        r.k = ransac_k((double)r.n_best / (double)r.nvalid);
       }
       ++r.iterations;
       if (r.iterations > (int)prm->n_ransac_iterations) { r.loop_done = true; r.pos_after_stop = hp[r.iterations - 1]; }
@@ -2660,28 +2526,34 @@ struct Engine {
     if (r.n_best <= 0) { round_done(s, false); return; }   // inliers_.empty(): computeModel() == false (:137-138)
     s.ph = PH_GROWTH;
   }
-  void round_done(Slot& s, bool have_pose) {
-    const GrowthOut* go = reinterpret_cast<const GrowthOut*>(mail(s) + 32);
-    const uint32_t n_kp = have_pose ? go->n_kp_inliers : 0u;
+  // a round is over, s.abs_pos behind its draws: the tail of its trace; whether its pose is accepted (GuessGenerator.cpp:205-206)
+  bool close_round(Slot& s, uint32_t n_kp) {
     ctx->counters.last_rounds += 1;
     s.tr.draws_after = s.start_draws + s.abs_pos; s.tr.n_inlier_kp = n_kp; s.tr.accepted = n_kp >= prm->min_inliers;
     s.traces.push_back(s.tr);
-    if (n_kp < prm->min_inliers) { ++s.oi; s.ph = PH_OBJECT; return; }   // GuessGenerator.cpp:205-206
+    return n_kp >= prm->min_inliers;
+  }
+  // an accepted pose (GuessGenerator.cpp:207-230): R (9 floats), t (3) and the n_kp inlier keypoints from where the round left them
+  void push_pose(Slot& s, uint32_t obj, const void* R, const void* t, const uint32_t* kp, uint32_t n_kp) {
     todhip_pose p;
     std::memset(&p, 0, sizeof(p));
-    p.object = s.objs[s.oi].obj;
-    std::memcpy(p.R, go->R, sizeof(p.R));
-    std::memcpy(p.t, go->T, sizeof(p.t));
+    p.object = obj;
+    std::memcpy(p.R, R, sizeof(p.R));
+    std::memcpy(p.t, t, sizeof(p.t));
     p.inlier_begin = (uint32_t)s.inliers.size();
-    const uint32_t* list = s.ws->m_kp.as<uint32_t>();
-    s.inliers.insert(s.inliers.end(), list, list + n_kp);
+    s.inliers.insert(s.inliers.end(), kp, kp + n_kp);
     p.inlier_end = (uint32_t)s.inliers.size();
     s.poses.push_back(p);
     ctx->counters.last_poses += 1;
+  }
+  void round_done(Slot& s, bool have_pose) {
+    const GrowthOut* go = reinterpret_cast<const GrowthOut*>(mail(s) + 32);
+    const uint32_t n_kp = have_pose ? go->n_kp_inliers : 0u;
+    if (!close_round(s, n_kp)) { ++s.oi; s.ph = PH_OBJECT; return; }
+    push_pose(s, s.objs[s.oi].obj, go->R, go->T, s.ws->m_kp.as<uint32_t>(), n_kp);
     // InvalidateQueryIndices and the next round's validity pass (:207-230) ran behind the growth kernel in this tick
     s.pending_invalidate = false;
-    s.tr = todhip_round_trace();
-    s.tr.object = s.objs[s.oi].obj; s.tr.draws_before = s.start_draws + s.abs_pos; s.tr.best_count = -INT_MAX;
+    begin_trace(s, s.objs[s.oi].obj);
     const uint32_t* m = mail(s);
     start_round(s, m[5], m[6], m[7]);
   }
@@ -2693,14 +2565,11 @@ struct Engine {
     RoundState& r = s.r;
     if (s.ph == PH_CLUSTER_WAIT) {
       if (m[60] != 0) { fail(s, TODHIP_ERANGE); return; }
-      s.n_all = m[64];
-      if (s.n_all == 0) { s.ph = PH_DONE; return; }
+      if (m[64] == 0) { s.ph = PH_DONE; return; }             // n_all: no match kept
       const uint32_t* hist = ws->m_hist.as<uint32_t>();
-      uint32_t* goff = ws->m_goff.as<uint32_t>();
       uint32_t total = 0, max_n = 0;
       s.objs.clear();
       for (uint32_t o = 0; o < n_objs; ++o) {
-        goff[o] = total;
         if (hist[o]) s.objs.push_back({o, total, hist[o]});
         total += hist[o];
         max_n = std::max(max_n, hist[o]);
@@ -2792,17 +2661,12 @@ struct Engine {
     TOD_HIP(ws->m_kp.reserve((size_t)std::max(nq, 1u) * sizeof(uint32_t)));
     VerifyPool* pool = pool_of(ctx);
     if (!pool->kceil_ready) {
-      // ransac.h:121-130 with libm, once: k = log(1 - 0.99) / log(1 - w^3), w = n_best / |valid|; `iterations_ < k` (:95) is
-      // `iterations_ < ceil(k)` for an integer iterations_, so the device replays the loop test exactly from this table
+      // ransac_k per (|valid|, n_best), once: `iterations_ < k` (ransac.h:95) is `iterations_ < ceil(k)` for an integer
+      // iterations_, so the device replays the loop test exactly from this table
       std::vector<uint32_t> tab(65u * 65u, 1u);
       for (uint32_t nv = 1; nv <= 64u; ++nv)
         for (uint32_t nb = 0; nb <= 64u; ++nb) {
-          const double w = (double)(int)nb / (double)nv;
-          double p_no_outliers = 1.0 - std::pow(w, 3.0);
-          p_no_outliers = std::max(std::numeric_limits<double>::epsilon(), p_no_outliers);
-          p_no_outliers = std::min(1.0 - std::numeric_limits<double>::epsilon(), p_no_outliers);
-          const double k = std::log(1.0 - 0.99) / std::log(p_no_outliers);
-          const double c = std::ceil(k);
+          const double c = std::ceil(ransac_k((double)(int)nb / (double)nv));
           tab[nv * 65u + nb] = c >= 2147483647.0 ? 0x7FFFFFFFu : (uint32_t)c;
         }
       TOD_HIP(pool->kceil.reserve(tab.size() * sizeof(uint32_t)));
@@ -2818,9 +2682,7 @@ struct Engine {
     TOD_HIP(ws->c_qpt.reserve((size_t)nq * 12)); TOD_HIP(ws->c_obj.reserve(cap * 4));
     TOD_HIP(ws->c_hist.reserve((size_t)n_objs * 4)); TOD_HIP(ws->c_goff.reserve((size_t)n_objs * 4));
     TOD_HIP(ws->c_src.reserve(cap * 4)); TOD_HIP(ws->c_cnt.reserve((size_t)n_objs * 4));
-    TOD_HIP(ws->m_hist.reserve((size_t)n_objs * 4)); TOD_HIP(ws->m_goff.reserve((size_t)n_objs * 4));
-    TOD_HIP(ws->f_train.reserve(cap * 12)); TOD_HIP(ws->f_query.reserve(cap * 12));
-    TOD_HIP(ws->f_qidx.reserve(cap * 4)); TOD_HIP(ws->f_kp.reserve(cap * 8));
+    TOD_HIP(ws->m_hist.reserve((size_t)n_objs * 4));
     TOD_HIP(ws->train.reserve(cap * 12)); TOD_HIP(ws->query.reserve(cap * 12));
     TOD_HIP(ws->qidx.reserve(cap * 4)); TOD_HIP(ws->kpxy.reserve(cap * 8));
     return TODHIP_OK;
@@ -2894,17 +2756,10 @@ struct Engine {
     }
     // more hypothesis evaluations than fit one launch's arguments (a batch of more than 16 frames): one launch all the same
     auto launch_evals = [&](const std::vector<EvalArgs>& v, bool wide, uint32_t lds, bool deferred) {
-      auto ext_it = [](const EvalArgs& a) { return dim3(a.it_end - a.it_begin); };
-      auto ext_def = [](const EvalArgs& a) { return dim3(a.n_deferred); };
-      if (v.size() > kMaxSlots && stage_ok) {
-        const bool ok = wide ? (deferred ? launch_many(st, eval_kernel<true, SlotsPtr<EvalArgs>>, v, 1, ext_def, used, 64u, lds, false)
-                                         : launch_many(st, eval_kernel<true, SlotsPtr<EvalArgs>>, v, 1, ext_it, used, 64u, lds, false))
-                             : (deferred ? launch_many(st, eval_kernel<false, SlotsPtr<EvalArgs>>, v, 1, ext_def, used, 64u, lds, false)
-                                         : launch_many(st, eval_kernel<false, SlotsPtr<EvalArgs>>, v, 1, ext_it, used, 64u, lds, false));
-        if (ok) return;
-      }
-      if (wide) { if (deferred) launch_list(st, eval_kernel<true>, v, 64, lds, 1, ext_def); else launch_list(st, eval_kernel<true>, v, 64, lds, 1, ext_it); }
-      else { if (deferred) launch_list(st, eval_kernel<false>, v, 64, lds, 1, ext_def); else launch_list(st, eval_kernel<false>, v, 64, lds, 1, ext_it); }
+      if (v.size() > kMaxSlots && stage_ok &&
+          pick_eval<SlotsPtr<EvalArgs>>(wide, deferred, [&](auto kern, auto ext) { return launch_many(st, kern, v, 1, ext, used, 64u, lds, false); }))
+        return;
+      pick_eval<Slots<EvalArgs>>(wide, deferred, [&](auto kern, auto ext) { launch_list(st, kern, v, 64, lds, 1, ext); return true; });
     };
     auto words = [](const CopyArgs& a) { return dim3(std::max(1u, std::min(64u, (a.n + 255u) / 256u))); };
     L.copy_in.insert(L.copy_in.end(), L.zero.begin(), L.zero.end());   // both precede every other kernel of the tick: one launch
@@ -2912,11 +2767,6 @@ struct Engine {
     for (size_t i = 0; i < L.sprint.size(); ++i) { L.sprint[i].rnd = L.sprint_src[i]->dev.as<uint32_t>(); L.sprint[i].rnd_len = L.sprint_src[i]->dev_valid; }
     launch_list<kWideSlots>(st, sprint_kernel, L.sprint, kSprintThreads, kSprintLds, 0, [](const SprintArgs&) { return dim3(1); });
     launch_list(st, cluster_frame_kernel, L.cluster, 256, 0, 0, [](const ClusterArgs&) { return dim3(1); });
-    launch_list(st, cluster_lookup_kernel, L.lookup, 256, 0, 1, [](const LookupArgs& a) { return dim3((a.nq + 255u) / 256u); });
-    launch_list(st, cluster_scan_kernel, L.scan, 256, 0, 0, [](const ScanArgs&) { return dim3(1); });
-    launch_list(st, cluster_scatter_kernel, L.scatter, 256, 0, 1,
-                [](const ScatterArgs& a) { return dim3((uint32_t)(((size_t)a.nq * a.k + 255u) / 256u)); });
-    launch_list(st, cluster_group_kernel, L.group, 256, 0, 1, [](const GroupArgs& a) { return dim3((a.n_all + 255u) / 256u); });
     launch_list<kWideSlots>(st, invalidate_kernel, L.inval, 256, 0, 0, [](const InvArgs&) { return dim3(1); });
     {
       auto one = [](const PrepSmallArgs&) { return dim3(1); };
@@ -3022,7 +2872,7 @@ struct Engine {
     return n;
   }
   void describe(char* what, size_t cap) const {
-    snprintf(what, cap, "lookup %zu adj %zu prep %zu draw %zu+%zu chain %zu eval %zu+%zu growth %zu inval %zu sprint %zu", L.lookup.size() + L.cluster.size(),
+    snprintf(what, cap, "lookup %zu adj %zu prep %zu draw %zu+%zu chain %zu eval %zu+%zu growth %zu inval %zu sprint %zu", L.cluster.size(),
              L.adj.size() + L.prep_small.size(), L.prep.size() + L.prep_small.size(), L.draw.size(), L.draw_small.size(), L.chain.size(), L.eval_small.size() + L.eval_direct.size(),
              L.eval_big.size(), L.growth.size(), L.inval.size(), L.sprint.size());
   }
@@ -3142,16 +2992,14 @@ int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy
     int rc = E.reserve_common(s);
     if (rc == TODHIP_OK) rc = E.reserve_cluster(s);
     if (rc != TODHIP_OK) return rc;
-    VerifyWs* ws = s.ws;
     ClusterArgs ca;
     ca.kp_xy = d_kp_xy + 2 * (size_t)f * nq; ca.cloud = nullptr; ca.depth = nullptr; ca.counts = d_counts + (size_t)f * nq;
     ca.matches = d_matches + f * per; ca.mxyz = d_mxyz + 3 * f * per; ca.nq = nq; ca.k = k; ca.H = ca.Wimg = 0xFFFFFFFFu; ca.n_objs = n_objs;
     ca.qidx_add = f * nq; ca.depth_is_u16 = 0; ca.fx = ca.fy = 1.f; ca.cx = ca.cy = 0.f;
-    ca.kept = ws->c_kept.as<uint32_t>(); ca.offs = ws->c_offs.as<uint32_t>(); ca.obj_of = ws->c_obj.as<uint32_t>();
-    ca.src = ws->c_src.as<uint32_t>(); ca.hist = d_hist + (size_t)f * n_objs; ca.goff = d_goff + (size_t)f * n_objs;
-    ca.cnt = ws->c_cnt.as<uint32_t>(); ca.qpt = ws->c_qpt.as<float>();
-    ca.train = d_X + 3 * f * per; ca.query = ws->query.as<float>(); ca.kpxy = ws->kpxy.as<float>(); ca.qidx = d_qidx + f * per;
-    ca.m_hist = ws->m_hist.as<uint32_t>(); ca.m_ctl = d_err + 8 * (size_t)f;       // [0] error, [4] matches kept (device words here)
+    cluster_scratch(ca, s.ws);
+    ca.hist = d_hist + (size_t)f * n_objs; ca.goff = d_goff + (size_t)f * n_objs;
+    ca.train = d_X + 3 * f * per; ca.qidx = d_qidx + f * per;
+    ca.m_ctl = d_err + 8 * (size_t)f;                          // [0] error, [4] matches kept (device words here)
     v.push_back(ca);
   }
   launch_list(ctx->stream, cluster_frame_kernel, v, 256, 0, 0, [](const ClusterArgs&) { return dim3(1); });
@@ -3162,11 +3010,9 @@ int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy
 void tod_verify_ws_free(todhip_ctx* ctx) {
   if (!ctx->verify_ws) return;
   VerifyPool* p = reinterpret_cast<VerifyPool*>(ctx->verify_ws);
-  for (VerifyWs* ws : p->slots) { ws->release(); delete ws; }
-  for (StreamCache* c : p->streams) { c->dev.release(); delete c; }
+  for (VerifyWs* ws : p->slots) delete ws;
+  for (StreamCache* c : p->streams) delete c;
   for (hipEvent_t e : p->side_ev) (void)hipEventDestroy(e);
-  for (size_t i = 0; i < VerifyPool::kMaxLanes; ++i) { p->args_stage[i].release(); p->args_dev[i].release(); }
-  p->kceil.release();
   delete p;
   ctx->verify_ws = nullptr;
 }
@@ -3464,16 +3310,11 @@ int todhip_test_consensus(todhip_ctx* ctx, const float* train, const float* quer
               [](const AdjArgs& a) { return dim3(a.job.n, (a.job.W + 3u) / 4u); });
   launch_list<kManySlots>(st, round_prep_kernel<Slots<PrepArgs, kManySlots>>, std::vector<PrepArgs>{{job, d_small + 5, nullptr, 0u}}, 256, 0, 1,
               [](const PrepArgs& a) { return dim3((a.job.n + 255u) / 256u); });
-  EvalArgs A;
-  A.job = job; A.iter_samples = ws->iter_samples.as<uint32_t>(); A.it_begin = 0; A.it_end = n_triples;
-  A.counts = ws->counts.as<int32_t>(); A.gate_m = ws->gate_m.as<uint32_t>(); A.work = d_small + 8;
-  A.status = d_small + 12; A.deferred = ws->deferred.as<uint32_t>(); A.stacks = ws->stacks.as<uint16_t>();
-  A.stack_cap = kStackCap; A.lds_bytes = kEvalLdsSmall; A.from_deferred = 0; A.n_deferred = 0;
-  A.adjc_scratch = nullptr; A.n_items_dev = nullptr;
+  EvalArgs A = eval_args(job, ws, ws->counts.as<int32_t>(), 0u, n_triples, kEvalLdsSmall);
   A.dbg = dbg ? ws->table.as<uint32_t>() : nullptr; A.dbg_stride = dbg_stride; A.stop_level = stop_level;
   if (n_triples > kMaxEvalWaves) return TODHIP_EINVAL;
-  if (W <= 8u) launch_list(st, eval_kernel<false>, std::vector<EvalArgs>{A}, 64, kEvalLdsSmall, 1, [](const EvalArgs& a) { return dim3(a.it_end - a.it_begin); });
-  else launch_list(st, eval_kernel<true>, std::vector<EvalArgs>{A}, 64, kEvalLdsSmall, 1, [](const EvalArgs& a) { return dim3(a.it_end - a.it_begin); });
+  auto launch = [&](auto kern, auto ext) { launch_list(st, kern, std::vector<EvalArgs>{A}, 64, A.lds_bytes, 1, ext); return true; };
+  pick_eval<Slots<EvalArgs>>(W > 8u, false, launch);
   TOD_HIP(hipGetLastError());
   TOD_HIP(hipMemcpyAsync(h_small + 12, d_small + 12, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   TOD_HIP(hipStreamSynchronize(st));
@@ -3483,8 +3324,7 @@ int todhip_test_consensus(todhip_ctx* ctx, const float* train, const float* quer
     TOD_HIP(ws->adjc_scratch.reserve((size_t)n_def * kAdjcScratchWords * sizeof(u64)));
     A.adjc_scratch = ws->adjc_scratch.as<u64>();
     TOD_HIP(hipMemsetAsync(d_small + 8, 0, sizeof(uint32_t), st));
-    if (W <= 8u) launch_list(st, eval_kernel<false>, std::vector<EvalArgs>{A}, 64, kEvalLdsBig, 1, [](const EvalArgs& a) { return dim3(a.n_deferred); });
-    else launch_list(st, eval_kernel<true>, std::vector<EvalArgs>{A}, 64, kEvalLdsBig, 1, [](const EvalArgs& a) { return dim3(a.n_deferred); });
+    pick_eval<Slots<EvalArgs>>(W > 8u, true, launch);
     TOD_HIP(hipGetLastError());
     TOD_HIP(hipMemcpyAsync(h_small + 12, d_small + 12, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     TOD_HIP(hipStreamSynchronize(st));
