@@ -1,6 +1,6 @@
 // C ABI entry points of libtodhip (include/todhip.h): context lifetime, DB ingest (stage B1),
 // and the host-buffer / device-buffer forms of the matcher. The verifier and ORB entry points live
-// in verify.hip and orb.hip.
+// in verify.hip (test hooks: verify_hooks.h) and orb.hip.
 #include <algorithm>
 #include <atomic>
 #include <cfloat>

@@ -161,6 +161,7 @@ int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_s
 // verify.hip / orb.hip
 void tod_verify_ws_free(todhip_ctx* ctx);
 // verify.hip: ClusterPerObject of F frames on the device without a cloud (pnp.hip's 2D-only branch); d_err: 8 words per frame
+// (ClusterCtl of verify_kernels.h: word 0 = error, word 4 = matches kept)
 int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy, uint32_t nq, const uint32_t* d_counts,
                                const todhip_dmatch* d_matches, const float* d_mxyz, uint32_t k, uint32_t n_objs, float* d_X,
                                uint32_t* d_qidx, uint32_t* d_hist, uint32_t* d_goff, uint32_t* d_err);

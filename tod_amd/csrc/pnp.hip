@@ -549,7 +549,7 @@ extern "C" int todhip_verify_2d(todhip_ctx* ctx, const float* kp_xy, uint32_t nq
 }
 
 // Device-resident forms: keypoints and the matcher's fixed-stride outputs (exactly what todhip_match_device / todhip_merge_shards_device
-// produced, for n_frames * nq queries) are in HBM and stay there: ClusterPerObject runs on the device (verify.hip's cluster_frame_kernel
+// produced, for n_frames * nq queries) are in HBM and stay there: ClusterPerObject runs on the device (verify_prep.h's cluster_frame_kernel
 // in its cloudless mode, one block per frame), pnp_active_kernel lists the objects worth a RANSAC, the host reads ONE word (their
 // number, for the grids) and launches hypotheses + refinement; the flags, the results and the keypoint indices of the matches come
 // back once, at the end. Each frame's result is the host-buffer call's (tests/test_pnp_gpu.py).

@@ -1,0 +1,155 @@
+// The todhip_test_* entry points: single kernels of the verifier driven from tests (FillAdjacency, selectWithinDistance for given
+// triples, the clique search on an explicit graph as in the reference's test/test_maximum_clique.cpp).
+// Included last by verify.hip, after its anonymous namespace and C entry points.
+
+extern "C" {
+
+int todhip_test_adjacency(todhip_ctx* ctx, const float* train, const float* query, const float* kpxy, uint32_t n,
+                          float span, float err, uint64_t* phys, uint64_t* samp) {
+  if (!ctx || !train || !query || !kpxy || !phys || !samp || n == 0 || n > (uint32_t)kMaxWords * 64u) return TODHIP_EINVAL;
+  TOD_HIP(hipSetDevice(ctx->device));
+  VerifyWs* ws = ws_of(ctx);
+  const uint32_t W = (n + 63u) / 64u;
+  hipStream_t st = ctx->stream;
+  TOD_HIP(ws->train.reserve((size_t)n * 12)); TOD_HIP(ws->query.reserve((size_t)n * 12));
+  TOD_HIP(ws->kpxy.reserve((size_t)n * 8));
+  TOD_HIP(ws->phys.reserve((size_t)n * W * 8)); TOD_HIP(ws->samp.reserve((size_t)n * W * 8));
+  TOD_HIP(ws->bits.reserve((size_t)8 * W * 8));
+  TOD_HIP(hipMemcpyAsync(ws->train.p, train, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->query.p, query, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->kpxy.p, kpxy, (size_t)n * 8, hipMemcpyHostToDevice, st));
+  ObjJob job;
+  std::memset(&job, 0, sizeof(job));
+  job.n = n; job.W = W;
+  job.train = ws->train.as<float>(); job.query = ws->query.as<float>(); job.kpxy = ws->kpxy.as<float>();
+  job.phys = ws->phys.as<u64>(); job.samp = ws->samp.as<u64>();
+  launch_list<kManySlots>(st, adjacency_kernel<Slots<AdjArgs, kManySlots>>, std::vector<AdjArgs>{{job, span, err}}, 256, 0, 2,
+              [](const AdjArgs& a) { return dim3(a.job.n, (a.job.W + 3u) / 4u); });
+  TOD_HIP(hipGetLastError());
+  TOD_HIP(hipMemcpyAsync(phys, ws->phys.p, (size_t)n * W * 8, hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipMemcpyAsync(samp, ws->samp.p, (size_t)n * W * 8, hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));
+  return TODHIP_OK;
+}
+
+// Test hook: FillAdjacency + selectWithinDistance (sac_model_registration_graph.h:171-269) for given sample
+// triples (samples_ order). counts[t] = consensus size (0 = rejected by the gate). With stop_level 1 the clique
+// search is skipped and counts[t] = -|F| for hypotheses that reach it. dbg (optional): dbg_stride words per triple.
+int todhip_test_consensus(todhip_ctx* ctx, const float* train, const float* query, const float* kpxy, uint32_t n,
+                          float span, float err, const uint32_t* triples, uint32_t n_triples, uint32_t stop_level,
+                          int32_t* counts, uint32_t* dbg, uint32_t dbg_stride) {
+  if (!ctx || !train || !query || !kpxy || !triples || !counts || n < 3 || n > (uint32_t)kMaxWords * 64u || n_triples == 0)
+    return TODHIP_EINVAL;
+  TOD_HIP(hipSetDevice(ctx->device));
+  int rc = set_big_lds_once(ctx);
+  if (rc != TODHIP_OK) return rc;
+  VerifyWs* ws = ws_of(ctx);
+  const uint32_t W = (n + 63u) / 64u;
+  hipStream_t st = ctx->stream;
+  TOD_HIP(ws->train.reserve((size_t)n * 12)); TOD_HIP(ws->query.reserve((size_t)n * 12));
+  TOD_HIP(ws->qidx.reserve((size_t)n * 4)); TOD_HIP(ws->kpxy.reserve((size_t)n * 8));
+  TOD_HIP(ws->phys.reserve((size_t)n * W * 8)); TOD_HIP(ws->samp.reserve((size_t)n * W * 8));
+  TOD_HIP(ws->bits.reserve((size_t)8 * W * 8)); TOD_HIP(ws->sampdeg.reserve((size_t)n * 4));
+  TOD_HIP(ws->small.reserve(256 * sizeof(uint32_t))); TOD_HIP(ws->h_small.reserve(256 * sizeof(uint32_t)));
+  TOD_HIP(ws->iter_samples.reserve((size_t)n_triples * 12)); TOD_HIP(ws->counts.reserve((size_t)n_triples * 4));
+  TOD_HIP(ws->gate_m.reserve((size_t)n_triples * 4)); TOD_HIP(ws->deferred.reserve((size_t)n_triples * 4));
+  TOD_HIP(ws->stacks.reserve((size_t)kMaxEvalWaves * kStackCap * sizeof(uint16_t)));
+  if (dbg) TOD_HIP(ws->table.reserve((size_t)n_triples * dbg_stride * 4));
+  TOD_HIP(hipMemcpyAsync(ws->train.p, train, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->query.p, query, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->kpxy.p, kpxy, (size_t)n * 8, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->iter_samples.p, triples, (size_t)n_triples * 12, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemsetAsync(ws->qidx.p, 0, (size_t)n * 4, st));
+  if (dbg) TOD_HIP(hipMemsetAsync(ws->table.p, 0, (size_t)n_triples * dbg_stride * 4, st));
+  ObjJob job;
+  job.n = n; job.W = W;
+  job.train = ws->train.as<float>(); job.query = ws->query.as<float>(); job.qidx = ws->qidx.as<uint32_t>();
+  job.kpxy = ws->kpxy.as<float>(); job.phys = ws->phys.as<u64>(); job.samp = ws->samp.as<u64>();
+  u64* bits = ws->bits.as<u64>();
+  job.finite = bits; job.valid = bits + W; job.deg7 = bits + 2 * W; job.sampdeg = ws->sampdeg.as<uint32_t>();
+  SlotCtl* d_ctl = ws->small.as<SlotCtl>();
+  EvalStatus* h_eval = &ws->h_small.as<SlotCtl>()->eval;
+  TOD_HIP(hipMemsetAsync(d_ctl, 0, sizeof(SlotCtl), st));
+  launch_list<kManySlots>(st, finite_kernel<Slots<JobArgs, kManySlots>>, std::vector<JobArgs>{{job}}, 256, 0, 1, [](const JobArgs& a) { return dim3((a.job.n + 255u) / 256u); });
+  launch_list<kManySlots>(st, adjacency_kernel<Slots<AdjArgs, kManySlots>>, std::vector<AdjArgs>{{job, span, err}}, 256, 0, 2,
+              [](const AdjArgs& a) { return dim3(a.job.n, (a.job.W + 3u) / 4u); });
+  launch_list<kManySlots>(st, round_prep_kernel<Slots<PrepArgs, kManySlots>>, std::vector<PrepArgs>{{job, d_ctl->prep, nullptr, 0u}}, 256, 0, 1,
+              [](const PrepArgs& a) { return dim3((a.job.n + 255u) / 256u); });
+  EvalArgs A = eval_args(job, ws, ws->counts.as<int32_t>(), 0u, n_triples, kEvalLdsSmall);
+  A.dbg = dbg ? ws->table.as<uint32_t>() : nullptr; A.dbg_stride = dbg_stride; A.stop_level = stop_level;
+  if (n_triples > kMaxEvalWaves) return TODHIP_EINVAL;
+  auto launch = [&](auto, auto kern, auto ext) { launch_list(st, kern, std::vector<EvalArgs>{A}, 64, A.lds_bytes, 1, ext); };
+  pick_eval(W > 8u, false, launch);
+  TOD_HIP(hipGetLastError());
+  TOD_HIP(hipMemcpyAsync(h_eval, &d_ctl->eval, sizeof(EvalStatus), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));
+  const uint32_t status = h_eval->error, n_def = h_eval->n_deferred;
+  if (status == 0 && n_def > 0) {
+    A.lds_bytes = kEvalLdsBig; A.from_deferred = 1; A.n_deferred = n_def;
+    TOD_HIP(ws->adjc_scratch.reserve((size_t)n_def * kAdjcScratchWords * sizeof(u64)));
+    A.adjc_scratch = ws->adjc_scratch.as<u64>();
+    TOD_HIP(hipMemsetAsync(&d_ctl->eval_work, 0, sizeof(uint32_t), st));
+    pick_eval(W > 8u, true, launch);
+    TOD_HIP(hipGetLastError());
+    TOD_HIP(hipMemcpyAsync(h_eval, &d_ctl->eval, sizeof(EvalStatus), hipMemcpyDeviceToHost, st));
+    TOD_HIP(hipStreamSynchronize(st));
+  }
+  TOD_HIP(hipMemcpyAsync(counts, ws->counts.p, (size_t)n_triples * 4, hipMemcpyDeviceToHost, st));
+  if (dbg) TOD_HIP(hipMemcpyAsync(dbg, ws->table.p, (size_t)n_triples * dbg_stride * 4, hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));
+  if (h_eval->error != 0) {
+    TOD_DBG("consensus status %u: g=%u value=%u m=%u it=%u", h_eval->error, h_eval->detail_g, h_eval->detail_value, h_eval->detail_m, h_eval->detail_it);
+    return TODHIP_ESCRATCH;
+  }
+  return TODHIP_OK;
+}
+
+// Test hook: the clique search on an explicit graph (edges as pairs), FindClique(minimal_size).
+// out3 = {clique size, error flag, steps}. Mirrors the reference's gtest shape (test/test_maximum_clique.cpp).
+static int test_clique_impl(todhip_ctx* ctx, uint32_t m, const uint32_t* edges, uint32_t n_edges, uint32_t minimal_size,
+                            uint32_t* out3, bool gate) {
+  if (!ctx || !out3 || m == 0 || m > 1024 || (n_edges && !edges)) return TODHIP_EINVAL;
+  TOD_HIP(hipSetDevice(ctx->device));
+  int rc = set_big_lds_once(ctx);
+  if (rc != TODHIP_OK) return rc;
+  VerifyWs* ws = ws_of(ctx);
+  const uint32_t MW = (m + 63u) / 64u;
+  std::vector<u64> adj((size_t)m * MW, 0ull);
+  for (uint32_t e = 0; e < n_edges; ++e) {
+    const uint32_t a = edges[2 * e], b = edges[2 * e + 1];
+    if (a >= m || b >= m || a == b) return TODHIP_EINVAL;
+    adj[(size_t)a * MW + (b >> 6)] |= 1ull << (b & 63u);
+    adj[(size_t)b * MW + (a >> 6)] |= 1ull << (a & 63u);
+  }
+  TOD_HIP(ws->clique_adj.reserve(adj.size() * 8 + 64));
+  TOD_HIP(ws->stacks.reserve((size_t)kStackCap * sizeof(uint16_t)));
+  TOD_HIP(ws->small.reserve(256 * sizeof(uint32_t)));
+  TOD_HIP(hipMemcpyAsync(ws->clique_adj.p, adj.data(), adj.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (gate_lds_bytes(m) > kEvalLdsBig) return TODHIP_ESCRATCH;
+  const uint32_t lds = gate_lds_bytes(m) <= kEvalLdsSmall ? kEvalLdsSmall : kEvalLdsBig;   // the two LDS tiers of eval_kernel
+  if (gate)
+    hipLaunchKernelGGL(clique_test_kernel<true>, dim3(1), dim3(64), lds, ctx->stream, ws->clique_adj.as<u64>(), m, minimal_size,
+                       ws->stacks.as<uint16_t>(), kStackCap, lds, ws->small.as<uint32_t>());
+  else
+    hipLaunchKernelGGL(clique_test_kernel<false>, dim3(1), dim3(64), lds, ctx->stream, ws->clique_adj.as<u64>(), m, minimal_size,
+                       ws->stacks.as<uint16_t>(), kStackCap, lds, ws->small.as<uint32_t>());
+  TOD_HIP(hipGetLastError());
+  TOD_HIP(hipMemcpyAsync(out3, ws->small.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  TOD_HIP(hipStreamSynchronize(ctx->stream));
+  return TODHIP_OK;
+}
+
+int todhip_test_clique(todhip_ctx* ctx, uint32_t m, const uint32_t* edges, uint32_t n_edges, uint32_t minimal_size,
+                       uint32_t* out3) {
+  return test_clique_impl(ctx, m, edges, n_edges, minimal_size, out3, false);
+}
+
+// The same graph through the form of the search the verifier's gate runs (clique_search<., kGate = true>): it stops as soon as
+// "is the clique FindClique(minimal_size) returns larger than minimal_size" is decided, so out3[0] is that clique's size only
+// when it is <= minimal_size, and a lower bound > minimal_size otherwise; out3[2] counts the steps actually walked.
+int todhip_test_clique_gate(todhip_ctx* ctx, uint32_t m, const uint32_t* edges, uint32_t n_edges, uint32_t minimal_size,
+                            uint32_t* out3) {
+  return test_clique_impl(ctx, m, edges, n_edges, minimal_size, out3, true);
+}
+
+}  // extern "C"

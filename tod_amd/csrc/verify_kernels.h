@@ -1,10 +1,14 @@
 // Stage C device code (gfx950): the graph-constrained RANSAC verifier of wg-perception/tod.
 // Reference: src/common/adjacency_ransac.cpp, sac_model_registration_graph.h, ransac.h, maximum_clique.cpp.
 // All adjacency is kept as bit matrices (n rows of W 64-bit words); one wave owns one hypothesis.
+// Holds what more than one of the verify_*.h headers needs: ObjJob, the draw table entry, the result structs kernels hand to the
+// host and the layout of the slot's control block and mailbox they sit in, wave helpers, float helpers. Precedes every other
+// verifier header.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace tod {
@@ -44,11 +48,77 @@ struct ChainOut {       // result of walking the draw table (getSamples x iterat
   uint32_t flag;        // 0 = all requested iterations drawn, 1 = window exhausted, 2 = selection empty (1000 failures)
 };
 
+// status words of hypothesis evaluations (gate_eval): counters accumulate over the launches of one batch
+struct EvalStatus {
+  uint32_t error;        // 0 = none, 1 = clique search failed, 2 = graph too large for any tier, 3 = corrupt draw table, 4 = bad index
+  uint32_t gate_calls;   // hypotheses that reached the clique search
+  uint32_t n_deferred;   // hypotheses left to the big-LDS pass (length of EvalArgs::deferred)
+  uint32_t pad_;
+  uint32_t detail_g, detail_value, detail_m, detail_it;   // diagnostics of an error: graph index, its value, |F|, iteration
+};
+
+struct GrowthOut {      // result of growth_kernel
+  float R[9], T[3];             // inverted pose (training -> camera), adjacency_ransac.cpp:304-305
+  uint32_t n_match_inliers;     // match indices in the grown set
+  uint32_t n_kp_inliers;        // unique keypoint indices (:306-308)
+  uint32_t passes;
+  uint32_t n_model_inliers;
+};
+
+// what cluster_frame_kernel reports per frame (ClusterArgs::m_ctl); an array of these is the d_err of tod_cluster_frames_nocloud
+struct ClusterCtl {
+  uint32_t error, pad1_[3];     // != 0: the frame's inputs were refused
+  uint32_t n_kept, pad5_[3];    // matches kept (n_all)
+};
+
+// The control block of one frame slot, 64 words of device memory (VerifyWs::small) that a tick's last kernel copies to the slot's
+// mailbox (pinned host memory, VerifyWs::m_small). The mailbox form has the same head and a tail that only the host side has:
+// cluster_frame_kernel writes it straight into the mailbox.
+template <class Tail>
+struct SlotWords {
+  uint32_t pad0_;
+  ChainOut chain;               // chain_kernel; chain.n_done also bounds the evaluation launched in the same tick
+  uint32_t prep[3];             // round_prep_kernel's statistics: |valid|, sum of sample degrees inside valid, triangle found
+  uint32_t eval_work;           // EvalArgs::work
+  uint32_t pad9_[3];
+  EvalStatus eval;
+  uint32_t pad20_[12];
+  GrowthOut growth;
+  uint32_t pad48_[12];
+  Tail tail;
+};
+struct SlotCtlTail { uint32_t pad60_[4]; };
+struct SlotMailTail { ClusterCtl cluster; uint32_t pad68_[60]; };
+typedef SlotWords<SlotCtlTail> SlotCtl;
+typedef SlotWords<SlotMailTail> SlotMail;
+constexpr uint32_t kMailSmallWords = 128u;         // [0, 64) = the slot's device control words, then the rest of ClusterCtl
+
+#define TOD_WORD_AT(T, member, word) static_assert(offsetof(T, member) == (word) * 4u, #T "::" #member " moved")
+TOD_WORD_AT(EvalStatus, error, 0); TOD_WORD_AT(EvalStatus, gate_calls, 1); TOD_WORD_AT(EvalStatus, n_deferred, 2);
+TOD_WORD_AT(EvalStatus, detail_g, 4); TOD_WORD_AT(EvalStatus, detail_value, 5); TOD_WORD_AT(EvalStatus, detail_m, 6);
+TOD_WORD_AT(EvalStatus, detail_it, 7);
+TOD_WORD_AT(ClusterCtl, error, 0); TOD_WORD_AT(ClusterCtl, n_kept, 4);
+TOD_WORD_AT(SlotCtl, chain, 1); TOD_WORD_AT(SlotCtl, prep, 5); TOD_WORD_AT(SlotCtl, eval_work, 8); TOD_WORD_AT(SlotCtl, eval, 12);
+TOD_WORD_AT(SlotCtl, growth, 32); TOD_WORD_AT(SlotCtl, tail, 60);
+TOD_WORD_AT(SlotMail, chain, 1); TOD_WORD_AT(SlotMail, prep, 5); TOD_WORD_AT(SlotMail, eval_work, 8); TOD_WORD_AT(SlotMail, eval, 12);
+TOD_WORD_AT(SlotMail, growth, 32); TOD_WORD_AT(SlotMail, tail.cluster.error, 60); TOD_WORD_AT(SlotMail, tail.cluster.n_kept, 64);
+static_assert(sizeof(EvalStatus) == 8 * 4 && sizeof(ChainOut) == 4 * 4 && sizeof(GrowthOut) == 16 * 4 && sizeof(ClusterCtl) == 8 * 4, "mailbox layout");
+static_assert(sizeof(SlotCtl) == 64 * 4 && sizeof(SlotMail) == kMailSmallWords * 4, "mailbox layout");
+
+#undef TOD_WORD_AT
+
 // ---------------------------------------------------------------------------------------------- wave helpers
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 
 // wave-uniform value -> SGPR: branches on it are scalar, so the compiler cannot split the wave's lanes
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+__device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t lane) {    // lane is wave-uniform: v_readlane_b32
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
+}
+__device__ __forceinline__ u64 rdlane64(u64 v, uint32_t lane) {
+  return ((u64)rdlane((uint32_t)(v >> 32), lane) << 32) | rdlane((uint32_t)v, lane);
+}
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll

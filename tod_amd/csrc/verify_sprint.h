@@ -1,4 +1,5 @@
-// Included by verify.hip inside its anonymous namespace, after eval_kernel / growth_kernel / invalidate_kernel.
+// Included by verify.hip inside its anonymous namespace, after verify_kernels.h, verify_launch.h (Slots), verify_clique.h,
+// verify_eval.h (EvalArgs, gate_eval) and verify_growth.h (kabsch_solve, growth_admits, pose_invert).
 //
 // sprint_kernel: the small objects of a frame, verified from the first draw to the last invalidation by ONE workgroup, with no host
 // round trip in between. A frame of self-similar texture spreads its matches over a couple of hundred objects
@@ -50,12 +51,31 @@ constexpr uint32_t kSprintMaxObjs = 48;        // live objects per launch
 enum { SPRINT_DONE = 0, SPRINT_NEED_STREAM = 1, SPRINT_FULL = 2, SPRINT_ERROR = 3 };
 constexpr uint32_t DRAW_LONG = 3;              // the attempt ran past the staged part of the stream: the window ends in front of it
 
-// header (words): [0] records written, [1] exit reason, [2] objects completed, [3..4] stream position at exit (of the last completed
-// round), [5] gate calls, [6] hypotheses evaluated, [7] error detail, [8] windows, [9..15] s_memtime ticks (100 MHz) spent staging the
-// stream / in the attempts / the walk / the evaluation / the bookkeeping / the growth / in all
-// record (words): [0] index of the object in the launch's list, [1] iterations, [2] best iteration, [3] best count (int), [4..5] draws
-// consumed by the round, [6] inlier keypoints, [7] 1 = growth ran (n_best > 0), [8..16] R, [17..19] T (inverted pose), [20] offset of
-// the keypoint list in kp_out, [21] match inliers, [22] growth passes, [23] model inliers
+// what a launch leaves in SprintArgs::out: one header, then one record per round
+struct SprintHeader {
+  uint32_t n_rec, reason, n_done;          // records written, exit reason (SPRINT_*), objects completed
+  uint32_t pos_lo, pos_hi;                 // stream position at exit (of the last completed round)
+  uint32_t gate_calls, hypotheses;         // gate calls, hypotheses evaluated
+  uint32_t err_detail, n_windows;
+  uint32_t t_ring, t_att, t_walk, t_eval, t_book, t_grow, t_all;   // s_memtime ticks (100 MHz) spent staging the stream / in the
+                                           // attempts / the walk / the evaluation / the bookkeeping / the growth / in all
+};
+struct SprintRecord {
+  uint32_t obj;                            // index of the object in the launch's list
+  uint32_t iterations, best_it;
+  int32_t n_best;                          // best count
+  uint32_t consumed_lo, consumed_hi;       // draws consumed by the round (64 bits)
+  uint32_t n_kp, grew;                     // inlier keypoints; 1 = growth ran (n_best > 0)
+  float R[9], T[3];                        // inverted pose
+  uint32_t kp_offset;                      // offset of the keypoint list in kp_out
+  uint32_t n_match, passes, n_model;       // match inliers, growth passes, model inliers
+  uint32_t pad24_[8];
+};
+static_assert(sizeof(SprintHeader) == kSprintHdrWords * 4 && sizeof(SprintRecord) == kSprintRecWords * 4, "sprint output layout");
+static_assert(offsetof(SprintHeader, pos_lo) == 3 * 4 && offsetof(SprintHeader, gate_calls) == 5 * 4 && offsetof(SprintHeader, t_all) == 15 * 4, "sprint output layout");
+static_assert(offsetof(SprintRecord, consumed_lo) == 4 * 4 && offsetof(SprintRecord, consumed_hi) == 5 * 4 && offsetof(SprintRecord, R) == 8 * 4 &&
+              offsetof(SprintRecord, T) == 17 * 4 && offsetof(SprintRecord, kp_offset) == 20 * 4 && offsetof(SprintRecord, n_model) == 23 * 4, "sprint output layout");
+__host__ __device__ inline SprintRecord* sprint_records(uint32_t* out) { return reinterpret_cast<SprintRecord*>(out + kSprintHdrWords); }
 struct SprintObj { ObjJob job; uint64_t skip; uint32_t index, pad; };   // skip: draws consumed by the objects the host skipped before it
 struct SprintArgs {
   const SprintObj* objs;          // pinned host memory, read directly
@@ -65,7 +85,7 @@ struct SprintArgs {
   const uint32_t* kceil;          // 65 x 65: ceil(k) per (|valid|, n_best)
   uint32_t* out;                  // header + records (pinned host memory)
   uint32_t* kp_out;               // inlier keypoint lists (pinned host memory)
-  uint32_t* status;               // gate_eval's status words (device)
+  EvalStatus* status;             // gate_eval's status words (device)
   uint16_t* stack;                // gate_eval's global level stacks (kSprintWaves x kSprintStackCap)
   uint32_t n_objs, max_iterations, min_inliers;
   float err;
@@ -503,9 +523,9 @@ __global__ __launch_bounds__(kSprintThreads) void sprint_kernel(Slots<SprintArgs
           float Ro[9], To[3];
           pose_invert(R, T, Ro, To);                                   // :304-305
           if (tid == 0u) {
-            uint32_t* rec = A.out + kSprintHdrWords + (size_t)n_rec * kSprintRecWords;
-            for (int e = 0; e < 9; ++e) rec[8 + e] = __float_as_uint(Ro[e]);
-            for (int e = 0; e < 3; ++e) rec[17 + e] = __float_as_uint(To[e]);
+            SprintRecord* rec = sprint_records(A.out) + n_rec;
+            for (int e = 0; e < 9; ++e) rec->R[e] = Ro[e];
+            for (int e = 0; e < 3; ++e) rec->T[e] = To[e];
           }
           if (n_kp >= A.min_inliers) {
             // ---- InvalidateQueryIndices (:93-123): every valid match whose keypoint is an inlier keypoint, then
@@ -537,11 +557,11 @@ __global__ __launch_bounds__(kSprintThreads) void sprint_kernel(Slots<SprintArgs
       }
       // ---- the round's record
       if (tid == 0u) {
-        uint32_t* rec = A.out + kSprintHdrWords + (size_t)n_rec * kSprintRecWords;
+        SprintRecord* rec = sprint_records(A.out) + n_rec;
         const u64 consumed = obj_pos - round_pos;
-        rec[0] = j; rec[1] = iterations; rec[2] = best_it; rec[3] = (uint32_t)n_best;
-        rec[4] = (uint32_t)consumed; rec[5] = (uint32_t)(consumed >> 32);
-        rec[6] = n_kp; rec[7] = grew; rec[20] = kp_used; rec[21] = n_match; rec[22] = passes; rec[23] = n_model;
+        rec->obj = j; rec->iterations = iterations; rec->best_it = best_it; rec->n_best = (int32_t)n_best;
+        rec->consumed_lo = (uint32_t)consumed; rec->consumed_hi = (uint32_t)(consumed >> 32);
+        rec->n_kp = n_kp; rec->grew = grew; rec->kp_offset = kp_used; rec->n_match = n_match; rec->passes = passes; rec->n_model = n_model;
       }
       kp_used += n_kp;
       ++n_rec;
@@ -551,11 +571,12 @@ __global__ __launch_bounds__(kSprintThreads) void sprint_kernel(Slots<SprintArgs
     ++n_done_objs;
   }
   if (tid == 0u) {
-    A.out[0] = n_rec; A.out[1] = reason; A.out[2] = n_done_objs;
-    A.out[3] = (uint32_t)pos; A.out[4] = (uint32_t)(pos >> 32);
-    A.out[5] = __hip_atomic_load(A.status + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / kSprintWaves;   // every wave ran every gate
-    A.out[6] = hyps; A.out[7] = err_detail; A.out[8] = n_windows;
-    A.out[9] = (uint32_t)t_ring; A.out[10] = (uint32_t)t_att; A.out[11] = (uint32_t)t_walk; A.out[12] = (uint32_t)t_eval;
-    A.out[13] = (uint32_t)t_book; A.out[14] = (uint32_t)t_grow; A.out[15] = (uint32_t)(clock64() - t_begin);
+    SprintHeader* hdr = reinterpret_cast<SprintHeader*>(A.out);
+    hdr->n_rec = n_rec; hdr->reason = reason; hdr->n_done = n_done_objs;
+    hdr->pos_lo = (uint32_t)pos; hdr->pos_hi = (uint32_t)(pos >> 32);
+    hdr->gate_calls = __hip_atomic_load(&A.status->gate_calls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / kSprintWaves;   // every wave ran every gate
+    hdr->hypotheses = hyps; hdr->err_detail = err_detail; hdr->n_windows = n_windows;
+    hdr->t_ring = (uint32_t)t_ring; hdr->t_att = (uint32_t)t_att; hdr->t_walk = (uint32_t)t_walk; hdr->t_eval = (uint32_t)t_eval;
+    hdr->t_book = (uint32_t)t_book; hdr->t_grow = (uint32_t)t_grow; hdr->t_all = (uint32_t)(clock64() - t_begin);
   }
 }
