@@ -1,6 +1,6 @@
 """Build-time checks on the generated gfx950 code (no GPU needed: hipcc cross-compiles).
 
-K4 (tod_amd/csrc/match.hip, hamming_topk_tiles) issues its DB-row prefetches as hand-written `s_load_dwordx16` pairs and waits
+K4 (hamming_topk_tiles in tod_amd/csrc/match_valu.h, a part of the translation unit match.hip) issues its DB-row prefetches as hand-written `s_load_dwordx16` pairs and waits
 for them with a hand-written `s_waitcnt lgkmcnt(0)`; hipcc does not know that the destination SGPRs are in flight in
 between. The design is only correct while the compiler neither reads, copies nor spills those registers between an issue
 and its wait -- which nothing but the generated code can confirm, so this test disassembles it (same compiler, same flags

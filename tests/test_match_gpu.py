@@ -434,11 +434,32 @@ def test_ratio_test_sharded_equals_unsharded(ctx):
         assert np.array_equal(m[f], o_m[f]), f
 
 
+@pytest.mark.parametrize("nq,n_rows", [(64, 65573), (64, 100003), (17, 6311)])
+def test_launch_plans_the_other_tests_do_not_reach(ctx, nq, n_rows):
+    """Launch shapes of the tiling plan (match_launch.h) beside those of the tests above, k = 2, radius 35, near rows planted in the
+    first tile, across tile borders and in the DB's last, partial step. On an MI355X (256 CUs):
+    64 x 65 573: two query blocks per wave over 228 tiles of 288 rows on the matrix cores -- not a multiple of 8, so the work items
+        are decoded through the virtual block id -- and 1025 tiles of 64 rows on the vector ALU, the counting merge on both;
+    64 x 100 003: 348 tiles of 288 rows on the matrix cores, i.e. >= 256 tiles for <= 64 queries: the wave merge;
+    17 x 6 311: the <= 32-query kernel with three tiles of 2112 rows, the last one 65 full steps and one of 7 rows.
+    (33 x 4 099, two query blocks with a masked tail, is test_ragged_query_counts[63], [64]: 11 tiles of 288 rows, the last 228.)"""
+    desc, pts, off = synth.make_db_ragged([n_rows // 3, n_rows - n_rows // 3], seed=n_rows)
+    rng = np.random.Generator(np.random.PCG64(nq))
+    q = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+    for qi, rows in ((0, (0, 5)), (nq // 2, (n_rows // 2, n_rows // 2 + 1)), (nq - 1, (n_rows - 1, 2111, 2112, 287, 288)), (3, (n_rows - 2,))):
+        for j, r in enumerate(rows):
+            desc[r] = q[qi]
+            desc[r, j] ^= 0x0F >> (j % 3)                    # distances 4, 3, 2, 4, 3: ranks differ from the row order
+    assert _assert_same(ctx, desc, pts, off, q, 2, 35) == 7
+
+
 def test_block_split_adapts_to_the_data():
     """The matrix-core engine's partial-distance elimination picks its block form from the launches' own statistics:
     rows that agree with the queries on the bit positions of the first 2 (3) of a block's 4 matrix instructions and differ on all
     the others make every block survive that split, so the context moves up a level after one report, holds it for 32 launches,
-    probes one level down once, and goes on; on independent bits it stays with the 2-split. Results == oracle on every launch."""
+    probes one level down once, and goes on; on independent bits it stays with the 2-split. Results == oracle on every launch.
+    The first case follows the hold through two failed probes: the hold a probe starts is the length in force when it is taken (32,
+    then 32 again), and the doubling that a failed probe's report causes applies from the next probe on (64)."""
     rng = np.random.default_rng(3)
     q1 = rng.integers(0, 256, 32, dtype=np.uint8)
     nq, n_rows = 1024, 20000
@@ -453,7 +474,7 @@ def test_block_split_adapts_to_the_data():
             desc[r] = d
         return desc
 
-    cases = {"first two agree": (db_of([2, 3, 6, 7]), [2] + [3] * 32 + [2, 3]),
+    cases = {"first two agree": (db_of([2, 3, 6, 7]), [2] + [3] * 32 + [2] + [3] * 32 + [2] + [3] * 64 + [2, 3]),
              "first three agree": (db_of([3, 7]), [2, 3] + [4] * 32 + [3, 4]),
              "independent bits": (rng.integers(0, 256, (n_rows, 32), dtype=np.uint8), [2] * 6)}
     pts = rng.standard_normal((n_rows, 3)).astype(np.float32)

@@ -143,7 +143,7 @@ int todhip_set_matcher_engine(todhip_ctx* ctx, int engine) {
 
 int todhip_set_matcher_block_split(todhip_ctx* ctx, int split) {
   if (!ctx || !(split == -1 || split == 0 || split == 2 || split == 3)) return TODHIP_EINVAL;
-  ctx->k4x_force = split;
+  ctx->k4x.force = split;
   return TODHIP_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/todhip.h"
+#include "match_split.h"
 
 #define TOD_HIP(call)                                  \
   do {                                                 \
@@ -117,11 +118,10 @@ struct todhip_ctx {
   uint64_t ev_head = 0, ev_tail = 0;   // pairs [ev_tail, ev_head) are recorded and not yet read
   todhip_counters counters = {};
   int matcher_engine = TODHIP_ENGINE_AUTO;   // todhip_set_matcher_engine
-  // K4x's half-block mode (match.hip, launch_topk_mfma_qt): cumulative {blocks that went on, blocks} of the launches in that mode,
-  // as the merge kernel leaves them in pinned memory; launches left before the next probe
+  // K4x's split blocks (match_launch.h, launch_topk_mfma_qt): cumulative {blocks that went on, blocks} of the launches in that mode,
+  // as the DB pass counts them and as the merge kernel leaves them in pinned memory; the controller that reads them (match_split.h)
   HostBuf k4x_stats_host; DevBuf k4x_stats_dev;
-  int k4x_force = -1;                         // todhip_set_matcher_block_split
-  uint32_t k4x_seq_sent = 0, k4x_seq_seen = 0, k4x_split = 2, k4x_hold = 0, k4x_hold_len = 32, k4x_last[4] = {0, 0, 0, 0};   // launch_topk_mfma_qt
+  K4xSplit k4x;                              // k4x.force: todhip_set_matcher_block_split
   float ratio = 0.f;                         // todhip_set_ratio_test (0 = off)
 
   std::vector<todhip_round_trace> traces;
@@ -146,7 +146,7 @@ inline uint32_t rng_next(todhip_rng& r) {
 // capi.hip: a stream of the given kind (todhip_stream_create), honouring the process's CU partition
 extern "C" hipError_t tod_stream_create(hipStream_t* out, int device, int kind);
 extern "C" uint32_t tod_cu_partition();                     // todhip_set_cu_partition's current value
-// match.hip
+// match.hip (the launchers: match_launch.h)
 int tod_timing_begin(todhip_ctx* ctx, int* slot);
 int tod_timing_end(todhip_ctx* ctx, int slot);
 int tod_timing_drain(todhip_ctx* ctx, uint64_t keep);

@@ -1,0 +1,43 @@
+// What both matcher engines and the merges share: the launch constants, the per-lane sorted list of partial keys (distance << 22 |
+// tile-local row; the merges widen them to distance << 32 | global row, the order (distance asc, global row asc) of decision D1) and
+// the pick over ascending lists of global keys. Restates no reference lines of its own.
+// Included by match.hip inside its anonymous namespace, after ctx.h.
+
+constexpr int kWords = 8;          // 256-bit descriptors (ORB / rBRIEF), 32 bytes per row
+constexpr int kGroupRows = 4;      // DB rows per SGPR group (two s_load_dwordx16)
+constexpr int kLocalBits = 22;     // tile-local row index bits in a partial key (tile <= 4M rows)
+constexpr uint32_t kLocalMask = (1u << kLocalBits) - 1u;
+constexpr int kBlock = 256;
+constexpr int kWavesPerBlock = kBlock / 64;
+constexpr int kWavesPerCU = 24;    // waves a CU holds at once: 6 blocks of 4 waves (<= 112 SGPRs); the grid is ~3x that
+constexpr uint32_t kSharePeriod = 128;   // groups between two exchanges of the per-query distance bound
+constexpr int kMergeGroups = 16;   // stage-1 merge fan-in
+
+template <int K>
+__device__ __forceinline__ void topk_insert(uint32_t (&best)[K], uint32_t key) {
+  // branch-free sorted insertion: key falls through the list, each slot keeps the smaller one
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    uint32_t lo = min(best[j], key);
+    key = max(best[j], key);
+    best[j] = lo;
+  }
+}
+
+// The smallest key of query qi over n_lists ascending lists (layout [list][nq][k]) that is greater than the last one taken (any,
+// while !have_last); ~0 when nothing is left. Keys are unique (the row is part of the key), so each list's candidate is its first
+// key greater than `last`.
+__device__ __forceinline__ uint64_t next_key_over_lists(const uint64_t* __restrict__ lists, uint32_t n_lists, uint32_t nq, uint32_t qi,
+                                                        uint32_t k, uint64_t last, bool have_last) {
+  uint64_t nxt = ~0ull;
+  for (uint32_t s = 0; s < n_lists; ++s) {
+    const uint64_t* lst = lists + ((size_t)s * nq + qi) * k;
+    for (uint32_t i = 0; i < k; ++i) {
+      uint64_t v = lst[i];
+      if (have_last && v <= last) continue;
+      if (v < nxt) nxt = v;
+      break;
+    }
+  }
+  return nxt;
+}

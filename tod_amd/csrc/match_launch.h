@@ -1,0 +1,239 @@
+// Host planning of the matcher's launches: the environment knobs, the tiling plan, the workspace set-up, the timing bracket, the
+// merge launch and the launchers of both engines. Each engine keeps its own, measured policy for how many tiles to ask for; what
+// follows that policy is shared. The k of the reference's knnMatch is DescriptorMatcher.cpp:211, its radius cut :212-220.
+// Included by match.hip inside its anonymous namespace, after match_keys.h, match_valu.h, match_mfma.h and match_merge.h.
+
+int k4_engine(const todhip_ctx* ctx, uint32_t nq);   // match.hip, behind this header
+
+// Tuning and diagnostics knobs, read once per process (tools/README.md has the same table).
+struct MatchEnv {
+  char engine;          // TODHIP_K4_ENGINE=valu|mfma      the engine while the context says "auto" (the first letter decides)
+  int k4_mode;          // TODHIP_K4_MODE=0..3             K4's elimination schedule (default -1: by radius)
+  int k4_wpc;           // TODHIP_K4_WAVES_PER_CU=n        K4 tiling: n waves per CU instead of the oversubscribed default (0)
+  int k4x_wpc;          // TODHIP_K4X_WAVES_PER_CU=n       K4x tiling: n waves per CU instead of 8 / 16 / 32 by launch shape (0)
+  int k4x_share;        // TODHIP_K4X_SHARE=n              K4x: steps between two exchanges of the distance bounds (16; each launcher has a floor)
+  int k4x_qt;           // TODHIP_K4X_QT=2|4|6|8           K4x: query blocks per wave, also for <= 32 queries (0: by launch shape)
+  int k4x_half;         // TODHIP_K4X_HALF=0|2|3           the process's default for todhip_set_matcher_block_split (-1: adaptive; 1 = 2)
+  bool k4x_half_debug;  // TODHIP_K4X_HALF_DEBUG           print every report of the split controller to stderr
+};
+inline const MatchEnv& match_env() {
+  static const MatchEnv env = [] {
+    auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+    const char* eng = getenv("TODHIP_K4_ENGINE");
+    return MatchEnv{eng ? eng[0] : '\0', num("TODHIP_K4_MODE", -1), num("TODHIP_K4_WAVES_PER_CU", 0), num("TODHIP_K4X_WAVES_PER_CU", 0),
+                    num("TODHIP_K4X_SHARE", 16), num("TODHIP_K4X_QT", 0), num("TODHIP_K4X_HALF", -1), getenv("TODHIP_K4X_HALF_DEBUG") != nullptr};
+  }();
+  return env;
+}
+
+struct Tiling { uint32_t n_tiles, rows_per_tile, blocks_per_xcd, tiles_per_xcd, groups; };
+
+// The shared tail: rows_per_tile is the engine's choice, rounded to its granule. The tile count it really gives, the grid of
+// 4-wave blocks per XCD (whole tiles per XCD when there are 8 k of them: the kernels' work-item decode) and the merge fan-in. False: a tile
+// would not fit the partial key's row bits.
+inline bool finish_tiling(uint32_t n_rows, uint32_t rows_per_tile, uint32_t n_qw, Tiling* t) {
+  if (rows_per_tile > kLocalMask) return false;
+  t->rows_per_tile = rows_per_tile;
+  t->n_tiles = (n_rows + rows_per_tile - 1) / rows_per_tile;
+  const uint32_t items = t->n_tiles * n_qw;
+  const uint32_t blocks = (items + kWavesPerBlock - 1) / kWavesPerBlock;
+  t->blocks_per_xcd = (blocks + 7u) / 8u;
+  t->tiles_per_xcd = 0;
+  if (t->n_tiles >= 8 && t->n_tiles % 8u == 0) {
+    t->tiles_per_xcd = t->n_tiles / 8u;
+    t->blocks_per_xcd = (t->tiles_per_xcd * n_qw + kWavesPerBlock - 1) / kWavesPerBlock;
+  }
+  t->groups = std::min(t->n_tiles, (uint32_t)kMergeGroups);
+  return true;
+}
+
+// The partial lists (m_part) and, in one buffer under one memset, the per-query bound words (0xFFFFFFFF = none published) and the
+// per-(tile, 64 queries) flag bytes (0xFF = nothing stored). Returns the flags; nullptr: a HIP error, left in the context.
+template <int K>
+uint8_t* prepare_lists(todhip_ctx* ctx, uint32_t n_tiles, uint32_t nq_pad, uint32_t n_qw64) {
+  const size_t bound_bytes = (size_t)nq_pad * sizeof(uint32_t), flag_bytes = (size_t)n_tiles * n_qw64;
+  hipError_t e = ctx->m_part.reserve((size_t)n_tiles * K * nq_pad * sizeof(uint32_t));
+  if (e == hipSuccess) e = ctx->m_bound.reserve(bound_bytes + flag_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(ctx->m_bound.p, 0xFF, bound_bytes + flag_bytes, ctx->stream);
+  if (e != hipSuccess) { ctx->last_hip_error = (int)e; return nullptr; }
+  return ctx->m_bound.as<uint8_t>() + bound_bytes;
+}
+
+// The optional HIP-event bracket around the DB pass (tod_timing_*, match.hip)
+struct KernelTimer {
+  todhip_ctx* ctx;
+  int slot = -1;
+  int begin() { return ctx->time_kernels ? tod_timing_begin(ctx, &slot) : TODHIP_OK; }
+  int end() { return slot >= 0 ? tod_timing_end(ctx, slot) : TODHIP_OK; }
+};
+
+// K4m behind a DB pass. wave: a handful of queries over thousands of tiles, a wave per (query, group). d_stats: the DB pass's
+// split-block counters, which the counting form carries to pinned memory (K4xSplit::take_report reads them there).
+template <int K>
+int launch_merge(todhip_ctx* ctx, uint32_t nq, uint32_t nq_pad, const Tiling& t, const uint8_t* d_stored, uint32_t n_qw64, bool wave,
+                 const uint32_t* d_stats, uint64_t* d_lists, uint32_t* n_lists) {
+  if (wave)
+    hipLaunchKernelGGL(merge_tiles_wave_kernel<K>, dim3((nq + kWavesPerBlock - 1) / kWavesPerBlock, t.groups), dim3(kBlock), 0, ctx->stream,
+                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, ctx->shard_first, t.groups, d_stored, n_qw64, d_lists);
+  else
+    hipLaunchKernelGGL(merge_tiles_kernel<K>, dim3((nq + kBlock - 1) / kBlock, t.groups), dim3(kBlock), 0, ctx->stream,
+                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, ctx->shard_first, t.groups, d_stored, n_qw64, d_lists,
+                       d_stats, d_stats ? ctx->k4x_stats_host.as<uint32_t>() : (uint32_t*)nullptr, d_stats ? ctx->k4x.seq_sent : 0u);
+  TOD_HIP(hipGetLastError());
+  *n_lists = t.groups;
+  return TODHIP_OK;
+}
+
+template <int K, int QT>
+int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
+  constexpr bool PF2 = QT < 8;                                        // register budget: see hamming_topk_mfma
+  const MatchEnv& env = match_env();
+  const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu >> kLocalBits : radius + 1u;   // distances are <= 256: no cut beyond that
+  const uint32_t n_rows = (uint32_t)ctx->shard_rows;
+  const uint32_t n_qw = (nq + 32u * QT - 1u) / (32u * QT), n_qw64 = (nq + 63u) / 64u;
+  const uint32_t nq_pad = n_qw64 * 64u;
+  // Rounds of waves: the chip holds 8 of these waves per CU (2 per SIMD, by registers). A launch whose wave count is just
+  // under a whole number of rounds has no straggling last round (measured, tools/k4x_sweep.py, 16 000 x 1M: 16 waves per
+  // CU = 2 rounds 1.13 ms, 14 = 1.6 rounds 1.37 ms, 8 = all resident 1.36 ms, 32 .. 128 1.11 ms); four rounds while a tile
+  // then still has >= 48 steps (a tile starts with empty lists), two otherwise. Tiles are whole 32-row steps.
+  uint32_t wpc = 32;
+  if ((uint64_t)n_rows * n_qw < (uint64_t)ctx->n_cu * wpc * 1536u) wpc = 16;
+  // A tile starts with empty lists and the radius as its threshold, and every row inside the threshold costs a walk of its block
+  // until the list's k-th entry tightens it. On independent bits almost no row is; on self-similar texture (rendered views of
+  // rectangle patterns: a median of 1300 rows of 1M within 35 bits of a query, tools/count_close_rows.py) tiles of a few hundred
+  // rows spend their life in that walk. One frame's launch therefore gets at most 8 waves per CU (tiles of >= ~4000 rows)
+  // and 4 query blocks per wave (launch_topk_mfma): 0.32 -> 0.19 ms on such a frame, 0.096 -> 0.095 ms on independent bits
+  // (tools/k4x_chained_frame.sh, tools/k4x_synth_frame.sh).
+  if ((uint64_t)n_rows * n_qw < (uint64_t)ctx->n_cu * 16u * 4096u) wpc = 8;
+  if (env.k4x_wpc > 0) wpc = (uint32_t)env.k4x_wpc;
+  uint32_t n_tiles = std::max(1u, (uint32_t)ctx->n_cu * wpc / n_qw);
+  n_tiles = std::min(n_tiles, std::max(1u, n_rows / 256u));
+  n_tiles = std::min(n_tiles, 8192u);
+  if (n_tiles >= 16) n_tiles &= ~7u;                                  // whole tiles per XCD, never more waves than asked for
+  Tiling t;
+  if (!finish_tiling(n_rows, ((n_rows + n_tiles - 1) / n_tiles + 31u) & ~31u, n_qw, &t)) return TODHIP_EINVAL;
+  uint8_t* const d_stored = prepare_lists<K>(ctx, t.n_tiles, nq_pad, n_qw64);
+  if (!d_stored) return TODHIP_EHIP;
+  KernelTimer timer{ctx};
+  if (int rc = timer.begin()) return rc;
+  // radius < 128: every threshold is >= 0 and the block test may compare raw bits (see mfma_block_test). cut <= 64 / <= 96: the
+  // thresholds minus 128 / 64 are >= 0 as well and a block may be split after 2 / 3 of its 4 MFMAs (mfma_block_test_part); which
+  // split a launch takes is K4xSplit's business (match_split.h).
+  const uint32_t min_split = QT < 4 ? 4u : (cut <= 64u ? 2u : (cut <= 96u ? 3u : 4u));   // the lowest split the thresholds allow
+  if (ctx->k4x.may_split(min_split, env.k4x_half)) {
+    if (!ctx->k4x_stats_host.p) {
+      TOD_HIP(ctx->k4x_stats_host.reserve(64));
+      std::memset(ctx->k4x_stats_host.p, 0, 64);
+      TOD_HIP(ctx->k4x_stats_dev.reserve(64));
+      TOD_HIP(hipMemsetAsync(ctx->k4x_stats_dev.p, 0, 64, ctx->stream));
+    }
+    ctx->k4x.take_report(ctx->k4x_stats_host.as<uint32_t>(), ctx->counters, min_split, env.k4x_half, env.k4x_half_debug);
+  }
+  const uint32_t split = ctx->k4x.next(min_split, env.k4x_half);       // 4 = whole blocks
+  auto kern = split == 2 ? hamming_topk_mfma<K, QT, 2, PF2>
+              : split == 3 ? hamming_topk_mfma<K, QT, 3, PF2>
+              : (cut <= 128u ? hamming_topk_mfma<K, QT, 1, PF2> : hamming_topk_mfma<K, QT, 0, PF2>);
+  ctx->counters.last_block_split = split;
+  uint32_t* const d_stats = split < 4 ? ctx->k4x_stats_dev.as<uint32_t>() : nullptr;
+  hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream,
+                     ctx->db_desc.as<uint32_t>(), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw, n_qw64,
+                     t.blocks_per_xcd, t.tiles_per_xcd, cut, (uint32_t)std::max(2, env.k4x_share), ctx->m_part.as<uint32_t>(),
+                     ctx->m_bound.as<uint32_t>(), d_stored, d_stats ? d_stats + 2u * (split - 2u) : nullptr);
+  if (int rc = timer.end()) return rc;
+  if (d_stats) ++ctx->k4x.seq_sent;
+  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, nq <= 64u && !d_stats && t.n_tiles >= 256u, d_stats, d_lists, n_lists);
+}
+
+template <int K>
+int launch_topk_mfma_q32(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
+  const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu >> kLocalBits : radius + 1u;
+  const uint32_t n_rows = (uint32_t)ctx->shard_rows, n_qw64 = 1u, nq_pad = 64u;
+  // one wave per tile; about 32 waves per CU in all (each holds four 1 KB loads in flight), tiles of >= 2048 rows
+  uint32_t n_tiles = std::max(1u, std::min<uint32_t>((uint32_t)ctx->n_cu * 32u, n_rows / 2048u));
+  n_tiles = std::min(n_tiles, 8192u);
+  Tiling t;
+  if (!finish_tiling(n_rows, ((n_rows + n_tiles - 1) / n_tiles + 31u) & ~31u, 1u, &t)) return TODHIP_EINVAL;
+  uint8_t* const d_stored = prepare_lists<K>(ctx, t.n_tiles, nq_pad, n_qw64);
+  if (!d_stored) return TODHIP_EHIP;
+  KernelTimer timer{ctx};
+  if (int rc = timer.begin()) return rc;
+  auto kern = cut <= 128u ? hamming_topk_mfma_q32<K, true> : hamming_topk_mfma_q32<K, false>;
+  hipLaunchKernelGGL(kern, dim3((t.n_tiles + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, ctx->stream,
+                     ctx->db_desc.as<uint32_t>(), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw64, cut,
+                     (uint32_t)std::max(4, match_env().k4x_share), ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
+  if (int rc = timer.end()) return rc;
+  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, true, nullptr, d_lists, n_lists);
+}
+
+template <int K>
+int launch_topk_mfma(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
+  const int env_qt = match_env().k4x_qt;
+  if (nq <= 32u && !(env_qt > 0))
+    return launch_topk_mfma_q32<K>(ctx, d_q, nq, radius, d_lists, n_lists);
+  // Query blocks of 32 per wave (QT): the registers hold 8 beside the k-entry lists for k <= 2, 6 for k <= 5 (the reference's k,
+  // DescriptorMatcher.cpp:211), 4 beyond. Six is the default even where eight fit: with eight a wave takes 256 registers, two waves
+  // fill a SIMD's file, and every kernel of the other stages (ORB, verifier) then waits for a matcher workgroup to retire before
+  // one of its own can start -- a quarter of a DB pass, 25 dependent launches per ORB batch. With six (213-221 registers, allocated
+  // in eights: 64-80 of a SIMD's 512 stay free) those kernels run beside the matcher's waves: alone the pass is 2 % slower (2.36 vs 2.32 ms whole blocks), in the
+  // pipeline ORB's stage falls from 1.9 to 1.2 ms, the verifier's from 2.05 to 1.5, and the matcher's own launch is no slower
+  // (tools/ab_k4x_residency.sh: headline 16.2k -> 16.6k frames/s, chained 8.7k -> 9.9k). Among the candidates the one that pads nq
+  // the least wins when that saves more than 3 % (a wave computes all its blocks; 1000 queries are 4 x 256 but 6 x 192).
+  // TODHIP_K4X_QT forces one (experiments).
+  // With at most 64 queries a wave holds two blocks (QT = 2): 8 MFMAs per 1 KB of rows -- the pass is then bound by HBM,
+  // not by the matrix pipe (BASELINE.json's "achieved HBM GB/s on BF-matcher" regime; tools/k4_small_q.py).
+  constexpr int kMaxQT = K <= 2 ? 8 : (K <= 5 ? 6 : 4);
+  auto padded = [&](uint32_t qt) { return (uint64_t)((nq + 32u * qt - 1u) / (32u * qt) * (32u * qt)); };
+  int qt = kMaxQT >= 6 ? 6 : 4;
+  if (kMaxQT >= 8 && padded(8) * 103u < padded(6) * 100u) qt = 8;
+  if (qt > 4 && padded(4) * 103u < padded((uint32_t)qt) * 100u) qt = 4;
+  if (padded(2) * 103u < padded((uint32_t)qt) * 100u) qt = 2;
+  if (nq <= 2048u && qt > 4) qt = 4;                                  // a frame or two: longer tiles, see launch_topk_mfma_qt
+  if ((env_qt == 2 || env_qt == 4 || env_qt == 6 || env_qt == 8) && env_qt <= kMaxQT) qt = env_qt;
+  if (qt == 8) return launch_topk_mfma_qt<K, (kMaxQT >= 8 ? 8 : 4)>(ctx, d_q, nq, radius, d_lists, n_lists);
+  if (qt == 6) return launch_topk_mfma_qt<K, (kMaxQT >= 6 ? 6 : 4)>(ctx, d_q, nq, radius, d_lists, n_lists);
+  if (qt == 2) return launch_topk_mfma_qt<K, 2>(ctx, d_q, nq, radius, d_lists, n_lists);
+  return launch_topk_mfma_qt<K, 4>(ctx, d_q, nq, radius, d_lists, n_lists);
+}
+
+template <int K>
+int launch_topk(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
+  if (k4_engine(ctx, nq) == 1) return launch_topk_mfma<K>(ctx, d_q, nq, radius, d_lists, n_lists);
+  const MatchEnv& env = match_env();
+  const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu : radius + 1u;   // distances are <= 256: no cut beyond that
+  const uint32_t n_rows = (uint32_t)ctx->shard_rows;
+  const uint32_t n_qw = (nq + 63u) / 64u;
+  const uint32_t nq_pad = n_qw * 64u;
+  // Tiling (measured, tools/time_k4.py): about three times more waves than fit the chip at once and tiles of at most
+  // ~2048 rows (16 000 queries x 1M rows: 3.27 ms with 4096-row tiles, 3.20 ms with 2048; 10M rows: 35.6 -> 34.3 ms).
+  // An exactly-resident grid of long-running waves (the first design) lost 15-20 %: the hardware does not spread
+  // blocks evenly over the CUs, and the query waves of a large tile drift apart in it (scalar-cache and L2 misses);
+  // short blocks rebalance by themselves and keep a tile's readers together.
+  uint32_t n_tiles;
+  if (env.k4_wpc > 0) {
+    n_tiles = (uint32_t)ctx->n_cu * (uint32_t)env.k4_wpc / n_qw;
+  } else {
+    n_tiles = std::max(3u * (uint32_t)ctx->n_cu * (uint32_t)kWavesPerCU / n_qw, (n_rows + 2047u) / 2048u);
+    n_tiles = std::min(n_tiles, 8192u);
+  }
+  if (n_tiles < 1) n_tiles = 1;
+  if (n_tiles >= 8) n_tiles = (n_tiles + 7u) & ~7u;      // whole tiles per XCD (8 XCDs)
+  uint32_t rows_per_tile = (n_rows + n_tiles - 1) / n_tiles;
+  rows_per_tile = ((rows_per_tile + 2 * kGroupRows - 1) / (2 * kGroupRows)) * (2 * kGroupRows);
+  if (rows_per_tile < 64) rows_per_tile = 64;
+  Tiling t;
+  if (!finish_tiling(n_rows, rows_per_tile, n_qw, &t)) return TODHIP_EINVAL;
+  uint8_t* const d_stored = prepare_lists<K>(ctx, t.n_tiles, nq_pad, n_qw);
+  if (!d_stored) return TODHIP_EHIP;
+  KernelTimer timer{ctx};
+  if (int rc = timer.begin()) return rc;
+  // every schedule is exact; TODHIP_K4_MODE overrides the choice (diagnostics: tools/k4_on_correlated_descriptors.py)
+  const int mode = (env.k4_mode >= 0 && env.k4_mode <= 3 && cut <= 256u) ? env.k4_mode
+                                                                         : (cut <= 38u ? 2 : (cut <= 48u ? 1 : (cut <= 80u ? 3 : 0)));
+  auto kern = mode == 2 ? hamming_topk_tiles<K, 2>
+                        : (mode == 1 ? hamming_topk_tiles<K, 1> : (mode == 3 ? hamming_topk_tiles<K, 3> : hamming_topk_tiles<K, 0>));
+  hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream,
+                     ctx->db_desc.as<uint32_t>(), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw,
+                     t.blocks_per_xcd, t.tiles_per_xcd, cut, ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
+  if (int rc = timer.end()) return rc;
+  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw, false, nullptr, d_lists, n_lists);
+}
