@@ -134,3 +134,33 @@ def test_batch_of_frames_equals_frame_by_frame(ctx):
         n_found += len(want)
     assert got[3] == [] and n_found >= 3
 
+
+def test_capacity_returns_of_the_three_forms(ctx):
+    """No room for the pose that is there: every form reports TODHIP_ECAPACITY, and its generator has still made the frame's one
+    draw. Set-up of test_device_form_after_the_device_matcher_equals_the_host_form; then the two-visible-objects scene with room
+    for one pose only."""
+    import torch
+    desc, pts, off = synth.make_db(6, per_object=800)
+    fr = synth.make_frame(desc, pts, off, 500, frame=3, visible_object=4)
+    spans = ctx.db_load(desc, pts, off)
+    row_ptr, m, xyz = ctx.match(fr["q_desc"], 3, 35)
+    d_q = torch.from_numpy(fr["q_desc"]).cuda(); d_kp = torch.from_numpy(fr["kp_xy"]).cuda()
+    cnt = torch.zeros(500, dtype=torch.int32, device="cuda"); mm = torch.zeros((1500, 4), dtype=torch.int32, device="cuda")
+    xx = torch.zeros((1500, 3), dtype=torch.float32, device="cuda")
+    ctx.match_device(d_q.data_ptr(), 500, 3, 35, cnt.data_ptr(), mm.data_ptr(), xx.data_ptr())
+    rng_h, rng_d, rngs = capi.rng_new(5), capi.rng_new(5), (capi.Rng * 1)(capi.rng_new(5))
+    calls = [lambda: ctx.verify_2d(fr["kp_xy"], K, row_ptr, m, xyz, spans, 8, 400, 3.0, rng_h, max_poses=0),
+             lambda: ctx.verify_2d_device(d_kp.data_ptr(), 500, K, cnt.data_ptr(), mm.data_ptr(), xx.data_ptr(), 3, spans, 8, 400, 3.0, rng_d,
+                                          max_poses=0),
+             lambda: ctx.verify_2d_batch_device(1, d_kp.data_ptr(), 500, K, cnt.data_ptr(), mm.data_ptr(), xx.data_ptr(), 3, spans, 8, 400, 3.0,
+                                                rngs, max_poses=0)]
+    for call, rng in zip(calls, (rng_h, rng_d, rngs[0])):
+        with pytest.raises(capi.TodError) as e:
+            call()
+        assert e.value.status == capi.ECAPACITY
+        assert rng.draws == 1
+    sc = synth.make_verify_scene(700, n_objects=6, per_object=300, visible=((1, 0.30), (4, 0.20)), matches_per_kp=3, seed=0)
+    rng = capi.rng_new(1)
+    with pytest.raises(capi.TodError) as e:
+        ctx.verify_2d(sc["kp_xy"], K, sc["row_ptr"], sc["matches"], sc["matches_xyz"], sc["spans"], 12, 500, 3.0, rng, max_poses=1)
+    assert e.value.status == capi.ECAPACITY and rng.draws == 1

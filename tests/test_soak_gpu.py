@@ -53,15 +53,31 @@ def test_repeated_calls_do_not_leak_and_do_not_drift():
 
 
 def test_contexts_can_be_created_and_destroyed_repeatedly():
+    """Every stage's workspace is created and torn down with its context: ORB (with its captured graph), both verifiers, the LSH
+    index and, on odd iterations, the float matcher's."""
     import torch
     torch.cuda.init()
     desc, pts, off = synth.make_db(2, per_object=2000)
     q = synth.make_frame(desc, pts, off, 200)["q_desc"]
+    img = synth.make_image(0, H=240, W=320)
+    sc = synth.make_verify_scene(300, visible=((1, 0.3),))
+    K = np.array([[525.0, 0, 320.0], [0, 525.0, 240.0], [0, 0, 1]], np.float32)
+    g = np.random.Generator(np.random.PCG64(7))
+    desc_f = g.standard_normal((2000, 128)).astype(np.float32)
+    pts_f = g.standard_normal((2000, 3)).astype(np.float32)
     base = None
     for i in range(30):
         c = capi.Context(0)
         c.db_load(desc, pts, off)
         row_ptr, m, xyz = c.match(q, 2, 40)
+        c.orb(img)
+        c.verify(sc["kp_xy"], sc["cloud"], sc["row_ptr"], sc["matches"], sc["matches_xyz"], sc["spans"], 8, 200, 0.01, capi.rng_new(1))
+        c.verify_2d(sc["kp_xy"], K, sc["row_ptr"], sc["matches"], sc["matches_xyz"], sc["spans"], 8, 200, 3.0, capi.rng_new(1))
+        c.set_lsh(4, 16, 1)
+        c.match(q, 2, 40)
+        if i % 2:
+            c.db_load(desc_f, pts_f, np.array([0, 2000], np.uint32))
+            c.match_l2(desc_f[:64], 2, 1e6)
         c.close()
         if i == 4:
             base = _free_mb()

@@ -112,6 +112,36 @@ def _np_ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+def _k9(K):
+    return np.ascontiguousarray(K, np.float32).reshape(9)
+
+
+def _verify_in(spans, min_inliers, n_iter, err):
+    """What every verify* call passes in besides its frame: (spans f32[n_objs], VerifyParams). The caller holds both during the call."""
+    return np.ascontiguousarray(spans, np.float32), VerifyParams(min_inliers, n_iter, err)
+
+
+def _pose_out(max_poses, n_kp, n_frames=None, cache=None):
+    """Output arrays of one verify* call: room for max_poses poses (per frame, with a pose_ptr, when n_frames is given) and their
+    inlier keypoints. cache: the Context that keeps the inlier array between calls (a megabyte per batch otherwise; results are
+    copied out of it). Returns (poses, n_poses, inl, n_inl, pose_ptr)."""
+    cap_p = max_poses if n_frames is None else max_poses * n_frames
+    cap = max(n_kp, 1) * cap_p
+    if cache is None:
+        inl = np.zeros(cap, np.uint32)
+    else:
+        if getattr(cache, "_inl_cap", 0) < cap:
+            cache._inl = np.zeros(cap, np.uint32)
+            cache._inl_cap = cap
+        inl = cache._inl
+    return (Pose * cap_p)(), C.c_uint32(cap_p), inl, C.c_uint32(cap), None if n_frames is None else (C.c_uint32 * (n_frames + 1))()
+
+
+def _pose_list(poses, lo, hi, inl):
+    return [dict(object=int(poses[i].object), R=np.array(poses[i].R[:], np.float32).reshape(3, 3), t=np.array(poses[i].t[:], np.float32),
+                 inliers=inl[poses[i].inlier_begin:poses[i].inlier_end].copy()) for i in range(lo, hi)]
+
+
 class Context:
     """One HIP device + stream (todhip_ctx)."""
 
@@ -205,31 +235,22 @@ class Context:
                "todhip_db_info")
         return dict(total_rows=tot.value, shard_first=first.value, shard_rows=rows.value, n_objs=nobj.value)
 
-    def match(self, q_desc, k, radius):
-        """Host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
-        q = np.ascontiguousarray(q_desc, np.uint8)
+    def _match_host(self, fn, what, q, k, radius):
         nq = q.shape[0]
         row_ptr = np.zeros(nq + 1, np.uint32)
         m = np.zeros(max(nq * k, 1), DMATCH_DTYPE)
         xyz = np.zeros((max(nq * k, 1), 3), np.float32)
-        rc = lib().todhip_match(self._h, _np_ptr(q), C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius),
-                                _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz))
-        _check(rc, "todhip_match")
+        _check(fn(self._h, _np_ptr(q), C.c_uint32(nq), C.c_uint32(k), radius, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz)), what)
         n = int(row_ptr[nq])
         return row_ptr, m[:n].copy(), xyz[:n].copy()
 
+    def match(self, q_desc, k, radius):
+        """Host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
+        return self._match_host(lib().todhip_match, "todhip_match", np.ascontiguousarray(q_desc, np.uint8), k, C.c_uint32(radius))
+
     def match_l2(self, q_desc, k, radius):
         """Float descriptors, host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
-        q = np.ascontiguousarray(q_desc, np.float32)
-        nq = q.shape[0]
-        row_ptr = np.zeros(nq + 1, np.uint32)
-        m = np.zeros(max(nq * k, 1), DMATCH_DTYPE)
-        xyz = np.zeros((max(nq * k, 1), 3), np.float32)
-        rc = lib().todhip_match_l2(self._h, _np_ptr(q), C.c_uint32(nq), C.c_uint32(k), C.c_float(radius), _np_ptr(row_ptr),
-                                   _np_ptr(m), _np_ptr(xyz))
-        _check(rc, "todhip_match_l2")
-        n = int(row_ptr[nq])
-        return row_ptr, m[:n].copy(), xyz[:n].copy()
+        return self._match_host(lib().todhip_match_l2, "todhip_match_l2", np.ascontiguousarray(q_desc, np.float32), k, C.c_float(radius))
 
     def match_l2_device(self, d_q, nq, k, radius, d_counts, d_matches, d_xyz):
         rc = lib().todhip_match_l2_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_float(radius),
@@ -269,122 +290,70 @@ class Context:
         row_ptr = np.ascontiguousarray(row_ptr, np.uint32)
         matches = np.ascontiguousarray(matches, DMATCH_DTYPE)
         mxyz = np.ascontiguousarray(matches_xyz, np.float32)
-        sp = np.ascontiguousarray(spans, np.float32)
-        prm = VerifyParams(min_inliers, n_iter, err)
-        poses = (Pose * max_poses)()
-        n_poses = C.c_uint32(max_poses)
-        cap = max(len(kp), 1) * max_poses
-        inl = np.zeros(cap, np.uint32)
-        n_inl = C.c_uint32(cap)
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
+        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, len(kp))
         rc = lib().todhip_verify(self._h, _np_ptr(kp), C.c_uint32(len(kp)), _np_ptr(cloud), C.c_uint32(H),
-                                 C.c_uint32(W), _np_ptr(row_ptr), _np_ptr(matches), _np_ptr(mxyz), _np_ptr(sp),
-                                 C.c_uint32(len(sp)), C.byref(prm), C.byref(rng), poses, C.byref(n_poses),
-                                 _np_ptr(inl), C.byref(n_inl))
+                                 C.c_uint32(W), _np_ptr(row_ptr), _np_ptr(matches), _np_ptr(mxyz), _np_ptr(sp), C.c_uint32(len(sp)),
+                                 C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
         _check(rc, "todhip_verify")
-        out = []
-        for i in range(n_poses.value):
-            p = poses[i]
-            out.append(dict(object=int(p.object), R=np.array(p.R[:], np.float32).reshape(3, 3),
-                            t=np.array(p.t[:], np.float32), inliers=inl[p.inlier_begin:p.inlier_end].copy()))
-        return out
+        return _pose_list(poses, 0, n_poses.value, inl)
 
     def verify_2d(self, kp_xy, K, row_ptr, matches, matches_xyz, spans, min_inliers, n_iter, err_px, rng, max_poses=64):
         """The 2D-only branch (no cloud): todhip_verify_2d. err_px: reprojection threshold in pixels."""
         kp = np.ascontiguousarray(kp_xy, np.float32)
-        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
         row_ptr = np.ascontiguousarray(row_ptr, np.uint32)
         matches = np.ascontiguousarray(matches, DMATCH_DTYPE)
         mxyz = np.ascontiguousarray(matches_xyz, np.float32)
-        sp = np.ascontiguousarray(spans, np.float32)
-        prm = VerifyParams(min_inliers, n_iter, err_px)
-        poses = (Pose * max_poses)()
-        n_poses = C.c_uint32(max_poses)
-        cap = max(len(kp), 1) * max_poses
-        inl = np.zeros(cap, np.uint32)
-        n_inl = C.c_uint32(cap)
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err_px)
+        K9 = _k9(K)
+        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, len(kp))
         rc = lib().todhip_verify_2d(self._h, _np_ptr(kp), C.c_uint32(len(kp)), _np_ptr(K9), _np_ptr(row_ptr),
                                     matches.ctypes.data_as(C.c_void_p), _np_ptr(mxyz), _np_ptr(sp), C.c_uint32(len(sp)),
                                     C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
         _check(rc, "todhip_verify_2d")
-        return [dict(object=int(poses[i].object), R=np.array(poses[i].R[:], np.float32).reshape(3, 3),
-                     t=np.array(poses[i].t[:], np.float32),
-                     inliers=inl[poses[i].inlier_begin:poses[i].inlier_end].copy()) for i in range(n_poses.value)]
+        return _pose_list(poses, 0, n_poses.value, inl)
 
     def verify_2d_device(self, d_kp_xy, nq, K, d_counts, d_matches, d_xyz, k, spans, min_inliers, n_iter, err_px, rng, max_poses=64):
-        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
-        sp = np.ascontiguousarray(spans, np.float32)
-        prm = VerifyParams(min_inliers, n_iter, err_px)
-        poses = (Pose * max_poses)()
-        n_poses = C.c_uint32(max_poses)
-        cap = max(nq, 1) * max_poses
-        inl = np.zeros(cap, np.uint32)
-        n_inl = C.c_uint32(cap)
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err_px)
+        K9 = _k9(K)
+        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq)
         rc = lib().todhip_verify_2d_device(self._h, C.c_void_p(d_kp_xy), C.c_uint32(nq), _np_ptr(K9), C.c_void_p(d_counts),
                                            C.c_void_p(d_matches), C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp), C.c_uint32(len(sp)),
                                            C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
         _check(rc, "todhip_verify_2d_device")
-        return [dict(object=int(poses[i].object), R=np.array(poses[i].R[:], np.float32).reshape(3, 3),
-                     t=np.array(poses[i].t[:], np.float32),
-                     inliers=inl[poses[i].inlier_begin:poses[i].inlier_end].copy()) for i in range(n_poses.value)]
+        return _pose_list(poses, 0, n_poses.value, inl)
 
     def verify_2d_batch_device(self, n_frames, d_kp_xy, nq, K, d_counts, d_matches, d_xyz, k, spans, min_inliers, n_iter, err_px, rngs,
                                max_poses=16):
         """rngs: ctypes array (Rng * n_frames). Returns a list (per frame) of lists of pose dicts."""
-        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
-        sp = np.ascontiguousarray(spans, np.float32)
-        prm = VerifyParams(min_inliers, n_iter, err_px)
-        cap_p = max_poses * n_frames
-        poses = (Pose * cap_p)()
-        n_poses = C.c_uint32(cap_p)
-        pose_ptr = (C.c_uint32 * (n_frames + 1))()
-        cap = max(nq, 1) * cap_p
-        inl = np.zeros(cap, np.uint32)
-        n_inl = C.c_uint32(cap)
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err_px)
+        K9 = _k9(K)
+        poses, n_poses, inl, n_inl, pose_ptr = _pose_out(max_poses, nq, n_frames)
         rc = lib().todhip_verify_2d_batch_device(self._h, C.c_uint32(n_frames), C.c_void_p(d_kp_xy), C.c_uint32(nq), _np_ptr(K9),
                                                  C.c_void_p(d_counts), C.c_void_p(d_matches), C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp),
                                                  C.c_uint32(len(sp)), C.byref(prm), rngs, poses, C.byref(n_poses), pose_ptr, _np_ptr(inl),
                                                  C.byref(n_inl))
         _check(rc, "todhip_verify_2d_batch_device")
-        return [[dict(object=int(poses[i].object), R=np.array(poses[i].R[:], np.float32).reshape(3, 3), t=np.array(poses[i].t[:], np.float32),
-                      inliers=inl[poses[i].inlier_begin:poses[i].inlier_end].copy()) for i in range(pose_ptr[f], pose_ptr[f + 1])]
-                for f in range(n_frames)]
+        return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
 
     def verify_device(self, d_kp_xy, nq, d_cloud, H, W, d_counts, d_matches, d_xyz, k, spans, min_inliers, n_iter,
                       err, rng, max_poses=64):
         """Device-pointer form (ints from tensor.data_ptr()); poses are returned on the host."""
-        sp = np.ascontiguousarray(spans, np.float32)
-        prm = VerifyParams(min_inliers, n_iter, err)
-        poses = (Pose * max_poses)()
-        n_poses = C.c_uint32(max_poses)
-        cap = max(nq, 1) * max_poses
-        if getattr(self, "_inl_cap", 0) < cap:
-            self._inl = np.zeros(cap, np.uint32)
-            self._inl_cap = cap
-        inl = self._inl
-        n_inl = C.c_uint32(cap)
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
+        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq, cache=self)
         rc = lib().todhip_verify_device(self._h, C.c_void_p(d_kp_xy), C.c_uint32(nq), C.c_void_p(d_cloud),
                                         C.c_uint32(H), C.c_uint32(W), C.c_void_p(d_counts), C.c_void_p(d_matches),
                                         C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp), C.c_uint32(len(sp)),
                                         C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl),
                                         C.byref(n_inl))
         _check(rc, "todhip_verify_device")
-        out = []
-        for i in range(n_poses.value):
-            p = poses[i]
-            out.append(dict(object=int(p.object), R=np.array(p.R[:], np.float32).reshape(3, 3),
-                            t=np.array(p.t[:], np.float32), inliers=inl[p.inlier_begin:p.inlier_end].copy()))
-        return out
+        return _pose_list(poses, 0, n_poses.value, inl)
 
     def verify_device_depth(self, d_kp_xy, nq, d_depth, depth_is_u16, H, W, K, d_counts, d_matches, d_xyz, k, spans,
                             min_inliers, n_iter, err, rng, max_poses=64):
-        sp = np.ascontiguousarray(spans, np.float32)
-        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
-        prm = VerifyParams(min_inliers, n_iter, err)
-        poses = (Pose * max_poses)()
-        n_poses = C.c_uint32(max_poses)
-        cap = max(nq, 1) * max_poses
-        inl = np.zeros(cap, np.uint32)
-        n_inl = C.c_uint32(cap)
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
+        K9 = _k9(K)
+        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq)
         rc = lib().todhip_verify_device_depth(self._h, C.c_void_p(d_kp_xy), C.c_uint32(nq), C.c_void_p(d_depth),
                                               C.c_int(1 if depth_is_u16 else 0), C.c_uint32(H), C.c_uint32(W),
                                               _np_ptr(K9), C.c_void_p(d_counts), C.c_void_p(d_matches),
@@ -392,26 +361,14 @@ class Context:
                                               C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl),
                                               C.byref(n_inl))
         _check(rc, "todhip_verify_device_depth")
-        return [dict(object=int(poses[i].object), R=np.array(poses[i].R[:], np.float32).reshape(3, 3),
-                     t=np.array(poses[i].t[:], np.float32),
-                     inliers=inl[poses[i].inlier_begin:poses[i].inlier_end].copy()) for i in range(n_poses.value)]
+        return _pose_list(poses, 0, n_poses.value, inl)
 
     def verify_batch_device(self, n_frames, d_kp_xy, nq, d_cloud, H, W, d_counts, d_matches, d_xyz, k, spans, min_inliers,
                             n_iter, err, rngs, max_poses=16, depth=None):
         """rngs: ctypes array (Rng * n_frames). depth = (d_depth, is_u16, K) selects the depth form (d_cloud ignored).
         Returns a list (per frame) of lists of pose dicts."""
-        sp = np.ascontiguousarray(spans, np.float32)
-        prm = VerifyParams(min_inliers, n_iter, err)
-        cap_p = max_poses * n_frames
-        poses = (Pose * cap_p)()
-        n_poses = C.c_uint32(cap_p)
-        pose_ptr = (C.c_uint32 * (n_frames + 1))()
-        cap = max(nq, 1) * cap_p
-        if getattr(self, "_inl_cap", 0) < cap:                # (a megabyte per call otherwise: kept per context, results are copied out)
-            self._inl = np.zeros(cap, np.uint32)
-            self._inl_cap = cap
-        inl = self._inl
-        n_inl = C.c_uint32(cap)
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
+        poses, n_poses, inl, n_inl, pose_ptr = _pose_out(max_poses, nq, n_frames, cache=self)
         if depth is None:
             rc = lib().todhip_verify_batch_device(self._h, C.c_uint32(n_frames), C.c_void_p(d_kp_xy), C.c_uint32(nq),
                                                   C.c_void_p(d_cloud), C.c_uint32(H), C.c_uint32(W), C.c_void_p(d_counts),
@@ -420,7 +377,7 @@ class Context:
                                                   _np_ptr(inl), C.byref(n_inl))
         else:
             d_depth, is_u16, K = depth
-            K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+            K9 = _k9(K)
             rc = lib().todhip_verify_batch_device_depth(self._h, C.c_uint32(n_frames), C.c_void_p(d_kp_xy), C.c_uint32(nq),
                                                         C.c_void_p(d_depth), C.c_int(1 if is_u16 else 0), C.c_uint32(H),
                                                         C.c_uint32(W), _np_ptr(K9), C.c_void_p(d_counts), C.c_void_p(d_matches),
@@ -428,13 +385,7 @@ class Context:
                                                         C.byref(prm), rngs, poses, C.byref(n_poses), pose_ptr, _np_ptr(inl),
                                                         C.byref(n_inl))
         _check(rc, "todhip_verify_batch_device")
-        out = []
-        for f in range(n_frames):
-            out.append([dict(object=int(poses[i].object), R=np.array(poses[i].R[:], np.float32).reshape(3, 3),
-                             t=np.array(poses[i].t[:], np.float32),
-                             inliers=inl[poses[i].inlier_begin:poses[i].inlier_end].copy())
-                        for i in range(pose_ptr[f], pose_ptr[f + 1])])
-        return out
+        return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
 
     def verify_trace(self, cap=4096):
         arr = (RoundTrace * cap)()
@@ -495,52 +446,38 @@ class Context:
         n = n_out.value
         return kp[:n].copy(), aux[:n].copy(), desc[:n].copy()
 
+    def orb_device(self, d_gray, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux, d_desc, cap):
+        n_out = C.c_uint32(cap)
+        rc = lib().todhip_orb_device(self._h, C.c_void_p(d_gray), C.c_uint32(H), C.c_uint32(W), C.c_uint32(stride),
+                                     C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor), None,
+                                     C.c_void_p(d_kp_xy), C.c_void_p(d_kp_aux), C.c_void_p(d_desc), C.byref(n_out))
+        _check(rc, "todhip_orb_device")
+        return n_out.value
 
-def _orb_device(self, d_gray, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux, d_desc, cap):
-    n_out = C.c_uint32(cap)
-    rc = lib().todhip_orb_device(self._h, C.c_void_p(d_gray), C.c_uint32(H), C.c_uint32(W), C.c_uint32(stride),
-                                 C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor), None,
-                                 C.c_void_p(d_kp_xy), C.c_void_p(d_kp_aux), C.c_void_p(d_desc), C.byref(n_out))
-    _check(rc, "todhip_orb_device")
-    return n_out.value
+    def orb_batch_device(self, d_gray, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux,
+                         d_desc, cap):
+        n = (C.c_uint32 * n_frames)()
+        rc = lib().todhip_orb_batch_device(self._h, C.c_void_p(d_gray), C.c_uint32(n_frames), C.c_uint64(frame_stride), C.c_uint32(H),
+                                           C.c_uint32(W), C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels),
+                                           C.c_float(scale_factor), None, C.c_void_p(d_kp_xy), C.c_void_p(d_kp_aux),
+                                           C.c_void_p(d_desc), C.c_uint32(cap), n)
+        _check(rc, "todhip_orb_batch_device")
+        return list(n)
 
+    def rescale_depth(self, depth, H, W, nearest=False):
+        """rescale_depth (Trainer.cpp:62-81): depth [dH, dW] float32 metres / uint16 mm -> [H, W] float32 metres."""
+        u16 = depth.dtype == np.uint16
+        d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32)
+        out = np.empty((H, W), np.float32)
+        rc = lib().todhip_rescale_depth(self._h, _np_ptr(d), C.c_int(1 if u16 else 0), C.c_uint32(d.shape[0]), C.c_uint32(d.shape[1]),
+                                        _np_ptr(out), C.c_uint32(H), C.c_uint32(W), C.c_int(1 if nearest else 0))
+        _check(rc, "todhip_rescale_depth")
+        return out
 
-Context.orb_device = _orb_device
-
-
-def _orb_batch_device(self, d_gray, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux,
-                      d_desc, cap):
-    n = (C.c_uint32 * n_frames)()
-    rc = lib().todhip_orb_batch_device(self._h, C.c_void_p(d_gray), C.c_uint32(n_frames), C.c_uint64(frame_stride), C.c_uint32(H),
-                                       C.c_uint32(W), C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels),
-                                       C.c_float(scale_factor), None, C.c_void_p(d_kp_xy), C.c_void_p(d_kp_aux),
-                                       C.c_void_p(d_desc), C.c_uint32(cap), n)
-    _check(rc, "todhip_orb_batch_device")
-    return list(n)
-
-
-Context.orb_batch_device = _orb_batch_device
-
-
-def _rescale_depth(self, depth, H, W, nearest=False):
-    """rescale_depth (Trainer.cpp:62-81): depth [dH, dW] float32 metres / uint16 mm -> [H, W] float32 metres."""
-    u16 = depth.dtype == np.uint16
-    d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32)
-    out = np.empty((H, W), np.float32)
-    rc = lib().todhip_rescale_depth(self._h, _np_ptr(d), C.c_int(1 if u16 else 0), C.c_uint32(d.shape[0]), C.c_uint32(d.shape[1]),
-                                    _np_ptr(out), C.c_uint32(H), C.c_uint32(W), C.c_int(1 if nearest else 0))
-    _check(rc, "todhip_rescale_depth")
-    return out
-
-
-def _rescale_depth_device(self, d_depth_in, is_u16, dH, dW, d_depth_out, H, W, nearest=False):
-    rc = lib().todhip_rescale_depth_device(self._h, C.c_void_p(d_depth_in), C.c_int(1 if is_u16 else 0), C.c_uint32(dH),
-                                           C.c_uint32(dW), C.c_void_p(d_depth_out), C.c_uint32(H), C.c_uint32(W), C.c_int(1 if nearest else 0))
-    _check(rc, "todhip_rescale_depth_device")
-
-
-Context.rescale_depth = _rescale_depth
-Context.rescale_depth_device = _rescale_depth_device
+    def rescale_depth_device(self, d_depth_in, is_u16, dH, dW, d_depth_out, H, W, nearest=False):
+        rc = lib().todhip_rescale_depth_device(self._h, C.c_void_p(d_depth_in), C.c_int(1 if is_u16 else 0), C.c_uint32(dH),
+                                               C.c_uint32(dW), C.c_void_p(d_depth_out), C.c_uint32(H), C.c_uint32(W), C.c_int(1 if nearest else 0))
+        _check(rc, "todhip_rescale_depth_device")
 
 
 class Model:
@@ -560,7 +497,7 @@ class Model:
             depth = self._ctx.rescale_depth(depth, H, W)
         u16 = depth.dtype == np.uint16
         d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32)
-        K9 = np.ascontiguousarray(K, np.float32).reshape(9)
+        K9 = _k9(K)
         R9 = np.ascontiguousarray(R, np.float32).reshape(9)
         T3 = np.ascontiguousarray(T, np.float32).reshape(3)
         n = C.c_uint32(0)

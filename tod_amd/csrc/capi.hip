@@ -51,11 +51,7 @@ void todhip_destroy(todhip_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  tod_verify_ws_free(ctx);
-  tod_orb_ws_free(ctx);
-  tod_l2_ws_free(ctx);
-  tod_pnp_ws_free(ctx);
-  tod_lsh_ws_free(ctx);
+  for (std::unique_ptr<TodWs>& w : ctx->ws) w.reset();       // (graphs, side events and buffers, while the stream still exists)
   for (int i = 0; i < 2 * todhip_ctx::kEvPairs; ++i)
     if (ctx->evp[i]) (void)hipEventDestroy(ctx->evp[i]);
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
@@ -295,6 +291,18 @@ int todhip_db_info(const todhip_ctx* ctx, uint64_t* total_rows, uint64_t* shard_
   return TODHIP_OK;
 }
 
+// stream nullptr: the context's
+static int merge_shards(todhip_ctx* ctx, hipStream_t stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k,
+                        uint32_t radius, void* d_counts, void* d_matches, void* d_matches_xyz) {
+  if (!ctx || !d_keys_all || !d_counts || !d_matches || !d_matches_xyz) return TODHIP_EINVAL;
+  if (k == 0 || k > 8 || radius == 0 || n_shards == 0) return TODHIP_EINVAL;
+  if (ctx->total_rows == 0) return TODHIP_ENODB;
+  if (ctx->ratio > 0.f && k < 2) return TODHIP_EINVAL;
+  return tod_match_finalize(ctx, reinterpret_cast<const uint64_t*>(d_keys_all), n_shards, nq, k, k, radius,
+                            reinterpret_cast<uint32_t*>(d_counts), reinterpret_cast<todhip_dmatch*>(d_matches),
+                            reinterpret_cast<float*>(d_matches_xyz), stream);
+}
+
 int todhip_match_shard_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint32_t k, uint32_t radius,
                               void* d_keys) {
   if (!ctx || !d_q_desc || !d_keys || k == 0 || k > 8 || radius == 0) return TODHIP_EINVAL;
@@ -303,26 +311,15 @@ int todhip_match_shard_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq
   return tod_match_shard_keys(ctx, d_q_desc, nq, k, radius, reinterpret_cast<uint64_t*>(d_keys));
 }
 
-int todhip_merge_shards_device(todhip_ctx* ctx, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k,
-                               uint32_t radius, void* d_counts, void* d_matches, void* d_matches_xyz) {
-  if (!ctx || !d_keys_all || !d_counts || !d_matches || !d_matches_xyz) return TODHIP_EINVAL;
-  if (k == 0 || k > 8 || radius == 0 || n_shards == 0) return TODHIP_EINVAL;
-  if (ctx->total_rows == 0) return TODHIP_ENODB;
-  if (ctx->ratio > 0.f && k < 2) return TODHIP_EINVAL;
-  return tod_match_finalize(ctx, reinterpret_cast<const uint64_t*>(d_keys_all), n_shards, nq, k, k, radius,
-                            reinterpret_cast<uint32_t*>(d_counts), reinterpret_cast<todhip_dmatch*>(d_matches),
-                            reinterpret_cast<float*>(d_matches_xyz));
-}
-
 int todhip_merge_shards_device_on(todhip_ctx* ctx, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq,
                                   uint32_t k, uint32_t radius, void* d_counts, void* d_matches, void* d_matches_xyz) {
-  if (!ctx || !hip_stream || !d_keys_all || !d_counts || !d_matches || !d_matches_xyz) return TODHIP_EINVAL;
-  if (k == 0 || k > 8 || radius == 0 || n_shards == 0) return TODHIP_EINVAL;
-  if (ctx->total_rows == 0) return TODHIP_ENODB;
-  if (ctx->ratio > 0.f && k < 2) return TODHIP_EINVAL;
-  return tod_match_finalize(ctx, reinterpret_cast<const uint64_t*>(d_keys_all), n_shards, nq, k, k, radius,
-                            reinterpret_cast<uint32_t*>(d_counts), reinterpret_cast<todhip_dmatch*>(d_matches),
-                            reinterpret_cast<float*>(d_matches_xyz), reinterpret_cast<hipStream_t>(hip_stream));
+  if (!ctx || !hip_stream) return TODHIP_EINVAL;
+  return merge_shards(ctx, reinterpret_cast<hipStream_t>(hip_stream), d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_matches_xyz);
+}
+
+int todhip_merge_shards_device(todhip_ctx* ctx, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k,
+                               uint32_t radius, void* d_counts, void* d_matches, void* d_matches_xyz) {
+  return merge_shards(ctx, nullptr, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_matches_xyz);
 }
 
 int todhip_match_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint32_t k, uint32_t radius,
@@ -368,18 +365,22 @@ int todhip_match(todhip_ctx* ctx, const uint8_t* q_desc, uint32_t nq, uint32_t k
   int rc = todhip_match_device(ctx, ctx->m_q.p, nq, k, radius, h_counts, h_m, h_xyz);
   if (rc != TODHIP_OK) return rc;
   TOD_HIP(hipStreamSynchronize(ctx->stream));
-  // fixed stride k -> CSR (the cell's vector<vector<DMatch>> / vector<Mat> shapes)
-  uint32_t out = 0;
-  for (uint32_t qi = 0; qi < nq; ++qi) {
-    row_ptr[qi] = out;
-    const uint32_t c = h_counts[qi];
-    std::memcpy(matches + out, h_m + (size_t)qi * k, (size_t)c * sizeof(todhip_dmatch));
-    std::memcpy(matches_xyz + (size_t)out * 3, h_xyz + (size_t)qi * k * 3, (size_t)c * 3 * sizeof(float));
-    out += c;
-  }
-  row_ptr[nq] = out;
-  ctx->counters.last_matches = out;
+  ctx->counters.last_matches = tod_pack_csr(h_counts, h_m, h_xyz, nq, k, row_ptr, matches, matches_xyz);
   return TODHIP_OK;
 }
 
 }  // extern "C"
+
+uint32_t tod_pack_csr(const uint32_t* counts, const todhip_dmatch* m, const float* xyz, uint32_t nq, uint32_t k, uint32_t* row_ptr,
+                      todhip_dmatch* matches, float* matches_xyz) {
+  uint32_t out = 0;
+  for (uint32_t qi = 0; qi < nq; ++qi) {
+    row_ptr[qi] = out;
+    const uint32_t c = counts[qi];
+    std::memcpy(matches + out, m + (size_t)qi * k, (size_t)c * sizeof(todhip_dmatch));
+    std::memcpy(matches_xyz + (size_t)out * 3, xyz + (size_t)qi * k * 3, (size_t)c * 3 * sizeof(float));
+    out += c;
+  }
+  row_ptr[nq] = out;
+  return out;
+}

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../include/todhip.h"
@@ -90,6 +91,11 @@ struct HostBuf {
   template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// A stage's workspace: defined in the stage's translation unit (struct XWs : TodWs with kSlot = its slot), created on first use by
+// tod_ws<XWs>(ctx), owned by the context. Its destructor is the stage's whole teardown. The slots are released in this order.
+struct TodWs { virtual ~TodWs() {} };
+enum TodWsSlot { kWsVerify, kWsOrb, kWsL2, kWsPnp, kWsLsh, kWsSlots };
+
 struct todhip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -126,13 +132,15 @@ struct todhip_ctx {
 
   std::vector<todhip_round_trace> traces;
 
-  // ---- verifier / ORB workspaces live in their own translation units
-  void* verify_ws = nullptr;
-  void* orb_ws = nullptr;
-  void* l2_ws = nullptr;
-  void* pnp_ws = nullptr;
-  void* lsh_ws = nullptr;
+  std::unique_ptr<TodWs> ws[kWsSlots];       // todhip_destroy releases them before the events and the stream go
 };
+
+template <typename T> T* tod_ws(todhip_ctx* ctx) {
+  std::unique_ptr<TodWs>& s = ctx->ws[T::kSlot];
+  if (!s) s.reset(new T());
+  return static_cast<T*>(s.get());
+}
+template <typename T> const T* tod_ws(const todhip_ctx* ctx) { return static_cast<const T*>(ctx->ws[T::kSlot].get()); }   // nullptr: never used
 
 // glibc random_r TYPE_3 (see include/todhip.h, decision D4)
 inline uint32_t rng_next(todhip_rng& r) {
@@ -143,6 +151,10 @@ inline uint32_t rng_next(todhip_rng& r) {
   return out;
 }
 
+// capi.hip: fixed stride k -> CSR (the cell's vector<vector<DMatch>> / vector<Mat> shapes): query qi's first counts[qi] slots, packed;
+// returns the total (== row_ptr[nq])
+uint32_t tod_pack_csr(const uint32_t* counts, const todhip_dmatch* m, const float* xyz, uint32_t nq, uint32_t k, uint32_t* row_ptr,
+                      todhip_dmatch* matches, float* matches_xyz);
 // capi.hip: a stream of the given kind (todhip_stream_create), honouring the process's CU partition
 extern "C" hipError_t tod_stream_create(hipStream_t* out, int device, int kind);
 extern "C" uint32_t tod_cu_partition();                     // todhip_set_cu_partition's current value
@@ -158,22 +170,16 @@ int tod_match_shard_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t
 int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k_in, uint32_t k_out,
                        uint32_t radius, uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz,
                        hipStream_t stream = nullptr);   // nullptr: the context's stream
-// verify.hip / orb.hip
-void tod_verify_ws_free(todhip_ctx* ctx);
 // verify.hip: ClusterPerObject of F frames on the device without a cloud (pnp.hip's 2D-only branch); d_err: 8 words per frame
 // (ClusterCtl of verify_kernels.h: word 0 = error, word 4 = matches kept)
 int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy, uint32_t nq, const uint32_t* d_counts,
                                const todhip_dmatch* d_matches, const float* d_mxyz, uint32_t k, uint32_t n_objs, float* d_X,
                                uint32_t* d_qidx, uint32_t* d_hist, uint32_t* d_goff, uint32_t* d_err);
-void tod_l2_ws_free(todhip_ctx* ctx);
-void tod_pnp_ws_free(todhip_ctx* ctx);      // pnp.hip
 // lsh.hip: the optional LSH-approximate mode (todhip_set_lsh)
-void tod_lsh_ws_free(todhip_ctx* ctx);
 bool tod_lsh_enabled(const todhip_ctx* ctx);
 int tod_lsh_build(todhip_ctx* ctx);
 int tod_lsh_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint64_t* d_lists, uint32_t* n_lists);
 int tod_l2_db_prepare(todhip_ctx* ctx);      // l2.hip: bf16 image + norms of a 128 x f32 DB resident in db_desc
-void tod_orb_ws_free(todhip_ctx* ctx);
 int tod_orb_device(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask, uint32_t H, uint32_t W, uint32_t stride,
                    uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern, float* d_kp_xy,
                    float* d_kp_aux, uint8_t* d_desc, uint32_t cap, uint32_t* n_out);

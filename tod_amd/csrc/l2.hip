@@ -52,15 +52,11 @@ typedef __attribute__((ext_vector_type(8))) short bf16x8;  // 8 bf16 = 4 VGPRs: 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-struct L2Ws {
+struct L2Ws : TodWs {
+  static constexpr int kSlot = kWsL2;
   DevBuf db_bf16, db_norm, q_bf16, q_eps, part, thr, slots, slot_cnt, cand, cand_cnt, keys, scal;
   uint32_t n_pad = 0;
 };
-
-L2Ws* l2ws_of(todhip_ctx* ctx) {
-  if (!ctx->l2_ws) ctx->l2_ws = new L2Ws();
-  return reinterpret_cast<L2Ws*>(ctx->l2_ws);
-}
 
 __device__ __forceinline__ uint16_t bf16_rne(float x) {
   const uint32_t b = __float_as_uint(x);
@@ -503,16 +499,9 @@ __global__ __launch_bounds__(256) void l2_finalize_kernel(const uint64_t* __rest
 
 }  // namespace
 
-void tod_l2_ws_free(todhip_ctx* ctx) {
-  if (!ctx->l2_ws) return;
-  L2Ws* ws = reinterpret_cast<L2Ws*>(ctx->l2_ws);
-  delete ws;
-  ctx->l2_ws = nullptr;
-}
-
 // called by todhip_db_load for 128 x f32 rows (already resident in ctx->db_desc): bf16 image, norms, Rmax
 int tod_l2_db_prepare(todhip_ctx* ctx) {
-  L2Ws* ws = l2ws_of(ctx);
+  L2Ws* ws = tod_ws<L2Ws>(ctx);
   const uint32_t n = (uint32_t)ctx->shard_rows;
   ws->n_pad = ((n + kTileRows - 1u) / kTileRows) * kTileRows;
   TOD_HIP(ws->db_bf16.reserve((size_t)std::max(ws->n_pad, kTileRows) * kDim * 2));
@@ -527,7 +516,7 @@ int tod_l2_db_prepare(todhip_ctx* ctx) {
 }
 
 static int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k, int exact_only) {
-  L2Ws* ws = l2ws_of(ctx);
+  L2Ws* ws = tod_ws<L2Ws>(ctx);
   hipStream_t st = ctx->stream;
   const uint32_t n = (uint32_t)ctx->shard_rows;
   TOD_HIP(ws->keys.reserve((size_t)nq * k * 8));
@@ -666,7 +655,7 @@ int todhip_match_l2_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, u
   static const bool exact_only = getenv("TODHIP_L2_EXACT_SCAN") != nullptr;      // diagnostics: skip the GEMM filter
   int rc = l2_keys(ctx, reinterpret_cast<const float*>(d_q_desc), nq, k, exact_only ? 1 : 0);
   if (rc != TODHIP_OK) return rc;
-  L2Ws* ws = l2ws_of(ctx);
+  L2Ws* ws = tod_ws<L2Ws>(ctx);
   hipLaunchKernelGGL(l2_finalize_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, ctx->stream, ws->keys.as<uint64_t>(), nq, k, radius,
                      ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), reinterpret_cast<uint32_t*>(d_counts),
                      reinterpret_cast<todhip_dmatch*>(d_matches), reinterpret_cast<float*>(d_matches_xyz));
@@ -698,15 +687,7 @@ int todhip_match_l2(todhip_ctx* ctx, const float* q_desc, uint32_t nq, uint32_t 
   TOD_HIP(hipMemcpyAsync(m.data(), ctx->m_matches.p, cap * sizeof(todhip_dmatch), hipMemcpyDeviceToHost, ctx->stream));
   TOD_HIP(hipMemcpyAsync(x.data(), ctx->m_xyz.p, cap * 12, hipMemcpyDeviceToHost, ctx->stream));
   TOD_HIP(hipStreamSynchronize(ctx->stream));
-  uint32_t out = 0;
-  for (uint32_t qi = 0; qi < nq; ++qi) {                    // fixed-stride slots -> CSR
-    for (uint32_t j = 0; j < counts[qi]; ++j) {
-      matches[out] = m[(size_t)qi * k + j];
-      std::memcpy(matches_xyz + 3 * (size_t)out, &x[((size_t)qi * k + j) * 3], 12);
-      ++out;
-    }
-    row_ptr[qi + 1] = out;
-  }
+  tod_pack_csr(counts.data(), m.data(), x.data(), nq, k, row_ptr, matches, matches_xyz);
   return TODHIP_OK;
 }
 

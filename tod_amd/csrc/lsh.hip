@@ -26,17 +26,13 @@ namespace {
 
 constexpr uint32_t kMaxTables = 32, kMaxKeyBits = 24, kMaxLevel = 3;
 
-struct LshWs {
+struct LshWs : TodWs {
+  static constexpr int kSlot = kWsLsh;
   uint32_t n_tables = 0, key_size = 0, level = 0;
   uint32_t n_masks = 0;
   uint64_t built_rows = ~0ull;          // shard_rows the index was built for (~0: not built)
   DevBuf pos, masks, off, rows, cursor, scan_tmp;
 };
-
-LshWs* lshws_of(todhip_ctx* ctx) {
-  if (!ctx->lsh_ws) ctx->lsh_ws = new LshWs();
-  return reinterpret_cast<LshWs*>(ctx->lsh_ws);
-}
 
 inline uint32_t mix32(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16; return x; }
 
@@ -166,21 +162,14 @@ int launch_query(todhip_ctx* ctx, LshWs* ws, const void* d_q, uint32_t nq, uint6
 
 }  // namespace
 
-void tod_lsh_ws_free(todhip_ctx* ctx) {
-  LshWs* ws = reinterpret_cast<LshWs*>(ctx->lsh_ws);
-  if (!ws) return;
-  delete ws;
-  ctx->lsh_ws = nullptr;
-}
-
 bool tod_lsh_enabled(const todhip_ctx* ctx) {
-  const LshWs* ws = reinterpret_cast<const LshWs*>(ctx->lsh_ws);
+  const LshWs* ws = tod_ws<LshWs>(ctx);
   return ws && ws->n_tables > 0;
 }
 
 // (re)build the index over the shard's rows resident in ctx->db_desc; called by todhip_db_load and todhip_set_lsh
 int tod_lsh_build(todhip_ctx* ctx) {
-  LshWs* ws = lshws_of(ctx);
+  LshWs* ws = tod_ws<LshWs>(ctx);
   ws->built_rows = ~0ull;
   if (ws->n_tables == 0 || ctx->desc_bytes != 32 || ctx->shard_rows == 0) return TODHIP_OK;
   if (ctx->shard_rows > 0xFFFFFFFFull) return TODHIP_EINVAL;
@@ -226,7 +215,7 @@ int tod_lsh_build(todhip_ctx* ctx) {
 
 // one list of k keys per query, the format of tod_match_lists
 int tod_lsh_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint64_t* d_lists, uint32_t* n_lists) {
-  LshWs* ws = lshws_of(ctx);
+  LshWs* ws = tod_ws<LshWs>(ctx);
   if (ws->built_rows != ctx->shard_rows) return TODHIP_EINVAL;
   *n_lists = 1;
   switch (k) {
@@ -247,7 +236,7 @@ extern "C" int todhip_set_lsh(todhip_ctx* ctx, uint32_t n_tables, uint32_t key_s
   if (n_tables > kMaxTables || (n_tables && (key_size == 0 || key_size > kMaxKeyBits)) || multi_probe_level > kMaxLevel) return TODHIP_EINVAL;
   if (n_tables && multi_probe_level > key_size) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
-  LshWs* ws = lshws_of(ctx);
+  LshWs* ws = tod_ws<LshWs>(ctx);
   ws->n_tables = n_tables; ws->key_size = key_size; ws->level = multi_probe_level;
   return tod_lsh_build(ctx);
 }

@@ -453,7 +453,8 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const uint32_t* __restric
   if (i < 8u * n) d_desc[i] = s_desc[i];
 }
 
-struct OrbWs {
+struct OrbWs : TodWs {
+  static constexpr int kSlot = kWsOrb;
   DevBuf pyr, blur, tmp, score, cand, eq, sel1, sel2, small, pattern, in_img, kp_xy, kp_aux, desc, o_xy, o_aux, o_desc, maskbuf;
   HostBuf h_out, h_kp;                                     // h_kp: the host form's keypoints, written by copy_out_kernel itself
   bool pattern_is_default = false;
@@ -463,12 +464,11 @@ struct OrbWs {
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   struct Key { uint32_t H, W, n_features, n_levels, cap, F; float sf; const void *kp, *aux, *desc, *img0, *mask; } key = {};
+  ~OrbWs() override {                                      // the captured graph goes before the buffers it refers to
+    if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
+    if (graph) (void)hipGraphDestroy(graph);
+  }
 };
-
-OrbWs* ows_of(todhip_ctx* ctx) {
-  if (!ctx->orb_ws) ctx->orb_ws = new OrbWs();
-  return reinterpret_cast<OrbWs*>(ctx->orb_ws);
-}
 
 void features_per_level(uint32_t n_features, uint32_t n_levels, float scale_factor, uint32_t* out) {
   const float factor = 1.0f / scale_factor;
@@ -492,7 +492,7 @@ int orb_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uin
       F > 65535u)
     return TODHIP_EINVAL;
   if (cap == 0) return TODHIP_ECAPACITY;
-  OrbWs* ws = ows_of(ctx);
+  OrbWs* ws = tod_ws<OrbWs>(ctx);
   hipStream_t st = ctx->stream;
   const size_t px = (size_t)H * W;
   const uint32_t cand_cap = (uint32_t)(px / 4 + 64);
@@ -620,15 +620,6 @@ int tod_orb_device(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask
                     cap, n_out);
 }
 
-void tod_orb_ws_free(todhip_ctx* ctx) {
-  if (!ctx->orb_ws) return;
-  OrbWs* ws = reinterpret_cast<OrbWs*>(ctx->orb_ws);
-  if (ws->graph_exec) (void)hipGraphExecDestroy(ws->graph_exec);   // the captured graph goes before the buffers it refers to
-  if (ws->graph) (void)hipGraphDestroy(ws->graph);
-  delete ws;
-  ctx->orb_ws = nullptr;
-}
-
 extern "C" {
 
 int todhip_orb_device(todhip_ctx* ctx, const void* d_gray, uint32_t H, uint32_t W, uint32_t stride, uint32_t n_features,
@@ -660,7 +651,7 @@ int todhip_orb_masked(todhip_ctx* ctx, const uint8_t* gray, const uint8_t* mask,
                       uint8_t* desc, uint32_t* n_out) {
   if (!ctx || !gray || !kp_xy || !kp_aux || !desc || !n_out || stride < W) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
-  OrbWs* ws = ows_of(ctx);
+  OrbWs* ws = tod_ws<OrbWs>(ctx);
   const uint32_t cap = *n_out;
   *n_out = 0;
   if (cap == 0) return TODHIP_ECAPACITY;

@@ -425,15 +425,88 @@ __global__ __launch_bounds__(256) void pnp_active_kernel(const uint32_t* __restr
   if (tid == 0) *n_active = s_base;
 }
 
-struct PnpWs { DevBuf objs, kp, q_idx, X, best, flags, results, hist, goff, err, spans, seeds, na; };
+struct PnpWs : TodWs {
+  static constexpr int kSlot = kWsPnp;
+  DevBuf objs, kp, q_idx, X, best, flags, results, hist, goff, err, spans, seeds, na;
+};
 
 }  // namespace
 
-void tod_pnp_ws_free(todhip_ctx* ctx) {
-  PnpWs* ws = reinterpret_cast<PnpWs*>(ctx->pnp_ws);
-  if (!ws) return;
-  delete ws;
-  ctx->pnp_ws = nullptr;
+// Where a call's poses go: the caller's arrays with their capacities as they came in (begin_2d takes them and zeroes the counts).
+struct Out2d {
+  todhip_pose* poses; uint32_t* n_poses; uint32_t* pose_ptr; uint32_t* inlier_kp; uint32_t* n_inlier_kp;
+  uint32_t cap_poses = 0, cap_inl = 0;
+};
+
+static bool args_2d_ok(const float* K9, const todhip_verify_params* prm, const Out2d& dst) {
+  if (!(prm->sensor_error > 0.f) || !(K9[0] > 0.f) || !(K9[4] > 0.f)) return false;
+  return !((*dst.n_poses && !dst.poses) || (*dst.n_inlier_kp && !dst.inlier_kp));
+}
+
+// n_slots match slots and F * nq keypoints must be countable in 32 bits; then the outputs start out empty
+static int begin_2d(todhip_ctx* ctx, uint32_t F, uint32_t nq, uint64_t n_slots, Out2d& dst) {
+  if (n_slots > 0xFFFFFFFFull || (uint64_t)F * nq > 0xFFFFFFFFull) return TODHIP_EINVAL;
+  TOD_HIP(hipSetDevice(ctx->device));
+  dst.cap_poses = *dst.n_poses; dst.cap_inl = *dst.n_inlier_kp;
+  *dst.n_poses = 0; *dst.n_inlier_kp = 0;
+  if (dst.pose_ptr) for (uint32_t f = 0; f <= F; ++f) dst.pose_ptr[f] = 0;
+  return TODHIP_OK;
+}
+
+// The common tail of the two forms. On the device: the na active objects (ws->objs), the keypoints of all frames (d_kp), and per
+// match slot the keypoint index and the model point (ws->q_idx, ws->X; n_slots of them). RANSAC + refinement of every object, then
+// the poses in the order of the list (frame major, objects ascending inside a frame). `active` and `q_idx` are the host's copies of
+// the two lists; a caller that built them on the device passes them empty and they come back with the results.
+static int solve_and_emit_2d(todhip_ctx* ctx, PnpWs* ws, const float* d_kp, uint32_t F, uint32_t nq, const float* K9,
+                             const todhip_verify_params* prm, uint32_t na, size_t n_slots, std::vector<ObjSpanP>& active,
+                             std::vector<uint32_t>& q_idx, const Out2d& dst) {
+  hipStream_t st = ctx->stream;
+  TOD_HIP(ws->best.reserve((size_t)na * 8));
+  TOD_HIP(ws->flags.reserve(n_slots));
+  TOD_HIP(ws->results.reserve((size_t)na * sizeof(ObjResult)));
+  TOD_HIP(hipMemsetAsync(ws->best.p, 0, (size_t)na * 8, st));
+  const Cam cam{(double)K9[0], (double)K9[4], (double)K9[2], (double)K9[5]};
+  const double err2 = (double)prm->sensor_error * (double)prm->sensor_error;
+  hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3((prm->n_ransac_iterations + 255u) / 256u, na), dim3(256), 0, st, ws->objs.as<ObjSpanP>(),
+                     d_kp, ws->q_idx.as<uint32_t>(), ws->X.as<float>(), cam, prm->n_ransac_iterations, err2,
+                     ws->best.as<unsigned long long>());
+  hipLaunchKernelGGL(pnp_refine_kernel, dim3(na), dim3(64), 0, st, ws->objs.as<ObjSpanP>(), d_kp, ws->q_idx.as<uint32_t>(),
+                     ws->X.as<float>(), cam, err2, prm->min_inliers, ws->best.as<unsigned long long>(), ws->flags.as<uint8_t>(),
+                     ws->results.as<ObjResult>());
+  TOD_HIP(hipGetLastError());
+  std::vector<ObjResult> res(na);
+  std::vector<uint8_t> flags(n_slots);
+  TOD_HIP(hipMemcpyAsync(res.data(), ws->results.p, (size_t)na * sizeof(ObjResult), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipMemcpyAsync(flags.data(), ws->flags.p, n_slots, hipMemcpyDeviceToHost, st));
+  if (active.empty()) {
+    active.resize(na); q_idx.resize(n_slots);
+    TOD_HIP(hipMemcpyAsync(active.data(), ws->objs.p, (size_t)na * sizeof(ObjSpanP), hipMemcpyDeviceToHost, st));
+    TOD_HIP(hipMemcpyAsync(q_idx.data(), ws->q_idx.p, n_slots * 4, hipMemcpyDeviceToHost, st));
+  }
+  TOD_HIP(hipStreamSynchronize(st));
+  uint32_t np = 0, ni = 0;
+  for (uint32_t a = 0; a < na; ++a) {
+    if (!res[a].valid) continue;
+    if (np >= dst.cap_poses) return TODHIP_ECAPACITY;
+    todhip_pose& out = dst.poses[np];
+    out.object = active[a].object;
+    std::memcpy(out.R, res[a].R, sizeof(out.R)); std::memcpy(out.t, res[a].t, sizeof(out.t));
+    out.inlier_begin = ni;
+    uint32_t last = 0xFFFFFFFFu;
+    for (uint32_t m = 0; m < active[a].n; ++m) {                       // keypoint indices of the frame, ascending, each once
+      const uint32_t q = q_idx[active[a].begin + m] - active[a].frame * nq;
+      if (!flags[active[a].begin + m] || q == last) continue;
+      if (ni >= dst.cap_inl) return TODHIP_ECAPACITY;
+      dst.inlier_kp[ni++] = last = q;
+    }
+    out.inlier_end = ni;
+    ++np;
+    if (dst.pose_ptr) dst.pose_ptr[active[a].frame + 1] = np;
+  }
+  if (dst.pose_ptr) for (uint32_t f = 0; f < F; ++f) dst.pose_ptr[f + 1] = std::max(dst.pose_ptr[f + 1], dst.pose_ptr[f]);   // frames without a pose
+  *dst.n_poses = np; *dst.n_inlier_kp = ni;
+  ctx->counters.last_poses = np;
+  return TODHIP_OK;
 }
 
 // One batch: per frame host arrays (keypoints, CSR matches), one generator per frame. The objects of all frames go through the two
@@ -441,10 +514,8 @@ void tod_pnp_ws_free(todhip_ctx* ctx) {
 struct Frame2d { const float* kp_xy; const uint32_t* row_ptr; const todhip_dmatch* matches; const float* matches_xyz; };
 
 static int verify_2d_core(todhip_ctx* ctx, uint32_t F, const Frame2d* fr, uint32_t nq, const float* K9, const float* spans, uint32_t n_objs,
-                          const todhip_verify_params* prm, todhip_rng* rngs, todhip_pose* poses, uint32_t* n_poses, uint32_t* pose_ptr,
-                          uint32_t* inlier_kp, uint32_t* n_inlier_kp) {
-  if (!(prm->sensor_error > 0.f) || !(K9[0] > 0.f) || !(K9[4] > 0.f)) return TODHIP_EINVAL;
-  if ((*n_poses && !poses) || (*n_inlier_kp && !inlier_kp)) return TODHIP_EINVAL;
+                          const todhip_verify_params* prm, todhip_rng* rngs, Out2d dst) {
+  if (!args_2d_ok(K9, prm, dst)) return TODHIP_EINVAL;
   size_t n_all = 0;
   for (uint32_t f = 0; f < F; ++f) {
     const uint32_t nm = fr[f].row_ptr[nq];
@@ -453,11 +524,8 @@ static int verify_2d_core(todhip_ctx* ctx, uint32_t F, const Frame2d* fr, uint32
       if (fr[f].matches[m].imgIdx < 0 || (uint32_t)fr[f].matches[m].imgIdx >= n_objs) return TODHIP_EINVAL;
     n_all += nm;
   }
-  if (n_all > 0xFFFFFFFFull || (uint64_t)F * nq > 0xFFFFFFFFull) return TODHIP_EINVAL;
-  TOD_HIP(hipSetDevice(ctx->device));
-  const uint32_t cap_poses = *n_poses, cap_inl = *n_inlier_kp;
-  *n_poses = 0; *n_inlier_kp = 0;
-  if (pose_ptr) for (uint32_t f = 0; f <= F; ++f) pose_ptr[f] = 0;
+  int rc = begin_2d(ctx, F, nq, n_all, dst);
+  if (rc != TODHIP_OK) return rc;
   // ClusterPerObject (adjacency_ransac.cpp:176-205) per frame: per object, matches in CSR order
   std::vector<uint32_t> q_idx(n_all);
   std::vector<float> X(3 * n_all), kp_all(2 * (size_t)F * nq);
@@ -484,59 +552,18 @@ static int verify_2d_core(todhip_ctx* ctx, uint32_t F, const Frame2d* fr, uint32
     base += nm;
   }
   if (active.empty() || prm->n_ransac_iterations == 0) return TODHIP_OK;
-  if (!ctx->pnp_ws) ctx->pnp_ws = new PnpWs();
-  PnpWs* ws = reinterpret_cast<PnpWs*>(ctx->pnp_ws);
+  PnpWs* ws = tod_ws<PnpWs>(ctx);
   hipStream_t st = ctx->stream;
   const uint32_t na = (uint32_t)active.size();
   TOD_HIP(ws->objs.reserve(na * sizeof(ObjSpanP)));
   TOD_HIP(ws->kp.reserve(kp_all.size() * 4));
   TOD_HIP(ws->q_idx.reserve(n_all * 4));
   TOD_HIP(ws->X.reserve(n_all * 12));
-  TOD_HIP(ws->best.reserve((size_t)na * 8));
-  TOD_HIP(ws->flags.reserve(n_all));
-  TOD_HIP(ws->results.reserve((size_t)na * sizeof(ObjResult)));
   TOD_HIP(hipMemcpyAsync(ws->objs.p, active.data(), na * sizeof(ObjSpanP), hipMemcpyHostToDevice, st));
   TOD_HIP(hipMemcpyAsync(ws->kp.p, kp_all.data(), kp_all.size() * 4, hipMemcpyHostToDevice, st));
   TOD_HIP(hipMemcpyAsync(ws->q_idx.p, q_idx.data(), n_all * 4, hipMemcpyHostToDevice, st));
   TOD_HIP(hipMemcpyAsync(ws->X.p, X.data(), n_all * 12, hipMemcpyHostToDevice, st));
-  TOD_HIP(hipMemsetAsync(ws->best.p, 0, (size_t)na * 8, st));
-  const Cam cam{(double)K9[0], (double)K9[4], (double)K9[2], (double)K9[5]};
-  const double err2 = (double)prm->sensor_error * (double)prm->sensor_error;
-  hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3((prm->n_ransac_iterations + 255u) / 256u, na), dim3(256), 0, st, ws->objs.as<ObjSpanP>(),
-                     ws->kp.as<float>(), ws->q_idx.as<uint32_t>(), ws->X.as<float>(), cam, prm->n_ransac_iterations, err2,
-                     ws->best.as<unsigned long long>());
-  hipLaunchKernelGGL(pnp_refine_kernel, dim3(na), dim3(64), 0, st, ws->objs.as<ObjSpanP>(), ws->kp.as<float>(), ws->q_idx.as<uint32_t>(),
-                     ws->X.as<float>(), cam, err2, prm->min_inliers, ws->best.as<unsigned long long>(), ws->flags.as<uint8_t>(),
-                     ws->results.as<ObjResult>());
-  TOD_HIP(hipGetLastError());
-  std::vector<ObjResult> res(na);
-  std::vector<uint8_t> flags(n_all);
-  TOD_HIP(hipMemcpyAsync(res.data(), ws->results.p, (size_t)na * sizeof(ObjResult), hipMemcpyDeviceToHost, st));
-  TOD_HIP(hipMemcpyAsync(flags.data(), ws->flags.p, n_all, hipMemcpyDeviceToHost, st));
-  TOD_HIP(hipStreamSynchronize(st));
-  uint32_t np = 0, ni = 0;
-  for (uint32_t a = 0; a < na; ++a) {                                   // frame major, objects ascending inside a frame
-    if (!res[a].valid) continue;
-    if (np >= cap_poses) return TODHIP_ECAPACITY;
-    todhip_pose& out = poses[np];
-    out.object = active[a].object;
-    std::memcpy(out.R, res[a].R, sizeof(out.R)); std::memcpy(out.t, res[a].t, sizeof(out.t));
-    out.inlier_begin = ni;
-    uint32_t last = 0xFFFFFFFFu;
-    for (uint32_t m = 0; m < active[a].n; ++m) {                       // keypoint indices of the frame, ascending, each once
-      const uint32_t q = q_idx[active[a].begin + m] - active[a].frame * nq;
-      if (!flags[active[a].begin + m] || q == last) continue;
-      if (ni >= cap_inl) return TODHIP_ECAPACITY;
-      inlier_kp[ni++] = last = q;
-    }
-    out.inlier_end = ni;
-    ++np;
-    if (pose_ptr) pose_ptr[active[a].frame + 1] = np;
-  }
-  if (pose_ptr) for (uint32_t f = 0; f < F; ++f) pose_ptr[f + 1] = std::max(pose_ptr[f + 1], pose_ptr[f]);   // frames without a pose
-  *n_poses = np; *n_inlier_kp = ni;
-  ctx->counters.last_poses = np;
-  return TODHIP_OK;
+  return solve_and_emit_2d(ctx, ws, ws->kp.as<float>(), F, nq, K9, prm, na, n_all, active, q_idx, dst);
 }
 
 extern "C" int todhip_verify_2d(todhip_ctx* ctx, const float* kp_xy, uint32_t nq, const float* K9, const uint32_t* row_ptr,
@@ -545,7 +572,7 @@ extern "C" int todhip_verify_2d(todhip_ctx* ctx, const float* kp_xy, uint32_t nq
                                 uint32_t* inlier_kp, uint32_t* n_inlier_kp) {
   if (!ctx || !K9 || !row_ptr || !prm || !rng || !n_poses || !n_inlier_kp || (nq && !kp_xy)) return TODHIP_EINVAL;
   const Frame2d fr = {kp_xy, row_ptr, matches, matches_xyz};
-  return verify_2d_core(ctx, 1, &fr, nq, K9, spans, n_objs, prm, rng, poses, n_poses, nullptr, inlier_kp, n_inlier_kp);
+  return verify_2d_core(ctx, 1, &fr, nq, K9, spans, n_objs, prm, rng, Out2d{poses, n_poses, nullptr, inlier_kp, n_inlier_kp});
 }
 
 // Device-resident forms: keypoints and the matcher's fixed-stride outputs (exactly what todhip_match_device / todhip_merge_shards_device
@@ -560,15 +587,12 @@ extern "C" int todhip_verify_2d_batch_device(todhip_ctx* ctx, uint32_t n_frames,
                                              uint32_t* n_inlier_kp) {
   if (!ctx || !K9 || !prm || !rng || !n_poses || !n_inlier_kp || k == 0 || n_frames == 0) return TODHIP_EINVAL;
   if (nq && (!d_kp_xy || !d_counts || !d_matches || !d_matches_xyz)) return TODHIP_EINVAL;
-  if (!(prm->sensor_error > 0.f) || !(K9[0] > 0.f) || !(K9[4] > 0.f)) return TODHIP_EINVAL;
-  if ((*n_poses && !poses) || (*n_inlier_kp && !inlier_kp)) return TODHIP_EINVAL;
+  Out2d dst{poses, n_poses, pose_ptr, inlier_kp, n_inlier_kp};
+  if (!args_2d_ok(K9, prm, dst)) return TODHIP_EINVAL;
   const uint32_t F = n_frames;
   const uint64_t per64 = (uint64_t)nq * k;
-  if (per64 * F > 0xFFFFFFFFull || (uint64_t)F * nq > 0xFFFFFFFFull) return TODHIP_EINVAL;
-  TOD_HIP(hipSetDevice(ctx->device));
-  const uint32_t cap_poses = *n_poses, cap_inl = *n_inlier_kp;
-  *n_poses = 0; *n_inlier_kp = 0;
-  if (pose_ptr) for (uint32_t f = 0; f <= F; ++f) pose_ptr[f] = 0;
+  int rc = begin_2d(ctx, F, nq, per64 * F, dst);
+  if (rc != TODHIP_OK) return rc;
   std::vector<uint32_t> seeds(F);
   for (uint32_t f = 0; f < F; ++f) seeds[f] = rng_next(rng[f]);        // the one draw a frame costs (as the host form)
   if (nq == 0 || n_objs == 0 || !spans) return nq && n_objs && !spans ? TODHIP_EINVAL : TODHIP_OK;
@@ -576,20 +600,18 @@ extern "C" int todhip_verify_2d_batch_device(todhip_ctx* ctx, uint32_t n_frames,
   const size_t n_slots = (size_t)F * per;
   // an object needs max(3, min_inliers) matches of its frame's nq k: that bounds the list of active objects
   const uint32_t cap = F * std::min<uint32_t>(n_objs, per / std::max(3u, prm->min_inliers)) + 1u;
-  if (!ctx->pnp_ws) ctx->pnp_ws = new PnpWs();
-  PnpWs* ws = reinterpret_cast<PnpWs*>(ctx->pnp_ws);
+  PnpWs* ws = tod_ws<PnpWs>(ctx);
   hipStream_t st = ctx->stream;
   TOD_HIP(ws->X.reserve(n_slots * 12)); TOD_HIP(ws->q_idx.reserve(n_slots * 4));
   TOD_HIP(ws->hist.reserve((size_t)F * n_objs * 4)); TOD_HIP(ws->goff.reserve((size_t)F * n_objs * 4));
   TOD_HIP(ws->err.reserve((size_t)F * 8 * 4)); TOD_HIP(ws->spans.reserve((size_t)n_objs * 4)); TOD_HIP(ws->seeds.reserve((size_t)F * 4));
   TOD_HIP(ws->objs.reserve((size_t)cap * sizeof(ObjSpanP))); TOD_HIP(ws->na.reserve(64));
-  TOD_HIP(ws->best.reserve((size_t)cap * 8)); TOD_HIP(ws->flags.reserve(n_slots)); TOD_HIP(ws->results.reserve((size_t)cap * sizeof(ObjResult)));
   TOD_HIP(hipMemcpyAsync(ws->spans.p, spans, (size_t)n_objs * 4, hipMemcpyHostToDevice, st));
   TOD_HIP(hipMemcpyAsync(ws->seeds.p, seeds.data(), (size_t)F * 4, hipMemcpyHostToDevice, st));
-  int rc = tod_cluster_frames_nocloud(ctx, F, reinterpret_cast<const float*>(d_kp_xy), nq, reinterpret_cast<const uint32_t*>(d_counts),
-                                      reinterpret_cast<const todhip_dmatch*>(d_matches), reinterpret_cast<const float*>(d_matches_xyz), k,
-                                      n_objs, ws->X.as<float>(), ws->q_idx.as<uint32_t>(), ws->hist.as<uint32_t>(), ws->goff.as<uint32_t>(),
-                                      ws->err.as<uint32_t>());
+  rc = tod_cluster_frames_nocloud(ctx, F, reinterpret_cast<const float*>(d_kp_xy), nq, reinterpret_cast<const uint32_t*>(d_counts),
+                                  reinterpret_cast<const todhip_dmatch*>(d_matches), reinterpret_cast<const float*>(d_matches_xyz), k,
+                                  n_objs, ws->X.as<float>(), ws->q_idx.as<uint32_t>(), ws->hist.as<uint32_t>(), ws->goff.as<uint32_t>(),
+                                  ws->err.as<uint32_t>());
   if (rc != TODHIP_OK) return rc;
   hipLaunchKernelGGL(pnp_active_kernel, dim3(1), dim3(256), 0, st, ws->hist.as<uint32_t>(), ws->goff.as<uint32_t>(), ws->spans.as<float>(),
                      ws->seeds.as<uint32_t>(), F, n_objs, per, prm->min_inliers, cap, ws->objs.as<ObjSpanP>(), ws->na.as<uint32_t>());
@@ -603,47 +625,9 @@ extern "C" int todhip_verify_2d_batch_device(todhip_ctx* ctx, uint32_t n_frames,
     if (err[8 * (size_t)f] != 0u) return TODHIP_EINVAL;                 // an object index outside the DB, a count beyond k
   if (na > cap - 1u) return TODHIP_ESCRATCH;                            // (cannot happen: cap bounds the list)
   if (na == 0 || prm->n_ransac_iterations == 0) return TODHIP_OK;
-  TOD_HIP(hipMemsetAsync(ws->best.p, 0, (size_t)na * 8, st));
-  const Cam cam{(double)K9[0], (double)K9[4], (double)K9[2], (double)K9[5]};
-  const double err2 = (double)prm->sensor_error * (double)prm->sensor_error;
-  const float* kp = reinterpret_cast<const float*>(d_kp_xy);
-  hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3((prm->n_ransac_iterations + 255u) / 256u, na), dim3(256), 0, st, ws->objs.as<ObjSpanP>(),
-                     kp, ws->q_idx.as<uint32_t>(), ws->X.as<float>(), cam, prm->n_ransac_iterations, err2, ws->best.as<unsigned long long>());
-  hipLaunchKernelGGL(pnp_refine_kernel, dim3(na), dim3(64), 0, st, ws->objs.as<ObjSpanP>(), kp, ws->q_idx.as<uint32_t>(), ws->X.as<float>(),
-                     cam, err2, prm->min_inliers, ws->best.as<unsigned long long>(), ws->flags.as<uint8_t>(), ws->results.as<ObjResult>());
-  TOD_HIP(hipGetLastError());
-  std::vector<ObjResult> res(na);
-  std::vector<ObjSpanP> active(na);
-  std::vector<uint8_t> flags(n_slots);
-  std::vector<uint32_t> q_idx(n_slots);
-  TOD_HIP(hipMemcpyAsync(res.data(), ws->results.p, (size_t)na * sizeof(ObjResult), hipMemcpyDeviceToHost, st));
-  TOD_HIP(hipMemcpyAsync(active.data(), ws->objs.p, (size_t)na * sizeof(ObjSpanP), hipMemcpyDeviceToHost, st));
-  TOD_HIP(hipMemcpyAsync(flags.data(), ws->flags.p, n_slots, hipMemcpyDeviceToHost, st));
-  TOD_HIP(hipMemcpyAsync(q_idx.data(), ws->q_idx.p, n_slots * 4, hipMemcpyDeviceToHost, st));
-  TOD_HIP(hipStreamSynchronize(st));
-  uint32_t np = 0, ni = 0;
-  for (uint32_t a = 0; a < na; ++a) {                                   // frame major, objects ascending inside a frame
-    if (!res[a].valid) continue;
-    if (np >= cap_poses) return TODHIP_ECAPACITY;
-    todhip_pose& out = poses[np];
-    out.object = active[a].object;
-    std::memcpy(out.R, res[a].R, sizeof(out.R)); std::memcpy(out.t, res[a].t, sizeof(out.t));
-    out.inlier_begin = ni;
-    uint32_t last = 0xFFFFFFFFu;
-    for (uint32_t m = 0; m < active[a].n; ++m) {                       // keypoint indices of the frame, ascending, each once
-      const uint32_t q = q_idx[active[a].begin + m] - active[a].frame * nq;
-      if (!flags[active[a].begin + m] || q == last) continue;
-      if (ni >= cap_inl) return TODHIP_ECAPACITY;
-      inlier_kp[ni++] = last = q;
-    }
-    out.inlier_end = ni;
-    ++np;
-    if (pose_ptr) pose_ptr[active[a].frame + 1] = np;
-  }
-  if (pose_ptr) for (uint32_t f = 0; f < F; ++f) pose_ptr[f + 1] = std::max(pose_ptr[f + 1], pose_ptr[f]);   // frames without a pose
-  *n_poses = np; *n_inlier_kp = ni;
-  ctx->counters.last_poses = np;
-  return TODHIP_OK;
+  std::vector<ObjSpanP> active;                                          // (both lists are on the device: read back with the results)
+  std::vector<uint32_t> q_idx;
+  return solve_and_emit_2d(ctx, ws, reinterpret_cast<const float*>(d_kp_xy), F, nq, K9, prm, na, n_slots, active, q_idx, dst);
 }
 
 extern "C" int todhip_verify_2d_device(todhip_ctx* ctx, const void* d_kp_xy, uint32_t nq, const float* K9, const void* d_counts,

@@ -65,7 +65,8 @@ struct VerifyWs {
 
 // one workspace per frame slot of a batch; slot 0 also serves the single-frame entry points and the test hooks
 struct StreamCache;
-struct VerifyPool {
+struct VerifyPool : TodWs {
+  static constexpr int kSlot = kWsVerify;
   std::vector<VerifyWs*> slots; std::vector<StreamCache*> streams;
   std::vector<hipEvent_t> side_ev;                          // one per lane of a batch (Engine::run_ticks), created on first use
   // argument sets of a launch group's long lists (launch_many): one pair per lane, so that groups in flight on different streams
@@ -73,6 +74,7 @@ struct VerifyPool {
   static constexpr size_t kMaxLanes = 17;
   HostBuf args_stage[kMaxLanes]; DevBuf args_dev[kMaxLanes];
   DevBuf kceil; bool kceil_ready = false;                   // sprint_kernel: ceil(k) of ransac.h:130 per (|valid|, n_best), 65 x 65
+  ~VerifyPool() override;                                   // (below StreamCache)
 };
 // The flights' streams belong to the process, not to a context: a process has eight hardware queues for all of its streams
 // (DESIGN 7), the runtime deals streams onto them round robin, and every further stream -- busy or not -- makes it likelier that two
@@ -123,12 +125,8 @@ constexpr uint32_t kEvalLdsBig = 160u * 1024u - 512u;
 constexpr uint32_t kStackCap = 128u * 1024u;       // u16 entries per wave beyond the LDS part of the stack (256 KB)
 constexpr uint32_t kMaxEvalWaves = 4096u;          // hypotheses per evaluation batch
 
-VerifyPool* pool_of(todhip_ctx* ctx) {
-  if (!ctx->verify_ws) ctx->verify_ws = new VerifyPool();
-  return reinterpret_cast<VerifyPool*>(ctx->verify_ws);
-}
 VerifyWs* ws_of(todhip_ctx* ctx, size_t slot = 0) {
-  VerifyPool* p = pool_of(ctx);
+  VerifyPool* p = tod_ws<VerifyPool>(ctx);
   while (p->slots.size() <= slot) p->slots.push_back(new VerifyWs());
   return p->slots[slot];
 }
@@ -279,14 +277,10 @@ int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy
   return TODHIP_OK;
 }
 
-void tod_verify_ws_free(todhip_ctx* ctx) {
-  if (!ctx->verify_ws) return;
-  VerifyPool* p = reinterpret_cast<VerifyPool*>(ctx->verify_ws);
-  for (VerifyWs* ws : p->slots) delete ws;
-  for (StreamCache* c : p->streams) delete c;
-  for (hipEvent_t e : p->side_ev) (void)hipEventDestroy(e);
-  delete p;
-  ctx->verify_ws = nullptr;
+VerifyPool::~VerifyPool() {
+  for (VerifyWs* ws : slots) delete ws;
+  for (StreamCache* c : streams) delete c;
+  for (hipEvent_t e : side_ev) (void)hipEventDestroy(e);
 }
 
 extern "C" {

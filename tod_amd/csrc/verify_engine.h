@@ -330,7 +330,7 @@ struct Engine {
     }
     SLOT_HIP(s.stream->ensure_device(s.abs_pos + total_skip + s.sprint_margin, st));
     SprintArgs a;
-    a.objs = list; a.rnd = nullptr; a.rnd_len = 0; a.pos0 = s.abs_pos; a.kceil = pool_of(ctx)->kceil.as<uint32_t>();
+    a.objs = list; a.rnd = nullptr; a.rnd_len = 0; a.pos0 = s.abs_pos; a.kceil = tod_ws<VerifyPool>(ctx)->kceil.as<uint32_t>();
     a.out = ws->m_sprint_out.as<uint32_t>(); a.kp_out = ws->m_sprint_kp.as<uint32_t>();
     a.status = ws->sprint_status.as<EvalStatus>(); a.stack = ws->sprint_stack.as<uint16_t>();
     a.n_objs = (uint32_t)s.sprint_members.size(); a.max_iterations = prm->n_ransac_iterations; a.min_inliers = prm->min_inliers;
@@ -604,7 +604,7 @@ struct Engine {
     TOD_HIP(ws->m_small.reserve(kMailSmallWords * sizeof(uint32_t)));
     TOD_HIP(ws->kp_bits.reserve((size_t)(kp_words + 1) * sizeof(u64)));
     TOD_HIP(ws->m_kp.reserve((size_t)std::max(nq, 1u) * sizeof(uint32_t)));
-    VerifyPool* pool = pool_of(ctx);
+    VerifyPool* pool = tod_ws<VerifyPool>(ctx);
     if (!pool->kceil_ready) {
       // ransac_k per (|valid|, n_best), once: `iterations_ < k` (ransac.h:95) is `iterations_ < ceil(k)` for an integer
       // iterations_, so the device replays the loop test exactly from this table
@@ -649,7 +649,7 @@ struct Engine {
   template <class A, class KernP, class Extent>
   bool launch_many(hipStream_t st, KernP kern, const std::vector<A>& v, int slot_dim, Extent extent, size_t& used, uint32_t block, uint32_t lds,
                    bool by_class) {
-    VerifyPool* pool = pool_of(ctx);
+    VerifyPool* pool = tod_ws<VerifyPool>(ctx);
     HostBuf& args_stage = pool->args_stage[lane_now];
     DevBuf& args_dev = pool->args_dev[lane_now];
     const size_t bytes = v.size() * sizeof(A);
@@ -705,7 +705,7 @@ struct Engine {
     {
       const size_t n_eval = L.eval_small.size() + L.eval_direct.size() + L.eval_big.size();
       if (L.adj.size() > 4u * kManySlots || n_eval > kMaxSlots || L.prep_small.size() > kManySlots) {
-        VerifyPool* pool = pool_of(ctx);
+        VerifyPool* pool = tod_ws<VerifyPool>(ctx);
         const size_t need = L.finite.size() * sizeof(JobArgs) + L.adj.size() * sizeof(AdjArgs) + L.prep.size() * sizeof(PrepArgs) +
                             L.prep_small.size() * sizeof(PrepSmallArgs) + n_eval * sizeof(EvalArgs) + 4096u;
         stage.ok = pool->args_stage[lane_now].reserve(need) == hipSuccess && pool->args_dev[lane_now].reserve(need) == hipSuccess;   // (the lane is idle)
@@ -770,7 +770,7 @@ struct Engine {
   int run(std::vector<Slot*>& slots) {
     // stream caches live in the context (a harness that restarts rand() per frame reuses one stream for ever); a
     // few of the most recent start states are kept
-    std::vector<StreamCache*>& caches = pool_of(ctx)->streams;
+    std::vector<StreamCache*>& caches = tod_ws<VerifyPool>(ctx)->streams;
     for (Slot* s : slots) {
       s->start_draws = s->rng->draws; s->abs_pos = 0; s->stream = nullptr;
       for (StreamCache* c : caches) if (c->same_start(*s->rng)) { s->stream = c; break; }
@@ -832,7 +832,7 @@ struct Engine {
   };
   int run_ticks(std::vector<Slot*>& slots) {
     struct InAir { InAir() { n = g_batches_in_air.fetch_add(1) + 1; } ~InAir() { g_batches_in_air.fetch_sub(1); } int n; } in_air;
-    VerifyPool* pool = pool_of(ctx);
+    VerifyPool* pool = tod_ws<VerifyPool>(ctx);
     std::vector<hipStream_t> side;
     SideStreams::PerDevice* pd = nullptr;
     if (slots.size() > 1 && in_air.n <= 2 && n_side_streams() > 0) TOD_HIP(g_side_streams.get(ctx->device, n_side_streams(), side, &pd));
