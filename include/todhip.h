@@ -31,7 +31,9 @@ typedef enum {
   TODHIP_ECAPACITY = -4,   /* caller-provided output capacity too small                                         */
   TODHIP_ERANGE = -5,      /* keypoint outside the cloud / imgIdx outside the object table                      */
   TODHIP_ENOMEM = -6,
-  TODHIP_ESCRATCH = -7     /* verifier scratch budget exceeded (never silently wrong)                           */
+  TODHIP_ESCRATCH = -7,    /* verifier scratch budget exceeded (never silently wrong)                           */
+  TODHIP_EBUSY = -8,       /* pipeline: every ring slot holds a ticket that was not waited for yet / tickets outstanding   */
+  TODHIP_ETIMEOUT = -9     /* pipeline: the ticket was not finished within timeout_ms; it stays waitable                   */
 } todhip_status;
 
 typedef struct todhip_ctx todhip_ctx;
@@ -299,6 +301,89 @@ int todhip_verify_2d_batch_device(todhip_ctx*, uint32_t n_frames, const void* d_
                                   const void* d_matches, const void* d_matches_xyz, uint32_t k, const float* spans, uint32_t n_objs,
                                   const todhip_verify_params*, todhip_rng* rng, todhip_pose* poses, uint32_t* n_poses,
                                   uint32_t* pose_ptr, uint32_t* inlier_kp, uint32_t* n_inlier_kp);
+
+/* ---- the detection pipeline: stages A -> B -> C on batches of frames, overlapped ------------------------------ */
+/* One object that owns what a host otherwise has to assemble around the three batched stage calls: a matcher context on a
+ * TODHIP_STREAM_THROUGHPUT stream, orb_workers ORB contexts and verify_workers verifier contexts on TODHIP_STREAM_LATENCY streams
+ * (created as todhip_stream_create creates them, so todhip_set_cu_partition, called before, keeps its meaning), one host thread per
+ * context, and a ring of ring_depth sets of device buffers. A step of up to frames_per_step frames is submitted, gets a ticket, and
+ * runs todhip_orb_batch_device -> todhip_match_device (one DB pass for the step) -> todhip_verify_batch_device_depth; step i uses ORB
+ * worker i % orb_workers and verifier worker i % verify_workers, the matcher issues the steps in ticket order, and the verifier's
+ * stream waits for an event recorded behind the matcher's work of the step. So the matcher of one step runs beside ORB of later steps
+ * and the verifier of earlier ones (tod_amd/pipeline.py and bench.py's data-chained run have the same structure in Python).
+ * Result: frame f of a step yields exactly what the single-frame device chain yields on that frame alone against the same DB --
+ * todhip_orb_device (capacity n_features) -> todhip_match_device on its n_kp descriptors -> todhip_verify_device_depth with a
+ * generator seeded rng_seed: keypoints, poses and their order, R and t bit for bit, inlier lists. A frame with fewer than n_features
+ * keypoints is padded with match counts 0 on the device.
+ * Threading: submit, wait and get_stats may be called from any threads, also concurrently; each ticket is waited for once.
+ * The pipeline uses 1 + orb_workers + verify_workers streams plus the verifier's two process-wide side streams; see INTEGRATION.md
+ * for the number of hardware queues a host should allow before HIP initialises. */
+typedef struct todhip_pipeline todhip_pipeline;
+enum { TODHIP_FRAME_GRAY8 = 0, TODHIP_FRAME_BGR8 = 1, TODHIP_FRAME_BGRA8 = 2 };
+typedef struct {
+  uint32_t struct_size;                /* sizeof(todhip_pipeline_params), as todhip_pipeline_default_params sets it */
+  uint32_t frames_per_step;            /* B: 1..64 frames per submit */
+  uint32_t H, W;                       /* every frame; the depth image has the same size */
+  int      frame_format;               /* TODHIP_FRAME_* */
+  int      depth_is_u16;               /* uint16 mm (0 = none) or float m (NaN = none) */
+  float    K9[9];                      /* camera matrix, row-major */
+  uint32_t n_features, n_levels; float scale_factor;   /* ORB; n_features is also the per-frame query capacity */
+  uint32_t k, radius;                  /* matcher: 1..8, > 0 */
+  todhip_verify_params verify;
+  uint32_t rng_seed;                   /* every frame's generator starts from this srand seed (decision D4); 0 -> 1 */
+  uint32_t orb_workers, verify_workers, ring_depth;    /* 0 -> 1, 2, verify_workers + 2; ring_depth > verify_workers; workers <= 8, ring <= 16 */
+  uint32_t max_poses_per_frame;        /* 0 -> 64 */
+} todhip_pipeline_params;
+/* Cumulative since creation. The *_s fields are host seconds inside the stage calls, summed over the workers of a stage (orb_s
+ * includes the uploads and the colour conversion, match_issue_s only issues work, verify_s starts once the matcher's event has
+ * fired); the matcher-kernel fields are the matcher context's counters and stay 0 unless
+ * todhip_set_kernel_timing(todhip_pipeline_matcher(p), 1) was called. Steps that ended in an error are not counted. */
+typedef struct {
+  uint64_t steps, frames, keypoints, poses;
+  double   orb_s, match_issue_s, verify_s;
+  double   sum_match_kernel_ms;
+  uint64_t n_match_kernel_launches;
+} todhip_pipeline_stats;
+
+/* Zeroes *out, sets struct_size and the defaults: 32 frames of 480 x 640 GRAY8, float depth, 1000 features / 3 levels / 1.2,
+ * k 5, radius 55, verify 15 / 1000 / 0.01, seed 1, workers 1 + 2, ring 4, 64 poses per frame. K9 is the caller's to fill. */
+int  todhip_pipeline_default_params(todhip_pipeline_params* out);
+/* Parameters are checked before any device work (TODHIP_EINVAL); without a usable device TODHIP_EHIP. Allocates every buffer of the
+ * device form; the host form's pinned staging and upload buffers are allocated by a slot's first todhip_pipeline_submit. */
+int  todhip_pipeline_create(int device, const todhip_pipeline_params*, todhip_pipeline** out);
+void todhip_pipeline_destroy(todhip_pipeline*);          /* drains what is in flight, joins its threads */
+/* The matcher context, for todhip_set_ratio_test / _set_lsh / _set_matcher_engine / _set_kernel_timing: only while no ticket is
+ * outstanding. It is the pipeline's: do not call the match functions on it and do not destroy it. */
+todhip_ctx* todhip_pipeline_matcher(todhip_pipeline*);
+/* todhip_db_load[_device] into the matcher context (one device, desc_bytes == 32); the spans are kept for the verifier workers.
+ * TODHIP_EBUSY while a ticket is outstanding. */
+int  todhip_pipeline_db_load(todhip_pipeline*, const todhip_object*, uint32_t n_objs, uint32_t desc_bytes);
+int  todhip_pipeline_db_load_device(todhip_pipeline*, const todhip_object*, uint32_t n_objs, uint32_t desc_bytes);
+/* n_frames in 1..frames_per_step, frames and depth images densely packed back to back without row padding: a frame is H*W bytes
+ * (GRAY8), H*W*3 (BGR8) or H*W*4 (BGRA8), a depth image H*W uint16 or float values. Tickets count up from 1. Never blocks on the
+ * GPU: with ring_depth tickets submitted and not yet waited for it returns TODHIP_EBUSY (wait for one, then submit again).
+ * Host form: copies into pinned staging owned by the ring slot and returns; the caller may reuse its buffers at once.
+ * Device form: no copy -- the stages READ THE CALLER'S DEVICE BUFFERS UNTIL THAT TICKET'S todhip_pipeline_wait HAS RETURNED the
+ * results (or an error other than TODHIP_ETIMEOUT / TODHIP_ECAPACITY); they must be complete when submit is called. */
+int  todhip_pipeline_submit(todhip_pipeline*, const uint8_t* frames, const void* depth, uint32_t n_frames, uint64_t* ticket);
+int  todhip_pipeline_submit_device(todhip_pipeline*, const void* d_frames, const void* d_depth, uint32_t n_frames, uint64_t* ticket);
+/* Results of one ticket, in any order of tickets, each ticket once (a second wait, or an unknown ticket: TODHIP_EINVAL).
+ * timeout_ms == 0 waits without limit; otherwise TODHIP_ETIMEOUT leaves the ticket waitable. n_kp[n_frames]; kp_xy (may be NULL)
+ * [n_frames * n_features * 2], frame f's keypoints at row f * n_features, rows behind n_kp[f] zero; poses of frame f are
+ * poses[pose_ptr[f] .. pose_ptr[f+1]), inlier_begin/end index inlier_kp, whose entries are frame-local keypoint indices (as
+ * todhip_verify_batch_device). *n_poses / *n_inlier_kp: capacity in, count out; when one is too small: TODHIP_ECAPACITY with the
+ * needed counts written, and the ticket stays waitable. A stage's error (TODHIP_ENODB when no DB was loaded ...) is returned here and
+ * ends the ticket. After TODHIP_EHIP the pipeline issues no further GPU work: every later submit and wait returns TODHIP_EHIP. */
+int  todhip_pipeline_wait(todhip_pipeline*, uint64_t ticket, uint32_t timeout_ms,
+                          uint32_t* n_kp /*[n_frames]*/, float* kp_xy /*[n_frames*n_features*2], may be NULL*/,
+                          todhip_pose* poses, uint32_t* n_poses /*cap in, count out*/, uint32_t* pose_ptr /*[n_frames+1]*/,
+                          uint32_t* inlier_kp, uint32_t* n_inlier_kp /*cap in, count out*/);
+int  todhip_pipeline_get_stats(todhip_pipeline*, todhip_pipeline_stats* out);
+/* One device-resident BGR8 / BGRA8 image (channels 3 | 4, row stride src_stride bytes) -> gray (row stride gray_stride bytes), the
+ * conversion the pipeline runs in front of ORB: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14, what adapter/ecto_cells.hpp computes on
+ * the host. Asynchronous on the context's stream. */
+int  todhip_bgr_to_gray_device(todhip_ctx*, const void* d_src, uint32_t channels /*3|4*/, uint32_t H, uint32_t W,
+                               uint32_t src_stride, void* d_gray, uint32_t gray_stride);
 
 /* ---- training ----------------------------------------------------------------- */
 /* Per-observation arithmetic of the reference's Trainer cell (src/training/Trainer.cpp:121-187, training.cpp:57-195):

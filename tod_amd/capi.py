@@ -15,7 +15,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # instead of, never copied over, the product file
 LIB_PATH = os.environ.get("TODHIP_LIB_PATH") or os.path.join(_PKG, "libtodhip.so")
 
-OK, EINVAL, ENODB, EHIP, ECAPACITY, ERANGE, ENOMEM, ESCRATCH = 0, -1, -2, -3, -4, -5, -6, -7
+OK, EINVAL, ENODB, EHIP, ECAPACITY, ERANGE, ENOMEM, ESCRATCH, EBUSY, ETIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
+FRAME_GRAY8, FRAME_BGR8, FRAME_BGRA8 = 0, 1, 2
 
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
 
@@ -53,6 +54,20 @@ class Counters(C.Structure):
                 ("k4x_half_blocks_completed", C.c_uint64)]
 
 
+class PipelineParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("frames_per_step", C.c_uint32), ("H", C.c_uint32), ("W", C.c_uint32),
+                ("frame_format", C.c_int), ("depth_is_u16", C.c_int), ("K9", C.c_float * 9), ("n_features", C.c_uint32),
+                ("n_levels", C.c_uint32), ("scale_factor", C.c_float), ("k", C.c_uint32), ("radius", C.c_uint32),
+                ("verify", VerifyParams), ("rng_seed", C.c_uint32), ("orb_workers", C.c_uint32), ("verify_workers", C.c_uint32),
+                ("ring_depth", C.c_uint32), ("max_poses_per_frame", C.c_uint32)]
+
+
+class PipelineStats(C.Structure):
+    _fields_ = [("steps", C.c_uint64), ("frames", C.c_uint64), ("keypoints", C.c_uint64), ("poses", C.c_uint64),
+                ("orb_s", C.c_double), ("match_issue_s", C.c_double), ("verify_s", C.c_double),
+                ("sum_match_kernel_ms", C.c_double), ("n_match_kernel_launches", C.c_uint64)]
+
+
 # every symbol include/todhip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
     "todhip_version", "todhip_create", "todhip_destroy", "todhip_stream", "todhip_last_hip_error",
@@ -65,6 +80,9 @@ EXPORTS = [
     "todhip_match_l2", "todhip_match_l2_device",
     "todhip_model_begin", "todhip_model_add_observation", "todhip_model_finish", "todhip_model_device", "todhip_model_free",
     "todhip_rescale_depth", "todhip_rescale_depth_device", "todhip_verify_2d", "todhip_verify_2d_device", "todhip_verify_2d_batch_device", "todhip_set_lsh",
+    "todhip_pipeline_default_params", "todhip_pipeline_create", "todhip_pipeline_destroy", "todhip_pipeline_matcher",
+    "todhip_pipeline_db_load", "todhip_pipeline_db_load_device", "todhip_pipeline_submit", "todhip_pipeline_submit_device",
+    "todhip_pipeline_wait", "todhip_pipeline_get_stats", "todhip_bgr_to_gray_device",
 ]
 
 _lib = None
@@ -93,6 +111,8 @@ def lib():
         L.todhip_destroy.restype = None
         L.todhip_rng_seed.restype = None
         L.todhip_model_free.restype = None
+        L.todhip_pipeline_destroy.restype = None
+        L.todhip_pipeline_matcher.restype = C.c_void_p
         _lib = L
     return _lib
 
@@ -525,6 +545,127 @@ class Model:
         if self._h:
             lib().todhip_model_free(self._ctx._h, self._h)
             self._h = C.c_void_p()
+
+
+class _Borrowed(Context):
+    """A context somebody else owns (the pipeline's matcher): the setters work, close() does nothing."""
+
+    def __init__(self, handle):
+        self._h = C.c_void_p(handle)
+        self._keep = None
+
+    def close(self):
+        self._h = C.c_void_p()
+
+
+def pipeline_params(**kw):
+    """todhip_pipeline_default_params with the given fields replaced (K: 3x3 camera matrix, verify: (min_inliers, n_iter, err))."""
+    p = PipelineParams()
+    _check(lib().todhip_pipeline_default_params(C.byref(p)), "todhip_pipeline_default_params")
+    for key, v in kw.items():
+        if key == "K":
+            p.K9[:] = [float(x) for x in _k9(v)]
+        elif key == "verify":
+            p.verify = VerifyParams(*v)
+        else:
+            setattr(p, key, v)
+    return p
+
+
+class Pipeline:
+    """ORB -> matcher -> verifier on batches of frames behind submit / wait (todhip_pipeline). Methods return the library's status
+    where the protocol makes a non-OK status an answer (submit, wait, db_load); create raises."""
+
+    def __init__(self, device=0, params=None, **kw):
+        self.params = params if params is not None else pipeline_params(**kw)
+        self._h = C.c_void_p()
+        _check(lib().todhip_pipeline_create(C.c_int(device), C.byref(self.params), C.byref(self._h)), "todhip_pipeline_create")
+        self._n = {}                                                  # ticket -> n_frames
+
+    def close(self):
+        if self._h:
+            lib().todhip_pipeline_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def matcher(self):
+        return _Borrowed(lib().todhip_pipeline_matcher(self._h))
+
+    def db_load(self, desc, pts, obj_off):
+        """As Context.db_load; returns the status."""
+        desc = np.ascontiguousarray(desc, np.uint8)
+        pts = np.ascontiguousarray(pts, np.float32)
+        obj_off = np.asarray(obj_off, np.int64)
+        n_obj = len(obj_off) - 1
+        objs = (TodObject * max(n_obj, 1))()
+        for o in range(n_obj):
+            lo, hi = int(obj_off[o]), int(obj_off[o + 1])
+            objs[o].desc, objs[o].pts_xyz, objs[o].n = desc.ctypes.data + lo * 32, pts.ctypes.data + lo * 12, hi - lo
+        return lib().todhip_pipeline_db_load(self._h, objs, C.c_uint32(n_obj), C.c_uint32(32))
+
+    def db_load_models(self, models):
+        objs = (TodObject * len(models))()
+        for i, m in enumerate(models):
+            objs[i].desc, objs[i].pts_xyz, objs[i].n = m.device()
+        return lib().todhip_pipeline_db_load_device(self._h, objs, C.c_uint32(len(models)), C.c_uint32(32))
+
+    def submit(self, frames, depth, n_frames=None):
+        """Host form: frames u8 [n, H, W(, 3 | 4)], depth f32 | u16 [n, H, W] as numpy arrays. Returns (status, ticket)."""
+        fr = np.ascontiguousarray(frames, np.uint8)
+        dp = np.ascontiguousarray(depth, np.uint16 if self.params.depth_is_u16 else np.float32)
+        n = len(fr) if n_frames is None else n_frames
+        t = C.c_uint64(0)
+        rc = lib().todhip_pipeline_submit(self._h, _np_ptr(fr), _np_ptr(dp), C.c_uint32(n), C.byref(t))
+        if rc == OK:
+            self._n[t.value] = n
+        return rc, t.value
+
+    def submit_device(self, d_frames, d_depth, n_frames):
+        """Device form (ints from tensor.data_ptr()); the buffers are read until wait() has returned the ticket's results."""
+        t = C.c_uint64(0)
+        rc = lib().todhip_pipeline_submit_device(self._h, C.c_void_p(d_frames), C.c_void_p(d_depth), C.c_uint32(n_frames), C.byref(t))
+        if rc == OK:
+            self._n[t.value] = n_frames
+        return rc, t.value
+
+    def wait(self, ticket, timeout_ms=0, max_poses=None, max_inliers=None, want_kp=True):
+        """Returns (status, result). result (status OK): list per frame of dict(n_kp, kp_xy f32[n_kp, 2] or None, poses = list of pose
+        dicts as Context.verify_batch_device returns them). ECAPACITY: result = (poses needed, inlier keypoints needed)."""
+        n = self._n.get(ticket, 1)
+        nq = self.params.n_features
+        cap_p = self.params.max_poses_per_frame * n if max_poses is None else max_poses
+        cap_i = cap_p * nq if max_inliers is None else max_inliers
+        n_kp = (C.c_uint32 * n)()
+        kp = np.zeros((n, nq, 2), np.float32) if want_kp else None
+        if getattr(self, "_inl_cap", 0) < max(cap_i, 1):              # kept between calls (megabytes per step; results are copied out)
+            self._inl, self._inl_cap = np.zeros(max(cap_i, 1), np.uint32), max(cap_i, 1)
+        poses, inl = (Pose * max(cap_p, 1))(), self._inl
+        n_poses, n_inl, pose_ptr = C.c_uint32(cap_p), C.c_uint32(cap_i), (C.c_uint32 * (n + 1))()
+        rc = lib().todhip_pipeline_wait(self._h, C.c_uint64(ticket), C.c_uint32(timeout_ms), n_kp, None if kp is None else _np_ptr(kp),
+                                        poses, C.byref(n_poses), pose_ptr, _np_ptr(inl), C.byref(n_inl))
+        if rc == ECAPACITY:
+            return rc, (n_poses.value, n_inl.value)
+        if rc != ETIMEOUT:
+            self._n.pop(ticket, None)
+        if rc != OK:
+            return rc, None
+        return rc, [dict(n_kp=int(n_kp[f]), kp_xy=None if kp is None else kp[f, :n_kp[f]].copy(),
+                         poses=_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl)) for f in range(n)]
+
+    def stats(self):
+        s = PipelineStats()
+        _check(lib().todhip_pipeline_get_stats(self._h, C.byref(s)), "todhip_pipeline_get_stats")
+        return {name: getattr(s, name) for name, _ in PipelineStats._fields_}
+
+
+def bgr_to_gray_device(ctx, d_src, channels, H, W, src_stride, d_gray, gray_stride):
+    _check(lib().todhip_bgr_to_gray_device(ctx._h, C.c_void_p(d_src), C.c_uint32(channels), C.c_uint32(H), C.c_uint32(W),
+                                           C.c_uint32(src_stride), C.c_void_p(d_gray), C.c_uint32(gray_stride)), "todhip_bgr_to_gray_device")
 
 
 def set_cu_partition(latency_cus):
