@@ -148,6 +148,31 @@ int todhip_set_ratio_test(todhip_ctx*, float ratio);
  * May be called before or after todhip_db_load (the index is built for the resident shard either way). */
 int todhip_set_lsh(todhip_ctx*, uint32_t n_tables, uint32_t key_size, uint32_t multi_probe_level);
 
+/* Optional exact bit order of the resident Hamming DB. The matrix-core engine's partial-distance elimination
+ * (todhip_set_matcher_block_split) only fires when the bit positions a block evaluates first are informative; descriptors whose
+ * leading positions are biased or correlated (rBRIEF patterns trained elsewhere, cv::ORB) make nearly every block go on. With
+ * TODHIP_BIT_ORDER_INFORMATIVE_FIRST the todhip_db_load[_device] calls that follow permute the bit positions of the shard's rows, and
+ * every todhip_match* form permutes its queries the same way into a workspace of the context (the caller's buffer is never written):
+ * Hamming distance does not depend on the order, so row indices, distances and everything behind them are those of the unordered DB,
+ * and the LSH mode reads its key bits through the inverse map (same keys, same candidates). Off by default; desc_bytes == 32 only
+ * (a 512-byte float DB ignores it). The order belongs to the context and its resident shard: every shard of a sharded DB computes
+ * its own. A later load in mode TODHIP_BIT_ORDER_NONE restores the identity.
+ * Bit i of a descriptor is bit i % 8 (LSB first) of byte i / 8 = bit i % 32 of little-endian dword i / 32.
+ * Definition (exact integers, deterministic). Sample: S = min(shard_rows, 65536), sample row i = row floor(i * shard_rows / S);
+ * ones[b] = sample rows with bit b set, both[a][b] = with bits a and b set. v[b] = ones[b] (S - ones[b]). Candidates: v descending,
+ * ties by ascending b. Walking them once, b is accepted iff v[b] > 0 and 4 c(a, b)^2 < v[a] v[b] for every a accepted before it,
+ * c(a, b) = |S both[a][b] - ones[a] ones[b]| (|correlation| < 1/2: the ORB paper's greedy step with one fixed threshold). Ranks:
+ * the accepted bits, then the rejected ones (constant bits, copies of earlier bits), each in candidate order. Rank r is stored at
+ * position 32 E[r / 32] + r % 32, E = {0, 4, 1, 5, 2, 6, 3, 7}: a matrix instruction of a block covers dwords s and s + 4 of a row,
+ * so ranks 0-63 are what a block sees first, 0-127 what a 2-split sees. The layout serves the matrix-core engine; the vector-ALU
+ * engine tests after dwords 0-2, 0-3 and 0-5 and so sees ranks 0-31, 64-95 and 128-159 first -- exact all the same, but not the
+ * best order for that engine. Any other mode, or a null pointer: TODHIP_EINVAL. */
+enum { TODHIP_BIT_ORDER_NONE = 0, TODHIP_BIT_ORDER_INFORMATIVE_FIRST = 1 };
+int todhip_set_db_bit_order(todhip_ctx*, int mode);
+/* The order of the resident DB: stored position p holds original bit src_of[p]. The identity while the option is off or nothing
+ * is loaded. */
+int todhip_db_bit_order(const todhip_ctx*, uint8_t src_of[256]);
+
 /* Device-resident form of the same call (inputs already in HBM, outputs stay in HBM):
  * d_counts[nq] (matches kept per query), d_matches[nq*k], d_matches_xyz[nq*k*3], fixed stride k. */
 int todhip_match_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t k, uint32_t radius,
@@ -352,8 +377,9 @@ int  todhip_pipeline_default_params(todhip_pipeline_params* out);
  * device form; the host form's pinned staging and upload buffers are allocated by a slot's first todhip_pipeline_submit. */
 int  todhip_pipeline_create(int device, const todhip_pipeline_params*, todhip_pipeline** out);
 void todhip_pipeline_destroy(todhip_pipeline*);          /* drains what is in flight, joins its threads */
-/* The matcher context, for todhip_set_ratio_test / _set_lsh / _set_matcher_engine / _set_kernel_timing: only while no ticket is
- * outstanding. It is the pipeline's: do not call the match functions on it and do not destroy it. */
+/* The matcher context, for todhip_set_ratio_test / _set_lsh / _set_matcher_engine / _set_kernel_timing / _set_db_bit_order: only
+ * while no ticket is outstanding. It is the pipeline's: do not call the match functions on it and do not destroy it.
+ * todhip_set_db_bit_order(todhip_pipeline_matcher(p), 1) before todhip_pipeline_db_load[_device] orders the pipeline's DB. */
 todhip_ctx* todhip_pipeline_matcher(todhip_pipeline*);
 /* todhip_db_load[_device] into the matcher context (one device, desc_bytes == 32); the spans are kept for the verifier workers.
  * TODHIP_EBUSY while a ticket is outstanding. */

@@ -80,6 +80,7 @@ EXPORTS = [
     "todhip_match_l2", "todhip_match_l2_device",
     "todhip_model_begin", "todhip_model_add_observation", "todhip_model_finish", "todhip_model_device", "todhip_model_free",
     "todhip_rescale_depth", "todhip_rescale_depth_device", "todhip_verify_2d", "todhip_verify_2d_device", "todhip_verify_2d_batch_device", "todhip_set_lsh",
+    "todhip_set_db_bit_order", "todhip_db_bit_order",
     "todhip_pipeline_default_params", "todhip_pipeline_create", "todhip_pipeline_destroy", "todhip_pipeline_matcher",
     "todhip_pipeline_db_load", "todhip_pipeline_db_load_device", "todhip_pipeline_submit", "todhip_pipeline_submit_device",
     "todhip_pipeline_wait", "todhip_pipeline_get_stats", "todhip_bgr_to_gray_device",
@@ -113,6 +114,8 @@ def lib():
         L.todhip_model_free.restype = None
         L.todhip_pipeline_destroy.restype = None
         L.todhip_pipeline_matcher.restype = C.c_void_p
+        L.todhip_set_db_bit_order.argtypes, L.todhip_set_db_bit_order.restype = [C.c_void_p, C.c_int], C.c_int
+        L.todhip_db_bit_order.argtypes, L.todhip_db_bit_order.restype = [C.c_void_p, C.c_void_p], C.c_int
         _lib = L
     return _lib
 
@@ -210,6 +213,17 @@ class Context:
     def set_lsh(self, n_tables, key_size=16, multi_probe_level=1):
         """LSH-approximate mode of the Hamming matcher (0 tables = the exact search, the default)."""
         _check(lib().todhip_set_lsh(self._h, C.c_uint32(n_tables), C.c_uint32(key_size), C.c_uint32(multi_probe_level)), "todhip_set_lsh")
+
+    def set_db_bit_order(self, mode):
+        """0 off (default), 1 informative bits first: the db_load calls that follow store the rows' bit positions in that order and the
+        match calls permute their queries alike -- identical results (todhip_set_db_bit_order)"""
+        _check(lib().todhip_set_db_bit_order(self._h, C.c_int(mode)), "todhip_set_db_bit_order")
+
+    def db_bit_order(self):
+        """u8[256]: stored position p of the resident DB holds original bit src_of[p] (the identity when off / nothing loaded)"""
+        src_of = np.zeros(256, np.uint8)
+        _check(lib().todhip_db_bit_order(self._h, _np_ptr(src_of)), "todhip_db_bit_order")
+        return src_of
 
     def set_kernel_timing(self, enable):
         _check(lib().todhip_set_kernel_timing(self._h, C.c_int(1 if enable else 0)), "todhip_set_kernel_timing")

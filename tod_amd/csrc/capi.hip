@@ -263,6 +263,10 @@ static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_o
     int rc = tod_l2_db_prepare(ctx);
     if (rc != TODHIP_OK) return rc;
   }
+  if (ctx->bit_order_mode != TODHIP_BIT_ORDER_NONE || ctx->bit_order_on) {   // todhip_set_db_bit_order: reorder the rows, or back to the identity
+    int rc = tod_bit_order_load(ctx);
+    if (rc != TODHIP_OK) return rc;
+  }
   if (tod_lsh_enabled(ctx)) {                               // todhip_set_lsh before the load: index this shard
     int rc = tod_lsh_build(ctx);
     if (rc != TODHIP_OK) return rc;

@@ -129,10 +129,19 @@ struct todhip_ctx {
   HostBuf k4x_stats_host; DevBuf k4x_stats_dev;
   K4xSplit k4x;                              // k4x.force: todhip_set_matcher_block_split
   float ratio = 0.f;                         // todhip_set_ratio_test (0 = off)
+  // todhip_set_db_bit_order (db_bitorder.hip): the mode the next load uses; the order of the resident shard (stored position p holds
+  // original bit bit_src_of[p]) and whether it differs from the identity; its device copy and the queries' workspace -- both stay
+  // empty until a load computes an order
+  int bit_order_mode = TODHIP_BIT_ORDER_NONE;
+  bool bit_order_on = false;
+  uint8_t bit_src_of[256];
+  DevBuf bit_tab, m_qord;
 
   std::vector<todhip_round_trace> traces;
 
   std::unique_ptr<TodWs> ws[kWsSlots];       // todhip_destroy releases them before the events and the stream go
+
+  todhip_ctx() { for (int p = 0; p < 256; ++p) bit_src_of[p] = (uint8_t)p; }
 };
 
 template <typename T> T* tod_ws(todhip_ctx* ctx) {
@@ -175,6 +184,10 @@ int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_s
 int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy, uint32_t nq, const uint32_t* d_counts,
                                const todhip_dmatch* d_matches, const float* d_mxyz, uint32_t k, uint32_t n_objs, float* d_X,
                                uint32_t* d_qidx, uint32_t* d_hist, uint32_t* d_goff, uint32_t* d_err);
+// db_bitorder.hip: the optional bit order of the resident Hamming DB (todhip_set_db_bit_order). _load: todhip_db_load's step between
+// the rows' arrival and the LSH index; _queries: nq query rows in the resident order (only while ctx->bit_order_on)
+int tod_bit_order_load(todhip_ctx* ctx);
+int tod_bit_order_queries(todhip_ctx* ctx, const void* d_q, uint32_t nq, const void** d_out);
 // lsh.hip: the optional LSH-approximate mode (todhip_set_lsh)
 bool tod_lsh_enabled(const todhip_ctx* ctx);
 int tod_lsh_build(todhip_ctx* ctx);

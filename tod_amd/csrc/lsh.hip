@@ -178,6 +178,11 @@ int tod_lsh_build(todhip_ctx* ctx) {
   const size_t stride = ((size_t)1 << ks) + 1;
   std::vector<uint8_t> pos((size_t)T * ks);
   for (uint32_t t = 0; t < T; ++t) key_bits(t, ks, &pos[(size_t)t * ks]);
+  if (ctx->bit_order_on) {                                             // todhip_set_db_bit_order: rows and queries are stored in another bit order;
+    uint8_t at[256];                                                   // the keys keep their bits -- read where those are now
+    for (int p = 0; p < 256; ++p) at[ctx->bit_src_of[p]] = (uint8_t)p;
+    for (uint8_t& b : pos) b = at[b];
+  }
   std::vector<uint32_t> masks;                                         // every xor mask of at most `level` key bits, the query's own bucket first
   masks.push_back(0u);
   for (uint32_t a = 0; a < ks && ws->level >= 1; ++a) masks.push_back(1u << a);
