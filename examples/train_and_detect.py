@@ -6,8 +6,10 @@
     todhip_orb -> todhip_match -> todhip_verify                           <- detector.py: features -> matcher -> guess generator
 
 Synthetic data (a textured plane rendered at a known pose), so that the recovered pose can be checked.
-Run on a machine with an MI355X:  python examples/train_and_detect.py
+Run on a machine with an MI355X:  python examples/train_and_detect.py [--learn-pattern]
+--learn-pattern: first learn an rBRIEF test pattern from the training view (todhip_pattern_learn_*), then train and detect with it.
 """
+import argparse
 import os
 import sys
 
@@ -35,15 +37,28 @@ def render(texture, theta, shift_px):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--learn-pattern", action="store_true", help="learn the ORB test pattern from the training view first")
+    args = ap.parse_args()
     ctx = capi.Context(0)
     texture = synth.make_image(321)
     depth = np.full((H, W), Z, np.float32)
     mask = np.zeros((H, W), np.uint8); mask[40:H - 40, 40:W - 40] = 255
 
+    # --- optionally the test pattern itself: model and queries must then both be described with it
+    pattern = None
+    if args.learn_pattern:
+        learner = capi.PatternLearner(ctx)
+        n = learner.add_view(texture, mask, n_features=1500, n_levels=3, scale_factor=1.2)
+        res = learner.finish(capi.PATTERN_ORDER_MATCHER); learner.close()
+        pattern = res["pattern"]
+        print("pattern: learned from %d keypoints and %d candidate tests, accepted per round %s" %
+              (n, res["n_candidates"], res["accepted_in_round"]))
+
     # --- training: one observation; the object frame is the training camera frame (R = I, T = 0)
     model = capi.Model(ctx, 4000)
     model.add_observation(texture, mask, depth, K, np.eye(3, dtype=np.float32), np.zeros(3, np.float32), n_features=1500,
-                          n_levels=3, scale_factor=1.2)
+                          n_levels=3, scale_factor=1.2, pattern=pattern)
     desc, pts = model.finish(); model.close()
     print("model: %d descriptors with 3D points" % len(desc))
     spans = ctx.db_load(desc, pts, np.array([0, len(desc)], np.uint32))
@@ -51,7 +66,7 @@ def main():
     # --- detection in a rotated, shifted view
     theta, shift = np.deg2rad(33.0), (24.0, -15.0)
     view = render(texture, theta, shift)
-    kp, aux, q = ctx.orb(view, 1000, 3, 1.2)
+    kp, aux, q = ctx.orb(view, 1000, 3, 1.2, pattern=pattern)
     v, u = np.mgrid[0:H, 0:W].astype(np.float32)
     cloud = np.stack([(u - K[0, 2]) * Z / F, (v - K[1, 2]) * Z / F, np.full((H, W), Z, np.float32)], axis=2).astype(np.float32)
     row_ptr, matches, xyz = ctx.match(q, 5, 55)

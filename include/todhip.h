@@ -405,6 +405,10 @@ int  todhip_pipeline_wait(todhip_pipeline*, uint64_t ticket, uint32_t timeout_ms
                           todhip_pose* poses, uint32_t* n_poses /*cap in, count out*/, uint32_t* pose_ptr /*[n_frames+1]*/,
                           uint32_t* inlier_kp, uint32_t* n_inlier_kp /*cap in, count out*/);
 int  todhip_pipeline_get_stats(todhip_pipeline*, todhip_pipeline_stats* out);
+/* The ORB pattern of the pipeline's ORB workers (256 x 4 int8, copied; NULL = the built-in one), from the next submit on: how a
+ * pattern learned by todhip_pattern_learn_* reaches the batched path. The DB must hold descriptors of the same pattern.
+ * TODHIP_EBUSY while a ticket is outstanding. */
+int  todhip_pipeline_set_pattern(todhip_pipeline*, const int8_t* pattern /* 256 x 4; NULL = built-in */);
 /* One device-resident BGR8 / BGRA8 image (channels 3 | 4, row stride src_stride bytes) -> gray (row stride gray_stride bytes), the
  * conversion the pipeline runs in front of ORB: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14, what adapter/ecto_cells.hpp computes on
  * the host. Asynchronous on the context's stream. */
@@ -442,6 +446,51 @@ int  todhip_model_finish(todhip_ctx*, todhip_model*, uint8_t* desc, float* pts_x
  * CouchDB, ModelFiller.cpp:23-24, and DescriptorMatcher::parameter_callback reads it back, DescriptorMatcher.cpp:60-129). */
 int  todhip_model_device(todhip_ctx*, todhip_model*, const void** d_desc, const void** d_pts_xyz, uint32_t* n);
 void todhip_model_free(todhip_ctx*, todhip_model*);
+
+/* ---- training: an rBRIEF test pattern learned from training views (Rublee et al., ORB, section 4.3) ------------------ */
+/* The built-in pattern of todhip_orb* is 256 seeded random tests: steered BRIEF, whose bits are biased and correlated. A learner
+ * collects the keypoints of training views, evaluates every candidate test on every keypoint's steered patch, and picks 256 tests
+ * whose means are near 0.5 and which are pairwise uncorrelated. The result is a `pattern` argument for every todhip_orb* form,
+ * todhip_model_add_observation and todhip_pipeline_set_pattern; DB and queries must be described with the same pattern. One learner
+ * call in flight per context, as everywhere. Definition (exact integers, deterministic):
+ * Candidates: M tests (x0, y0, x1, y1) in int8, 256 <= M <= 65536, every point with x^2 + y^2 <= 169 (the built-in pattern's disc: a
+ * rotated, rounded point stays inside the 31 x 31 patch); anything else, or capacity_keypoints of 0 or above 32768: TODHIP_EINVAL.
+ * candidates == NULL (n_candidates ignored) selects the built-in set: G = the points with x and y even and x^2 + y^2 <= 169, ordered
+ * by y ascending, then x ascending; the candidates are all pairs i < j of G, in lexicographic (i, j) order, at squared distance >= 16,
+ * test = (G[i], G[j]).
+ * Keypoints: add_view runs the detection stages of todhip_orb_masked with the same arguments (pyramid, FAST + NMS, Harris ranking,
+ * blur, intensity-centroid angle; output capacity n_features) and adds that call's keypoints in its output order, as many as still
+ * fit below capacity_keypoints: *n_added. Keypoint n of the learner is the n-th added overall, N their number. The device form takes
+ * d_gray (row stride `stride`) and d_mask (row stride W, may be NULL) in HBM.
+ * Response matrix: R[c][n] = 1 iff candidate c, steered for keypoint n exactly as a pattern row is steered for a descriptor bit,
+ * reads blur[p0] < blur[p1]. So for any 256 candidates used as a `pattern`, bit b of todhip_orb_masked's descriptor of keypoint n is
+ * R[that candidate][n]. Stored candidate-major: bit n % 32 of word n / 32 of row c, ceil(N / 32) words per row, padding bits zero.
+ * Selection (finish; N == 0: TODHIP_EINVAL): ones[c] = popcount of row c, both[a][c] = popcount of (row a & row c),
+ * v[c] = ones[c] (N - ones[c]). Candidate order: v descending, ties by ascending c. g(a, c) = |N both[a][c] - ones[a] ones[c]|.
+ * Rounds 1-4 use s = 6, 4, 2, 0: a round walks the not yet accepted candidates in candidate order and accepts c iff v[c] > 0 and
+ * (g(a, c)^2 << s) < v[a] v[c] for every a accepted so far, in any round (|correlation| < 1/8, 1/4, 1/2, 1: the paper's "raise the
+ * threshold and go again"). Round 5: the remaining candidates with v > 0, in candidate order. Round 6: the rest, in candidate order.
+ * Everything stops at 256 accepted. With N <= 2^15 every term fits an unsigned 64-bit integer (g <= 2^28, g^2 << 6 <= 2^62).
+ * Outputs: chosen[r] = the candidate accepted r-th, round_of[r] in 1..6 (both may be NULL), stats (may be NULL); pattern row pos(r) =
+ * candidate chosen[r], pos(r) = r for TODHIP_PATTERN_ORDER_RANK and 32 E[r / 32] + r % 32, E = {0, 4, 1, 5, 2, 6, 3, 7}, for
+ * TODHIP_PATTERN_ORDER_MATCHER -- the layout todhip_set_db_bit_order documents: ranks 0-127 are what a 2-split block of the matrix-core
+ * matcher sees first. Any other order: TODHIP_EINVAL. finish may be called again (another order, or after further views). */
+typedef struct todhip_pattern_learner todhip_pattern_learner;
+enum { TODHIP_PATTERN_ORDER_RANK = 0, TODHIP_PATTERN_ORDER_MATCHER = 1 };
+typedef struct { uint32_t n_keypoints, n_candidates, accepted_in_round[6]; } todhip_pattern_stats;
+int  todhip_pattern_learn_begin(todhip_ctx*, const int8_t* candidates /* M x 4, or NULL */, uint32_t n_candidates,
+                                uint32_t capacity_keypoints, todhip_pattern_learner** out);
+int  todhip_pattern_learn_add_view(todhip_ctx*, todhip_pattern_learner*, const uint8_t* gray, const uint8_t* mask /* may be NULL */,
+                                   uint32_t H, uint32_t W, uint32_t stride, uint32_t n_features, uint32_t n_levels,
+                                   float scale_factor, uint32_t* n_added);
+int  todhip_pattern_learn_add_view_device(todhip_ctx*, todhip_pattern_learner*, const void* d_gray, const void* d_mask /* may be NULL */,
+                                          uint32_t H, uint32_t W, uint32_t stride, uint32_t n_features, uint32_t n_levels,
+                                          float scale_factor, uint32_t* n_added);
+int  todhip_pattern_learn_finish(todhip_ctx*, todhip_pattern_learner*, int order, int8_t pattern[1024], uint32_t chosen[256],
+                                 uint8_t round_of[256], todhip_pattern_stats*);
+/* test hook: rows first .. first + count - 1 of the response matrix, count x ceil(N / 32) u32, to the host */
+int  todhip_pattern_learn_responses(todhip_ctx*, todhip_pattern_learner*, uint32_t first, uint32_t count, uint32_t* words);
+void todhip_pattern_learn_free(todhip_ctx*, todhip_pattern_learner*);
 
 /* ---- diagnostics --------------------------------------------------------------------------------- */
 /* Per-RANSAC-round trace of the last todhip_verify call (what GuessGenerator.cpp:202 prints, plus the

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("TODHIP_LIB_PATH") or os.path.join(_PKG, "libtodhip.so
 
 OK, EINVAL, ENODB, EHIP, ECAPACITY, ERANGE, ENOMEM, ESCRATCH, EBUSY, ETIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
 FRAME_GRAY8, FRAME_BGR8, FRAME_BGRA8 = 0, 1, 2
+PATTERN_ORDER_RANK, PATTERN_ORDER_MATCHER = 0, 1
 
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
 
@@ -68,6 +69,10 @@ class PipelineStats(C.Structure):
                 ("sum_match_kernel_ms", C.c_double), ("n_match_kernel_launches", C.c_uint64)]
 
 
+class PatternStats(C.Structure):
+    _fields_ = [("n_keypoints", C.c_uint32), ("n_candidates", C.c_uint32), ("accepted_in_round", C.c_uint32 * 6)]
+
+
 # every symbol include/todhip.h declares (checked by tests/test_abi.py against the header text)
 EXPORTS = [
     "todhip_version", "todhip_create", "todhip_destroy", "todhip_stream", "todhip_last_hip_error",
@@ -84,6 +89,8 @@ EXPORTS = [
     "todhip_pipeline_default_params", "todhip_pipeline_create", "todhip_pipeline_destroy", "todhip_pipeline_matcher",
     "todhip_pipeline_db_load", "todhip_pipeline_db_load_device", "todhip_pipeline_submit", "todhip_pipeline_submit_device",
     "todhip_pipeline_wait", "todhip_pipeline_get_stats", "todhip_bgr_to_gray_device",
+    "todhip_pattern_learn_begin", "todhip_pattern_learn_add_view", "todhip_pattern_learn_add_view_device", "todhip_pattern_learn_finish",
+    "todhip_pattern_learn_responses", "todhip_pattern_learn_free", "todhip_pipeline_set_pattern",
 ]
 
 _lib = None
@@ -113,6 +120,7 @@ def lib():
         L.todhip_rng_seed.restype = None
         L.todhip_model_free.restype = None
         L.todhip_pipeline_destroy.restype = None
+        L.todhip_pattern_learn_free.restype = None
         L.todhip_pipeline_matcher.restype = C.c_void_p
         L.todhip_set_db_bit_order.argtypes, L.todhip_set_db_bit_order.restype = [C.c_void_p, C.c_int], C.c_int
         L.todhip_db_bit_order.argtypes, L.todhip_db_bit_order.restype = [C.c_void_p, C.c_void_p], C.c_int
@@ -480,20 +488,24 @@ class Context:
         n = n_out.value
         return kp[:n].copy(), aux[:n].copy(), desc[:n].copy()
 
-    def orb_device(self, d_gray, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux, d_desc, cap):
+    def orb_device(self, d_gray, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux, d_desc, cap, pattern=None):
         n_out = C.c_uint32(cap)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
         rc = lib().todhip_orb_device(self._h, C.c_void_p(d_gray), C.c_uint32(H), C.c_uint32(W), C.c_uint32(stride),
-                                     C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor), None,
+                                     C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor),
+                                     None if pat is None else _np_ptr(pat),
                                      C.c_void_p(d_kp_xy), C.c_void_p(d_kp_aux), C.c_void_p(d_desc), C.byref(n_out))
         _check(rc, "todhip_orb_device")
         return n_out.value
 
     def orb_batch_device(self, d_gray, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux,
-                         d_desc, cap):
+                         d_desc, cap, pattern=None):
         n = (C.c_uint32 * n_frames)()
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
         rc = lib().todhip_orb_batch_device(self._h, C.c_void_p(d_gray), C.c_uint32(n_frames), C.c_uint64(frame_stride), C.c_uint32(H),
                                            C.c_uint32(W), C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels),
-                                           C.c_float(scale_factor), None, C.c_void_p(d_kp_xy), C.c_void_p(d_kp_aux),
+                                           C.c_float(scale_factor), None if pat is None else _np_ptr(pat), C.c_void_p(d_kp_xy),
+                                           C.c_void_p(d_kp_aux),
                                            C.c_void_p(d_desc), C.c_uint32(cap), n)
         _check(rc, "todhip_orb_batch_device")
         return list(n)
@@ -523,7 +535,7 @@ class Model:
         self._cap = capacity_rows
         _check(lib().todhip_model_begin(ctx._h, C.c_uint32(capacity_rows), C.byref(self._h)), "todhip_model_begin")
 
-    def add_observation(self, gray, mask, depth, K, R, T, n_features=500, n_levels=8, scale_factor=1.2):
+    def add_observation(self, gray, mask, depth, K, R, T, n_features=500, n_levels=8, scale_factor=1.2, pattern=None):
         g = np.ascontiguousarray(gray, np.uint8)
         mk = np.ascontiguousarray(mask, np.uint8)
         H, W = g.shape
@@ -535,10 +547,11 @@ class Model:
         R9 = np.ascontiguousarray(R, np.float32).reshape(9)
         T3 = np.ascontiguousarray(T, np.float32).reshape(3)
         n = C.c_uint32(0)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
         rc = lib().todhip_model_add_observation(self._ctx._h, self._h, _np_ptr(g), _np_ptr(mk), _np_ptr(d),
                                                 C.c_int(1 if u16 else 0), C.c_uint32(H), C.c_uint32(W), _np_ptr(K9),
                                                 _np_ptr(R9), _np_ptr(T3), C.c_uint32(n_features), C.c_uint32(n_levels),
-                                                C.c_float(scale_factor), None, C.byref(n))
+                                                C.c_float(scale_factor), None if pat is None else _np_ptr(pat), C.byref(n))
         _check(rc, "todhip_model_add_observation")
         return n.value
 
@@ -558,6 +571,64 @@ class Model:
     def close(self):
         if self._h:
             lib().todhip_model_free(self._ctx._h, self._h)
+            self._h = C.c_void_p()
+
+
+class PatternLearner:
+    """An rBRIEF test pattern learned from training views (todhip_pattern_learn_*): add_view() per view, then finish() -> the pattern
+    for Context.orb(pattern=...), Model.add_observation(pattern=...) and Pipeline.set_pattern. candidates: int8 [M, 4] tests
+    (x0, y0, x1, y1), or None for the built-in set."""
+
+    def __init__(self, ctx, capacity_keypoints=32768, candidates=None):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self.n_keypoints = 0
+        cand = None if candidates is None else np.ascontiguousarray(candidates, np.int8).reshape(-1, 4)
+        _check(lib().todhip_pattern_learn_begin(ctx._h, None if cand is None else _np_ptr(cand), C.c_uint32(0 if cand is None else len(cand)),
+                                                C.c_uint32(capacity_keypoints), C.byref(self._h)), "todhip_pattern_learn_begin")
+
+    def add_view(self, gray, mask=None, n_features=500, n_levels=8, scale_factor=1.2):
+        """The keypoints todhip_orb_masked finds in the view, as many as still fit; returns their number."""
+        g = np.ascontiguousarray(gray, np.uint8)
+        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        H, W = g.shape
+        n = C.c_uint32(0)
+        rc = lib().todhip_pattern_learn_add_view(self._ctx._h, self._h, _np_ptr(g), None if mk is None else _np_ptr(mk), C.c_uint32(H),
+                                                 C.c_uint32(W), C.c_uint32(W), C.c_uint32(n_features), C.c_uint32(n_levels),
+                                                 C.c_float(scale_factor), C.byref(n))
+        _check(rc, "todhip_pattern_learn_add_view")
+        self.n_keypoints += n.value
+        return n.value
+
+    def add_view_device(self, d_gray, d_mask, H, W, stride, n_features=500, n_levels=8, scale_factor=1.2):
+        """Device-pointer form (ints from tensor.data_ptr(); d_mask: row stride W, or None)."""
+        n = C.c_uint32(0)
+        rc = lib().todhip_pattern_learn_add_view_device(self._ctx._h, self._h, C.c_void_p(d_gray), C.c_void_p(d_mask), C.c_uint32(H),
+                                                        C.c_uint32(W), C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels),
+                                                        C.c_float(scale_factor), C.byref(n))
+        _check(rc, "todhip_pattern_learn_add_view_device")
+        self.n_keypoints += n.value
+        return n.value
+
+    def finish(self, order=PATTERN_ORDER_MATCHER):
+        """-> dict(pattern i8[256, 4], chosen u32[256], round_of u8[256], n_keypoints, n_candidates, accepted_in_round [6])"""
+        pattern, chosen, round_of = np.zeros((256, 4), np.int8), np.zeros(256, np.uint32), np.zeros(256, np.uint8)
+        st = PatternStats()
+        _check(lib().todhip_pattern_learn_finish(self._ctx._h, self._h, C.c_int(order), _np_ptr(pattern), _np_ptr(chosen), _np_ptr(round_of),
+                                                 C.byref(st)), "todhip_pattern_learn_finish")
+        return dict(pattern=pattern, chosen=chosen, round_of=round_of, n_keypoints=int(st.n_keypoints), n_candidates=int(st.n_candidates),
+                    accepted_in_round=[int(x) for x in st.accepted_in_round])
+
+    def responses(self, first, count):
+        """Rows first .. first + count - 1 of the response matrix: u32 [count, ceil(n_keypoints / 32)] (test hook)."""
+        words = np.zeros((count, (self.n_keypoints + 31) // 32), np.uint32)
+        _check(lib().todhip_pattern_learn_responses(self._ctx._h, self._h, C.c_uint32(first), C.c_uint32(count), _np_ptr(words)),
+               "todhip_pattern_learn_responses")
+        return words
+
+    def close(self):
+        if self._h:
+            lib().todhip_pattern_learn_free(self._ctx._h, self._h)
             self._h = C.c_void_p()
 
 
@@ -627,6 +698,13 @@ class Pipeline:
         for i, m in enumerate(models):
             objs[i].desc, objs[i].pts_xyz, objs[i].n = m.device()
         return lib().todhip_pipeline_db_load_device(self._h, objs, C.c_uint32(len(models)), C.c_uint32(32))
+
+    def set_pattern(self, pattern):
+        """The ORB workers' pattern from the next submit on (i8 [256, 4], None = built-in); returns the status (EBUSY while a ticket
+        is outstanding)."""
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
+        assert pat is None or pat.size == 1024
+        return lib().todhip_pipeline_set_pattern(self._h, None if pat is None else _np_ptr(pat))
 
     def submit(self, frames, depth, n_frames=None):
         """Host form: frames u8 [n, H, W(, 3 | 4)], depth f32 | u16 [n, H, W] as numpy arrays. Returns (status, ticket)."""

@@ -23,20 +23,16 @@
 // stage time unchanged within the spread
 #define TOD_LATENCY_PRIO_LEVEL 0
 #include "ctx.h"
+#include "orb_stages.h"
+
+using namespace tod_orb;
 
 namespace {
 
-constexpr int kEdge = 31;
-constexpr int kHalfPatch = 15;
 constexpr int kFastThr = 20;
-constexpr int kMaxLevels = 16;
 
-struct Cand { int x, y, score; float harris; };
-
-// control words of one level and one frame (device): what the selection kernels hand to each other without a
-// host round trip; [8 + l] = keypoints of level l
+// control words of one level and one frame (orb_stages.h: kCtlWords of them)
 enum { W_NCAND = 0, W_NSEL1 = 1, W_THR = 2, W_NEED_EQ = 3, W_NEQ = 4, W_NGT = 5, W_WANT = 6, W_HIST = 32 };
-constexpr uint32_t kCtlWords = 512;
 
 // same generator as the CPU restatement: seeded xorshift, points inside radius 13
 void default_pattern(int8_t* pat) {
@@ -66,14 +62,6 @@ void disc_umax(int* umax) {
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// geometry of the pyramid levels; want[l] == 0: the level yields nothing (too small, or no features asked of it)
-struct LevelTab {
-  uint32_t n_levels, F;
-  const uint8_t* img[kMaxLevels];                          // level l of frame 0 (frame stride: the level-0 pixel count)
-  uint32_t h[kMaxLevels], w[kMaxLevels], want[kMaxLevels];
-  float scale[kMaxLevels];
-};
 
 __global__ __launch_bounds__(256) void copy_rows_kernel(const uint8_t* __restrict__ src, uint32_t stride, uint8_t* dst,
                                                         uint32_t h, uint32_t w, size_t src_fs, size_t dst_fs) {
@@ -397,32 +385,14 @@ __global__ __launch_bounds__(256) void describe_kernel(LevelTab T, DescribeArgs 
   if (o >= A.cap) return;
   const Cand c = A.sel[i];
   const int x = c.x, y = c.y, W = (int)A.w;
-  int m10 = 0, m01 = 0;
-  if (l < 31u) {
-    const int v = (int)l - kHalfPatch;
-    const int d = v == 0 ? kHalfPatch : A.umax[v < 0 ? -v : v];
-    int rs = 0;
-    for (int u = -d; u <= d; ++u) {
-      const int px = A.img[(size_t)(y + v) * W + x + u];
-      m10 += u * px;
-      rs += px;
-    }
-    m01 = v * rs;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { m10 += __shfl_xor(m10, off); m01 += __shfl_xor(m01, off); }
+  int m10, m01;
+  patch_moments(A.img, W, x, y, A.umax, l, m10, m01);
   const float fm10 = (float)m10, fm01 = (float)m01;
-  const float nrm = sqrtf(fm10 * fm10 + fm01 * fm01);
-  const float ca = nrm > 0.f ? fm10 / nrm : 1.f, sa = nrm > 0.f ? fm01 / nrm : 0.f;
+  float ca, sa;
+  steer_of(fm10, fm01, ca, sa);
   uint32_t nib = 0;
 #pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int8_t* pp = A.pattern + 4 * (4 * (int)l + b);
-    const int x0 = (int)rintf((float)pp[0] * ca - (float)pp[1] * sa), y0 = (int)rintf((float)pp[0] * sa + (float)pp[1] * ca);
-    const int x1 = (int)rintf((float)pp[2] * ca - (float)pp[3] * sa), y1 = (int)rintf((float)pp[2] * sa + (float)pp[3] * ca);
-    const int t0 = A.blur[(size_t)(y + y0) * W + (x + x0)], t1 = A.blur[(size_t)(y + y1) * W + (x + x1)];
-    nib |= (uint32_t)(t0 < t1) << b;
-  }
+  for (int b = 0; b < 4; ++b) nib |= (uint32_t)steered_test(A.blur, W, x, y, ca, sa, A.pattern + 4 * (4 * (int)l + b)) << b;
   const uint32_t hi = __shfl_down(nib, 1);
   if ((l & 1u) == 0u) A.desc[(size_t)o * 32 + (l >> 1)] = (uint8_t)(nib | (hi << 4));
   if (l == 0) {
@@ -464,6 +434,8 @@ struct OrbWs : TodWs {
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
   struct Key { uint32_t H, W, n_features, n_levels, cap, F; float sf; const void *kp, *aux, *desc, *img0, *mask; } key = {};
+  LevelTab tab = {};                                       // of the captured sequence, for tod_orb_stages
+  uint32_t want_max = 0, sel_fs = 0;
   ~OrbWs() override {                                      // the captured graph goes before the buffers it refers to
     if (graph_exec) (void)hipGraphExecDestroy(graph_exec);
     if (graph) (void)hipGraphDestroy(graph);
@@ -564,6 +536,7 @@ int orb_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uin
         T.want[lvl] = (h <= 2u * kEdge || w <= 2u * kEdge) ? 0u : per_level[lvl];     // too small: the level count stays 0
         want_max = std::max(want_max, T.want[lvl]);
       }
+      ws->tab = T; ws->want_max = want_max; ws->sel_fs = sel2_cap;
       if (want_max > 0) {
         const uint32_t Vg = (uint32_t)V;
         hipLaunchKernelGGL(fast_nms_kernel, dim3((W + kNmsTileW - 1) / kNmsTileW, (H + kNmsTileH - 1) / kNmsTileH, Vg), dim3(256), 0, st,
@@ -618,6 +591,24 @@ int tod_orb_device(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask
                    float* d_kp_aux, uint8_t* d_desc, uint32_t cap, uint32_t* n_out) {
   return orb_device(ctx, d_gray, 0, d_mask, 1, H, W, stride, n_features, n_levels, scale_factor, pattern, d_kp_xy, d_kp_aux, d_desc,
                     cap, n_out);
+}
+
+// used by orb_learn.hip (orb_stages.h): one frame through the detection stages, and where they left their results
+int tod_orb_stages(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask, uint32_t H, uint32_t W, uint32_t stride,
+                   uint32_t n_features, uint32_t n_levels, float scale_factor, Stages* out) {
+  OrbWs* ws = tod_ws<OrbWs>(ctx);
+  TOD_HIP(ws->kp_xy.reserve((size_t)n_features * 8)); TOD_HIP(ws->kp_aux.reserve((size_t)n_features * 16));
+  TOD_HIP(ws->desc.reserve((size_t)n_features * 32));
+  uint32_t n = 0;
+  const int rc = orb_device(ctx, d_gray, 0, d_mask, 1, H, W, stride, n_features, n_levels, scale_factor, nullptr, ws->kp_xy.as<float>(),
+                            ws->kp_aux.as<float>(), ws->desc.as<uint8_t>(), n_features, &n);
+  if (rc != TODHIP_OK) return rc;
+  out->T = ws->tab;
+  out->blur = ws->blur.as<uint8_t>(); out->sel = ws->sel2.as<Cand>();
+  out->level_counts = ws->small.as<uint32_t>() + (size_t)n_levels * kCtlWords + 8;   // F == 1: the frame's row behind the levels' rows
+  out->fs = (size_t)H * W; out->sel_fs = ws->sel_fs; out->want_max = ws->want_max; out->n = n;
+  disc_umax(out->umax);
+  return TODHIP_OK;
 }
 
 extern "C" {

@@ -133,6 +133,8 @@ struct todhip_pipeline {
   std::vector<float> spans;
   uint32_t n_objs = 0;
   todhip_rng rng0;
+  int8_t pattern[1024] = {};             // todhip_pipeline_set_pattern: written only while every slot is free
+  bool has_pattern = false;
 
   std::mutex mu;                         // slot states, tickets, stats, dead, stop
   std::condition_variable cv;
@@ -190,8 +192,8 @@ int todhip_pipeline::orb_step(Slot* s, uint32_t w) {
     if (rc != TODHIP_OK) return rc;
     gray = s->gray.p;
   }
-  return todhip_orb_batch_device(octx[w], gray, n, px, prm.H, prm.W, prm.W, prm.n_features, prm.n_levels, prm.scale_factor, nullptr,
-                                 s->kp.p, s->aux.p, s->desc.p, nq, s->n_kp);
+  return todhip_orb_batch_device(octx[w], gray, n, px, prm.H, prm.W, prm.W, prm.n_features, prm.n_levels, prm.scale_factor,
+                                 has_pattern ? pattern : nullptr, s->kp.p, s->aux.p, s->desc.p, nq, s->n_kp);
 }
 
 int todhip_pipeline::match_step(Slot* s) {
@@ -449,6 +451,17 @@ int todhip_pipeline_db_load(todhip_pipeline* p, const todhip_object* objs, uint3
 }
 int todhip_pipeline_db_load_device(todhip_pipeline* p, const todhip_object* objs, uint32_t n_objs, uint32_t desc_bytes) {
   return p ? p->db_load(objs, n_objs, desc_bytes, true) : TODHIP_EINVAL;
+}
+
+int todhip_pipeline_set_pattern(todhip_pipeline* p, const int8_t* pattern) {
+  if (!p) return TODHIP_EINVAL;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->dead) return TODHIP_EHIP;
+  for (const Slot& s : p->slots)
+    if (s.state != kFree) return TODHIP_EBUSY;
+  p->has_pattern = pattern != nullptr;
+  if (pattern) std::memcpy(p->pattern, pattern, sizeof(p->pattern));
+  return TODHIP_OK;
 }
 
 int todhip_pipeline_submit(todhip_pipeline* p, const uint8_t* frames, const void* depth, uint32_t n_frames, uint64_t* ticket) {
