@@ -2,12 +2,15 @@
 //
 //   g++ -std=c++17 -Iinclude examples/pipeline_host.cpp -Ltod_amd -ltodhip -Wl,-rpath,$PWD/tod_amd -o pipeline_host
 //   GPU_MAX_HW_QUEUES=8 ./pipeline_host            ("Streams and hardware queues")
+//   GPU_MAX_HW_QUEUES=8 ./pipeline_host --objects 3,1   look for objects 3 and 1 only (the reference detector's json_object_ids)
 //
 // It creates a pipeline, loads an object DB from plain arrays, keeps ring_depth batches in flight -- it submits ahead and waits for
 // the oldest ticket only when the ring is full -- and prints the poses. The frames here are noise and the DB is random, so it prints
 // no pose; a real host puts its camera frames and its trained models (todhip_model_*, or rows read from its database) in their place.
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <random>
 #include <vector>
@@ -42,7 +45,21 @@ int drain(todhip_pipeline* pipe, uint64_t ticket, uint32_t n_frames, uint32_t n_
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  // --objects a,b,c: indices into the objs[] loaded below; without it every object is searched
+  std::vector<uint32_t> wanted;
+  bool restrict_objects = false;
+  for (int a = 1; a < argc; ++a) {
+    if (std::strcmp(argv[a], "--objects") != 0 || a + 1 >= argc) { std::fprintf(stderr, "usage: %s [--objects 3,17,42]\n", argv[0]); return 2; }
+    restrict_objects = true;
+    for (const char* p = argv[++a]; *p;) {
+      char* end = nullptr;
+      wanted.push_back((uint32_t)std::strtoul(p, &end, 10));
+      if (end == p) { std::fprintf(stderr, "--objects: a comma-separated list of object indices\n"); return 2; }
+      p = *end == ',' ? end + 1 : end;
+    }
+  }
+
   todhip_pipeline_params prm;
   todhip_pipeline_default_params(&prm);                 // struct_size and the defaults; then what this host knows
   prm.frames_per_step = 8;
@@ -69,6 +86,14 @@ int main() {
   }
   rc = todhip_pipeline_db_load(pipe, objs.data(), n_objs, 32);
   if (rc != TODHIP_OK) { std::fprintf(stderr, "todhip_pipeline_db_load: todhip_status %d\n", rc); todhip_pipeline_destroy(pipe); return 1; }
+
+  if (restrict_objects) {                                // between steps only: TODHIP_EBUSY while a ticket is outstanding
+    rc = todhip_pipeline_select_objects(pipe, wanted.data(), (uint32_t)wanted.size());
+    if (rc != TODHIP_OK) { std::fprintf(stderr, "todhip_pipeline_select_objects: todhip_status %d\n", rc); todhip_pipeline_destroy(pipe); return 1; }
+    uint32_t n_sel = 0; uint64_t sel_rows = 0;
+    todhip_db_selection(todhip_pipeline_matcher(pipe), &n_sel, &sel_rows, nullptr);
+    std::printf("searching %u of %u objects, %llu rows\n", n_sel, n_objs, (unsigned long long)sel_rows);
+  }
 
   const uint32_t B = prm.frames_per_step, n_batches = 6;
   const size_t px = (size_t)prm.H * prm.W;

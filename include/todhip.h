@@ -120,6 +120,26 @@ int todhip_db_load_device(todhip_ctx*, const todhip_object* objs, uint32_t n_obj
 int todhip_db_info(const todhip_ctx*, uint64_t* total_rows, uint64_t* shard_first_row, uint64_t* shard_rows,
                    uint32_t* n_objs);
 
+/* Restrict every later match on this context to the rows of the listed objects (indices into the objs[] of the last
+ * todhip_db_load[_device]); ids == NULL: all objects again (the state after a load). The list may be in any order and may
+ * repeat an index; an index >= n_objs: TODHIP_EINVAL and the previous selection stays. n_ids == 0 with ids != NULL selects
+ * nothing: every query then comes back with count 0. A new todhip_db_load[_device] resets the selection to all.
+ * The reference's detector is told which objects to find (json_object_ids, detector.py:53-60, conf/detection.ork:22) and
+ * DescriptorMatcher::parameter_callback builds its matcher from those alone. Definition: with S the ascending list of the distinct
+ * selected indices, todhip_match, todhip_match_device, todhip_match_shard_device and todhip_merge_shards_device[_on] return what a
+ * context loaded with only objs[S[0]], objs[S[1]], ... (same shard arguments) would return, except that imgIdx is S[imgIdx'], the
+ * index in the full DB, and the u64 keys of the sharded form carry rows of the full DB -- so ranks that hold different parts of S
+ * merge as before. The ratio test sees the two nearest SELECTED rows, the LSH mode indexes the selected rows, a bit order
+ * (todhip_set_db_bit_order) stays the one the load computed. Spans, todhip_db_info, the model points and the verifier's
+ * span-by-object-index input do not change. The selected rows of this context's shard are copied into a second buffer (32 bytes per
+ * row beside the full DB; none while all objects are selected).
+ * desc_bytes == 32 only: on a float DB (desc_bytes == 512) TODHIP_EINVAL. Without a DB TODHIP_ENODB. Synchronizes the context's
+ * stream, as todhip_db_load does; after TODHIP_EHIP all objects are selected. */
+int todhip_db_select_objects(todhip_ctx*, const uint32_t* ids, uint32_t n_ids);
+/* what is selected now: number of distinct selected objects, their rows in the whole DB and in this context's shard (any pointer
+ * may be NULL) */
+int todhip_db_selection(const todhip_ctx*, uint32_t* n_selected_objs, uint64_t* selected_rows, uint64_t* selected_shard_rows);
+
 /* Replaces DescriptorMatcher::process (DescriptorMatcher.cpp:195-252): exact Hamming k-NN (decision D1,
  * instead of FLANN-LSH knnMatch(k=5) at :211), radius truncation (:212-220; radius is the reference's
  * `unsigned int radius_`, 0 is rejected because the reference then indexes an empty vector at :237) and
@@ -409,6 +429,9 @@ int  todhip_pipeline_get_stats(todhip_pipeline*, todhip_pipeline_stats* out);
  * pattern learned by todhip_pattern_learn_* reaches the batched path. The DB must hold descriptors of the same pattern.
  * TODHIP_EBUSY while a ticket is outstanding. */
 int  todhip_pipeline_set_pattern(todhip_pipeline*, const int8_t* pattern /* 256 x 4; NULL = built-in */);
+/* todhip_db_select_objects on the pipeline's matcher context, from the next submit on; the verifier workers keep the spans of every
+ * object (poses name objects of the full DB). TODHIP_EBUSY while a ticket is outstanding. */
+int  todhip_pipeline_select_objects(todhip_pipeline*, const uint32_t* ids, uint32_t n_ids);
 /* One device-resident BGR8 / BGRA8 image (channels 3 | 4, row stride src_stride bytes) -> gray (row stride gray_stride bytes), the
  * conversion the pipeline runs in front of ORB: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14, what adapter/ecto_cells.hpp computes on
  * the host. Asynchronous on the context's stream. */

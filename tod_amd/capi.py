@@ -91,6 +91,7 @@ EXPORTS = [
     "todhip_pipeline_wait", "todhip_pipeline_get_stats", "todhip_bgr_to_gray_device",
     "todhip_pattern_learn_begin", "todhip_pattern_learn_add_view", "todhip_pattern_learn_add_view_device", "todhip_pattern_learn_finish",
     "todhip_pattern_learn_responses", "todhip_pattern_learn_free", "todhip_pipeline_set_pattern",
+    "todhip_db_select_objects", "todhip_db_selection", "todhip_pipeline_select_objects",
 ]
 
 _lib = None
@@ -124,6 +125,10 @@ def lib():
         L.todhip_pipeline_matcher.restype = C.c_void_p
         L.todhip_set_db_bit_order.argtypes, L.todhip_set_db_bit_order.restype = [C.c_void_p, C.c_int], C.c_int
         L.todhip_db_bit_order.argtypes, L.todhip_db_bit_order.restype = [C.c_void_p, C.c_void_p], C.c_int
+        if hasattr(L, "todhip_db_select_objects"):                    # (TODHIP_LIB_PATH may name a build from before the selection)
+            L.todhip_db_select_objects.argtypes, L.todhip_db_select_objects.restype = [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int
+            L.todhip_db_selection.argtypes, L.todhip_db_selection.restype = [C.c_void_p] * 4, C.c_int
+            L.todhip_pipeline_select_objects.argtypes, L.todhip_pipeline_select_objects.restype = [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int
         _lib = L
     return _lib
 
@@ -141,6 +146,16 @@ def _check(rc, what):
 
 def _np_ptr(a):
     return C.c_void_p(a.ctypes.data)
+
+
+def _ids_in(ids):
+    """(pointer, count, array to keep alive) of an object-index list for the select_objects calls; None -> (NULL, 0): all objects.
+    An empty list is a real, non-null pointer: it selects nothing."""
+    if ids is None:
+        return None, 0, None
+    a = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    keep = a if a.size else np.zeros(1, np.uint32)
+    return _np_ptr(keep), int(a.size), keep
 
 
 def _k9(K):
@@ -276,6 +291,18 @@ class Context:
         _check(lib().todhip_db_info(self._h, C.byref(tot), C.byref(first), C.byref(rows), C.byref(nobj)),
                "todhip_db_info")
         return dict(total_rows=tot.value, shard_first=first.value, shard_rows=rows.value, n_objs=nobj.value)
+
+    def select_objects(self, ids):
+        """Search only the rows of the listed objects (indices of the last db_load, any order, repeats allowed) from now on; None:
+        all objects again, []: nothing. imgIdx and the sharded keys keep the numbering of the full DB (todhip_db_select_objects)."""
+        p, n, keep = _ids_in(ids)
+        _check(lib().todhip_db_select_objects(self._h, p, C.c_uint32(n)), "todhip_db_select_objects")
+
+    def selection(self):
+        """dict(n_objs, rows, shard_rows): the distinct selected objects, their rows in the whole DB and in this context's shard"""
+        n, rows, srows = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(lib().todhip_db_selection(self._h, C.byref(n), C.byref(rows), C.byref(srows)), "todhip_db_selection")
+        return dict(n_objs=n.value, rows=rows.value, shard_rows=srows.value)
 
     def _match_host(self, fn, what, q, k, radius):
         nq = q.shape[0]
@@ -705,6 +732,12 @@ class Pipeline:
         pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
         assert pat is None or pat.size == 1024
         return lib().todhip_pipeline_set_pattern(self._h, None if pat is None else _np_ptr(pat))
+
+    def select_objects(self, ids):
+        """Context.select_objects on the pipeline's matcher, from the next submit on; returns the status (EBUSY while a ticket is
+        outstanding)."""
+        p, n, keep = _ids_in(ids)
+        return lib().todhip_pipeline_select_objects(self._h, p, C.c_uint32(n))
 
     def submit(self, frames, depth, n_frames=None):
         """Host form: frames u8 [n, H, W(, 3 | 4)], depth f32 | u16 [n, H, W] as numpy arrays. Returns (status, ticket)."""

@@ -194,6 +194,7 @@ static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_o
   // 32: 256-bit binary descriptors (ORB), Hamming; 512: 128 x f32 (SIFT-like), L2 -- one device only
   if (desc_bytes != 32 && !(desc_bytes == 512 && shard_count == 1)) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
+  tod_view_reset(ctx);                                      // todhip_db_select_objects: a load selects all objects
   ctx->h_obj_off.assign(n_objs + 1, 0u);
   uint64_t total = 0;
   for (uint32_t o = 0; o < n_objs; ++o) {

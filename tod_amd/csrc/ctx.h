@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/todhip.h"
+#include "db_select.h"
 #include "match_split.h"
 
 #define TOD_HIP(call)                                  \
@@ -136,6 +137,12 @@ struct todhip_ctx {
   bool bit_order_on = false;
   uint8_t bit_src_of[256];
   DevBuf bit_tab, m_qord;
+  // todhip_db_select_objects (db_select.hip): while sel_on, every Hamming search runs over view_desc -- the shard's rows of the selected
+  // objects, compacted in ascending object order, kDbSlackBytes of zeros behind them as behind db_desc -- and its keys go through
+  // view_tab (sel.seg_view, then sel.seg_global) back to rows of the full DB. Off (all objects): sel is empty, both buffers are unused.
+  bool sel_on = false;
+  TodViewTables sel;
+  DevBuf view_desc, view_tab;
 
   std::vector<todhip_round_trace> traces;
 
@@ -143,6 +150,12 @@ struct todhip_ctx {
 
   todhip_ctx() { for (int p = 0; p < 256; ++p) bit_src_of[p] = (uint8_t)p; }
 };
+
+// What the Hamming searches read: the active view, or the whole shard exactly as before while all objects are selected. Keys of a view
+// are built on first row 0 and mapped by tod_view_remap.
+inline const void* tod_db_rows(const todhip_ctx* ctx) { return ctx->sel_on ? ctx->view_desc.p : ctx->db_desc.p; }
+inline uint64_t tod_db_n_rows(const todhip_ctx* ctx) { return ctx->sel_on ? ctx->sel.view_rows() : ctx->shard_rows; }
+inline uint64_t tod_db_first_row(const todhip_ctx* ctx) { return ctx->sel_on ? 0ull : ctx->shard_first; }
 
 template <typename T> T* tod_ws(todhip_ctx* ctx) {
   std::unique_ptr<TodWs>& s = ctx->ws[T::kSlot];
@@ -188,6 +201,9 @@ int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy
 // the rows' arrival and the LSH index; _queries: nq query rows in the resident order (only while ctx->bit_order_on)
 int tod_bit_order_load(todhip_ctx* ctx);
 int tod_bit_order_queries(todhip_ctx* ctx, const void* d_q, uint32_t nq, const void** d_out);
+// db_select.hip: back to all objects (todhip_db_load); n keys (distance << 32 | view row, or ~0) -> (distance << 32 | global row)
+void tod_view_reset(todhip_ctx* ctx);
+int tod_view_remap(todhip_ctx* ctx, uint64_t* d_keys, size_t n);
 // lsh.hip: the optional LSH-approximate mode (todhip_set_lsh)
 bool tod_lsh_enabled(const todhip_ctx* ctx);
 int tod_lsh_build(todhip_ctx* ctx);

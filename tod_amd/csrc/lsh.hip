@@ -30,7 +30,7 @@ struct LshWs : TodWs {
   static constexpr int kSlot = kWsLsh;
   uint32_t n_tables = 0, key_size = 0, level = 0;
   uint32_t n_masks = 0;
-  uint64_t built_rows = ~0ull;          // shard_rows the index was built for (~0: not built)
+  uint64_t built_rows = ~0ull;          // active rows the index was built for (~0: not built)
   DevBuf pos, masks, off, rows, cursor, scan_tmp;
 };
 
@@ -153,9 +153,9 @@ __global__ __launch_bounds__(256) void lsh_query_kernel(const uint8_t* __restric
 
 template <uint32_t K>
 int launch_query(todhip_ctx* ctx, LshWs* ws, const void* d_q, uint32_t nq, uint64_t* d_lists) {
-  hipLaunchKernelGGL((lsh_query_kernel<K>), dim3((nq + 3u) / 4u), dim3(256), 0, ctx->stream, ctx->db_desc.as<uint8_t>(), ctx->shard_first,
-                     reinterpret_cast<const uint8_t*>(d_q), nq, ws->pos.as<uint8_t>(), ws->n_tables, ws->key_size, ws->masks.as<uint32_t>(),
-                     ws->n_masks, ws->off.as<uint32_t>(), ws->rows.as<uint32_t>(), (uint32_t)ctx->shard_rows, d_lists);
+  hipLaunchKernelGGL((lsh_query_kernel<K>), dim3((nq + 3u) / 4u), dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t*>(tod_db_rows(ctx)),
+                     tod_db_first_row(ctx), reinterpret_cast<const uint8_t*>(d_q), nq, ws->pos.as<uint8_t>(), ws->n_tables, ws->key_size, ws->masks.as<uint32_t>(),
+                     ws->n_masks, ws->off.as<uint32_t>(), ws->rows.as<uint32_t>(), (uint32_t)tod_db_n_rows(ctx), d_lists);
   TOD_HIP(hipGetLastError());
   return TODHIP_OK;
 }
@@ -167,14 +167,16 @@ bool tod_lsh_enabled(const todhip_ctx* ctx) {
   return ws && ws->n_tables > 0;
 }
 
-// (re)build the index over the shard's rows resident in ctx->db_desc; called by todhip_db_load and todhip_set_lsh
+// (re)build the index over the active rows (tod_db_rows: the shard's, or the view of the selected objects); called by todhip_db_load,
+// todhip_db_select_objects and todhip_set_lsh
 int tod_lsh_build(todhip_ctx* ctx) {
   LshWs* ws = tod_ws<LshWs>(ctx);
   ws->built_rows = ~0ull;
-  if (ws->n_tables == 0 || ctx->desc_bytes != 32 || ctx->shard_rows == 0) return TODHIP_OK;
-  if (ctx->shard_rows > 0xFFFFFFFFull) return TODHIP_EINVAL;
+  if (ws->n_tables == 0 || ctx->desc_bytes != 32 || tod_db_n_rows(ctx) == 0) return TODHIP_OK;
+  if (tod_db_n_rows(ctx) > 0xFFFFFFFFull) return TODHIP_EINVAL;
   hipStream_t st = ctx->stream;
-  const uint32_t n = (uint32_t)ctx->shard_rows, T = ws->n_tables, ks = ws->key_size;
+  const uint8_t* const db = reinterpret_cast<const uint8_t*>(tod_db_rows(ctx));
+  const uint32_t n = (uint32_t)tod_db_n_rows(ctx), T = ws->n_tables, ks = ws->key_size;
   const size_t stride = ((size_t)1 << ks) + 1;
   std::vector<uint8_t> pos((size_t)T * ks);
   for (uint32_t t = 0; t < T; ++t) key_bits(t, ks, &pos[(size_t)t * ks]);
@@ -201,7 +203,7 @@ int tod_lsh_build(todhip_ctx* ctx) {
   TOD_HIP(hipMemcpyAsync(ws->masks.p, masks.data(), masks.size() * 4, hipMemcpyHostToDevice, st));
   TOD_HIP(hipMemsetAsync(ws->off.p, 0, T * stride * 4, st));
   TOD_HIP(hipStreamSynchronize(st));                                   // pos / masks leave scope below
-  hipLaunchKernelGGL(lsh_count_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, ctx->db_desc.as<uint8_t>(), n, ws->pos.as<uint8_t>(), T, ks,
+  hipLaunchKernelGGL(lsh_count_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, db, n, ws->pos.as<uint8_t>(), T, ks,
                      ws->off.as<uint32_t>());
   size_t tmp_bytes = 0;
   if (hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, ws->off.as<uint32_t>(), ws->off.as<uint32_t>(), (int)stride, st) != hipSuccess) return TODHIP_EHIP;
@@ -210,18 +212,18 @@ int tod_lsh_build(todhip_ctx* ctx) {
     uint32_t* off_t = ws->off.as<uint32_t>() + t * stride;
     TOD_HIP(hipcub::DeviceScan::InclusiveSum(ws->scan_tmp.p, tmp_bytes, off_t, off_t, (int)stride, st));
     TOD_HIP(hipMemsetAsync(ws->cursor.p, 0, stride * 4, st));
-    hipLaunchKernelGGL(lsh_scatter_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, ctx->db_desc.as<uint8_t>(), n,
+    hipLaunchKernelGGL(lsh_scatter_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, db, n,
                        ws->pos.as<uint8_t>() + (size_t)t * ks, ks, off_t, ws->cursor.as<uint32_t>(), ws->rows.as<uint32_t>() + (size_t)t * n);
   }
   TOD_HIP(hipGetLastError());
-  ws->built_rows = ctx->shard_rows;
+  ws->built_rows = tod_db_n_rows(ctx);
   return TODHIP_OK;
 }
 
 // one list of k keys per query, the format of tod_match_lists
 int tod_lsh_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint64_t* d_lists, uint32_t* n_lists) {
   LshWs* ws = tod_ws<LshWs>(ctx);
-  if (ws->built_rows != ctx->shard_rows) return TODHIP_EINVAL;
+  if (ws->built_rows != tod_db_n_rows(ctx)) return TODHIP_EINVAL;
   *n_lists = 1;
   switch (k) {
     case 1: return launch_query<1>(ctx, ws, d_q, nq, d_lists);

@@ -50,7 +50,7 @@ int k4_engine(const todhip_ctx* ctx, uint32_t nq) {
   // repo's ORB descriptors; 1000 x 1M 0.25 | 0.085; 1000 x 100k 0.035 | 0.021; 500 x 5000 0.008 | 0.013. The matrix form
   // pays from ~2^24 pairs on; below, a wave's fixed start-up costs more than it saves. (Few queries over a big DB are
   // matrix-engine work too: both engines pad to 64 query columns, and 8 MFMAs per KB of rows keep up with HBM.)
-  return (uint64_t)nq * ctx->shard_rows >= (1ull << 24) ? 1 : 0;
+  return (uint64_t)nq * tod_db_n_rows(ctx) >= (1ull << 24) ? 1 : 0;
 }
 
 }  // namespace
@@ -81,14 +81,9 @@ int tod_timing_end(todhip_ctx* ctx, int slot) {
   return TODHIP_OK;
 }
 
-// Per-query candidate lists of this shard: d_lists[n_lists][nq][k] (each ascending). n_lists <= kMergeGroups.
-int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
-                    uint32_t* n_lists) {
-  if (ctx->desc_bytes != 32) return TODHIP_EINVAL;
-  if (ctx->bit_order_on) {                 // todhip_set_db_bit_order: the rows are stored in another bit order, the queries follow them
-    int rc = tod_bit_order_queries(ctx, d_q, nq, &d_q);
-    if (rc != TODHIP_OK) return rc;
-  }
+// the search over the active rows (tod_db_rows): d_q is already in the resident bit order
+static int match_lists_active(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
+                              uint32_t* n_lists) {
   if (tod_lsh_enabled(ctx)) return tod_lsh_lists(ctx, d_q, nq, k, d_lists, n_lists);   // todhip_set_lsh: candidates from the index only
   if (ctx->ratio > 0.f) radius = 256u;   // the ratio test needs the true second neighbour, however far: no radius bound in the search
   const uint32_t* q = reinterpret_cast<const uint32_t*>(d_q);
@@ -105,11 +100,33 @@ int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, u
   }
 }
 
+// Per-query candidate lists of this shard: d_lists[n_lists][nq][k] (each ascending). n_lists <= kMergeGroups.
+int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
+                    uint32_t* n_lists) {
+  if (ctx->desc_bytes != 32) return TODHIP_EINVAL;
+  if (ctx->bit_order_on) {                 // todhip_set_db_bit_order: the rows are stored in another bit order, the queries follow them
+    int rc = tod_bit_order_queries(ctx, d_q, nq, &d_q);
+    if (rc != TODHIP_OK) return rc;
+  }
+  if (!ctx->sel_on) return match_lists_active(ctx, d_q, nq, k, radius, d_lists, n_lists);
+  // todhip_db_select_objects: the same search over the view. No selected row in this shard: no DB pass, one list of padding keys
+  // (what an empty shard contributes, tod_match_shard_keys); otherwise the lists' view rows become rows of the full DB.
+  if (k == 0 || k > 8) return TODHIP_EINVAL;
+  if (tod_db_n_rows(ctx) == 0) {
+    TOD_HIP(hipMemsetAsync(d_lists, 0xFF, (size_t)nq * k * sizeof(uint64_t), ctx->stream));
+    *n_lists = 1;
+    return TODHIP_OK;
+  }
+  int rc = match_lists_active(ctx, d_q, nq, k, radius, d_lists, n_lists);
+  if (rc != TODHIP_OK) return rc;
+  return tod_view_remap(ctx, d_lists, (size_t)*n_lists * nq * k);
+}
+
 size_t tod_match_lists_bytes(uint32_t nq, uint32_t k) { return (size_t)kMergeGroups * nq * k * sizeof(uint64_t); }
 
 int tod_match_shard_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_keys) {
   if (nq == 0) return TODHIP_OK;
-  if (ctx->shard_rows == 0) {   // an empty shard contributes only padding keys
+  if (tod_db_n_rows(ctx) == 0) {   // an empty shard (or one without a selected row) contributes only padding keys
     TOD_HIP(hipMemsetAsync(d_keys, 0xFF, (size_t)nq * k * sizeof(uint64_t), ctx->stream));
     return TODHIP_OK;
   }

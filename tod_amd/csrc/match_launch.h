@@ -74,10 +74,10 @@ int launch_merge(todhip_ctx* ctx, uint32_t nq, uint32_t nq_pad, const Tiling& t,
                  const uint32_t* d_stats, uint64_t* d_lists, uint32_t* n_lists) {
   if (wave)
     hipLaunchKernelGGL(merge_tiles_wave_kernel<K>, dim3((nq + kWavesPerBlock - 1) / kWavesPerBlock, t.groups), dim3(kBlock), 0, ctx->stream,
-                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, ctx->shard_first, t.groups, d_stored, n_qw64, d_lists);
+                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, tod_db_first_row(ctx), t.groups, d_stored, n_qw64, d_lists);
   else
     hipLaunchKernelGGL(merge_tiles_kernel<K>, dim3((nq + kBlock - 1) / kBlock, t.groups), dim3(kBlock), 0, ctx->stream,
-                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, ctx->shard_first, t.groups, d_stored, n_qw64, d_lists,
+                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, tod_db_first_row(ctx), t.groups, d_stored, n_qw64, d_lists,
                        d_stats, d_stats ? ctx->k4x_stats_host.as<uint32_t>() : (uint32_t*)nullptr, d_stats ? ctx->k4x.seq_sent : 0u);
   TOD_HIP(hipGetLastError());
   *n_lists = t.groups;
@@ -89,7 +89,7 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
   constexpr bool PF2 = QT < 8;                                        // register budget: see hamming_topk_mfma
   const MatchEnv& env = match_env();
   const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu >> kLocalBits : radius + 1u;   // distances are <= 256: no cut beyond that
-  const uint32_t n_rows = (uint32_t)ctx->shard_rows;
+  const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
   const uint32_t n_qw = (nq + 32u * QT - 1u) / (32u * QT), n_qw64 = (nq + 63u) / 64u;
   const uint32_t nq_pad = n_qw64 * 64u;
   // Rounds of waves: the chip holds 8 of these waves per CU (2 per SIMD, by registers). A launch whose wave count is just
@@ -136,7 +136,7 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
   ctx->counters.last_block_split = split;
   uint32_t* const d_stats = split < 4 ? ctx->k4x_stats_dev.as<uint32_t>() : nullptr;
   hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream,
-                     ctx->db_desc.as<uint32_t>(), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw, n_qw64,
+                     reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw, n_qw64,
                      t.blocks_per_xcd, t.tiles_per_xcd, cut, (uint32_t)std::max(2, env.k4x_share), ctx->m_part.as<uint32_t>(),
                      ctx->m_bound.as<uint32_t>(), d_stored, d_stats ? d_stats + 2u * (split - 2u) : nullptr);
   if (int rc = timer.end()) return rc;
@@ -147,7 +147,7 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
 template <int K>
 int launch_topk_mfma_q32(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
   const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu >> kLocalBits : radius + 1u;
-  const uint32_t n_rows = (uint32_t)ctx->shard_rows, n_qw64 = 1u, nq_pad = 64u;
+  const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx), n_qw64 = 1u, nq_pad = 64u;
   // one wave per tile; about 32 waves per CU in all (each holds four 1 KB loads in flight), tiles of >= 2048 rows
   uint32_t n_tiles = std::max(1u, std::min<uint32_t>((uint32_t)ctx->n_cu * 32u, n_rows / 2048u));
   n_tiles = std::min(n_tiles, 8192u);
@@ -159,7 +159,7 @@ int launch_topk_mfma_q32(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint
   if (int rc = timer.begin()) return rc;
   auto kern = cut <= 128u ? hamming_topk_mfma_q32<K, true> : hamming_topk_mfma_q32<K, false>;
   hipLaunchKernelGGL(kern, dim3((t.n_tiles + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, ctx->stream,
-                     ctx->db_desc.as<uint32_t>(), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw64, cut,
+                     reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw64, cut,
                      (uint32_t)std::max(4, match_env().k4x_share), ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
   if (int rc = timer.end()) return rc;
   return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, true, nullptr, d_lists, n_lists);
@@ -200,7 +200,7 @@ int launch_topk(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radi
   if (k4_engine(ctx, nq) == 1) return launch_topk_mfma<K>(ctx, d_q, nq, radius, d_lists, n_lists);
   const MatchEnv& env = match_env();
   const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu : radius + 1u;   // distances are <= 256: no cut beyond that
-  const uint32_t n_rows = (uint32_t)ctx->shard_rows;
+  const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
   const uint32_t n_qw = (nq + 63u) / 64u;
   const uint32_t nq_pad = n_qw * 64u;
   // Tiling (measured, tools/time_k4.py): about three times more waves than fit the chip at once and tiles of at most
@@ -232,7 +232,7 @@ int launch_topk(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radi
   auto kern = mode == 2 ? hamming_topk_tiles<K, 2>
                         : (mode == 1 ? hamming_topk_tiles<K, 1> : (mode == 3 ? hamming_topk_tiles<K, 3> : hamming_topk_tiles<K, 0>));
   hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream,
-                     ctx->db_desc.as<uint32_t>(), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw,
+                     reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw,
                      t.blocks_per_xcd, t.tiles_per_xcd, cut, ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
   if (int rc = timer.end()) return rc;
   return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw, false, nullptr, d_lists, n_lists);

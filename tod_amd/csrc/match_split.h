@@ -19,6 +19,10 @@ struct K4xSplit {
   uint32_t split = 2, hold = 0, hold_len = 32;   // level in use; launches left before the next probe; the hold after that probe
   uint32_t last[4] = {0, 0, 0, 0};       // the cumulative counts already accounted for
 
+  // the data the launches see has changed (todhip_db_select_objects): start over at the lowest level. The report counters stay: the
+  // device's totals are cumulative.
+  void restart() { split = 2; hold = 0; hold_len = 32; }
+
   int mode(int process_default) const { return force >= 0 ? force : process_default; }
   // false: whole blocks, and neither method below is needed. min_split: the lowest split the thresholds allow (4: none)
   bool may_split(uint32_t min_split, int process_default) const { return mode(process_default) != 0 && min_split != 4u; }

@@ -464,6 +464,18 @@ int todhip_pipeline_set_pattern(todhip_pipeline* p, const int8_t* pattern) {
   return TODHIP_OK;
 }
 
+int todhip_pipeline_select_objects(todhip_pipeline* p, const uint32_t* ids, uint32_t n_ids) {
+  if (!p) return TODHIP_EINVAL;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->dead) return TODHIP_EHIP;
+  for (const Slot& s : p->slots)
+    if (s.state != kFree) return TODHIP_EBUSY;
+  std::lock_guard<std::mutex> g(p->mctx_mu);
+  const int rc = todhip_db_select_objects(p->mctx, ids, n_ids);
+  if (rc == TODHIP_EHIP) p->dead = true;
+  return rc;
+}
+
 int todhip_pipeline_submit(todhip_pipeline* p, const uint8_t* frames, const void* depth, uint32_t n_frames, uint64_t* ticket) {
   return p ? p->submit(frames, depth, n_frames, ticket, true) : TODHIP_EINVAL;
 }

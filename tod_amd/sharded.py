@@ -61,6 +61,7 @@ class ShardedMatcher:
          ops.all_gather(out, inp);      ops.all_to_all(out, inp)        (flat views, equal splits)
          ops.match_shard(q_all, n, keys_out)          this rank's shard against n queries, on ops.compute
          ops.merge(keys_mine, n_shards, n, out, stream)   merge + radius cut + gather into `out`, on `stream`
+         ops.select_objects(ids)                      this rank's shard searches only those objects from now on (None: all)
 
        begin(n_steps, q_of): q_of(i) -> (this rank's descriptors of step i as a [B, Q, desc_bytes] tensor, event or None
        after which they are complete). step(i, out) issues step i and returns the stream on which `out` becomes complete.
@@ -86,6 +87,12 @@ class ShardedMatcher:
         self.ev_gathered, self.ev_exchanged = {}, {}
         if self.overlap and n_steps > 0:
             self._gather(0)
+
+    def select_objects(self, ids):
+        """Search only the listed objects of the DB (indices of the full DB, any order; None: all again) from the next step on.
+        Every rank calls it with the same list between two steps; each restricts its own shard, the candidate keys keep rows of the
+        full DB, so the exchange and the merge do not change (todhip_db_select_objects)."""
+        self.ops.select_objects(None if ids is None else [int(i) for i in ids])
 
     def _gather(self, i):
         ops = self.ops
@@ -190,18 +197,22 @@ class GpuOps:
         else:       # the merge only reads the context's immutable tables: it may run beside the next DB pass
             self.ctx.merge_shards_device_on(stream.cuda_stream, *args)
 
+    def select_objects(self, ids):
+        self.compute.synchronize()                      # the context's calls are issued on this stream
+        self.ctx.select_objects(ids)
+
 
 class HostOps:
     """ShardedMatcher backend without a GPU (tests/test_sharded_cpu.py): CPU tensors, gloo collectives, one synchronous
     "stream" per name so that the overlapped choreography (buffer rotation, issue order) runs exactly as on the GPU; the
     two compute calls are injected."""
 
-    def __init__(self, dist, match_shard, merge, two_streams=True):
+    def __init__(self, dist, match_shard, merge, two_streams=True, select_objects=None):
         import torch
         self.torch, self.dist = torch, dist
         self.compute = "compute"
         self.comm = "comm" if two_streams else self.compute
-        self._match_shard, self._merge = match_shard, merge
+        self._match_shard, self._merge, self._select = match_shard, merge, select_objects
         self.log = []                                   # (what, stream) in issue order: the tests check it is rank independent
 
     def alloc(self, shape, dtype_name):
@@ -229,3 +240,7 @@ class HostOps:
 
     def merge(self, keys_mine, n_shards, n, out, stream):
         out["result"] = self._merge(keys_mine.clone())
+
+    def select_objects(self, ids):
+        self.log.append("select_objects")
+        self._select(ids)
