@@ -6,8 +6,10 @@
     todhip_orb -> todhip_match -> todhip_verify                           <- detector.py: features -> matcher -> guess generator
 
 Synthetic data (a textured plane rendered at a known pose), so that the recovered pose can be checked.
-Run on a machine with an MI355X:  python examples/train_and_detect.py [--learn-pattern]
+Run on a machine with an MI355X:  python examples/train_and_detect.py [--learn-pattern] [--compact DIST,HAM]
 --learn-pattern: first learn an rBRIEF test pattern from the training view (todhip_pattern_learn_*), then train and detect with it.
+--compact DIST,HAM: train from two views a few degrees apart and merge the model's near-duplicate rows (todhip_model_compact: rows
+within DIST metres and HAM descriptor bits of a row kept before them go), e.g. --compact 0.003,24.
 """
 import argparse
 import os
@@ -39,6 +41,7 @@ def render(texture, theta, shift_px):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--learn-pattern", action="store_true", help="learn the ORB test pattern from the training view first")
+    ap.add_argument("--compact", metavar="DIST,HAM", help="train from two views and merge near-duplicate rows, e.g. 0.003,24")
     args = ap.parse_args()
     ctx = capi.Context(0)
     texture = synth.make_image(321)
@@ -55,10 +58,21 @@ def main():
         print("pattern: learned from %d keypoints and %d candidate tests, accepted per round %s" %
               (n, res["n_candidates"], res["accepted_in_round"]))
 
-    # --- training: one observation; the object frame is the training camera frame (R = I, T = 0)
+    # --- training: one observation (two with --compact); the object frame is the training camera frame (R = I, T = 0)
     model = capi.Model(ctx, 4000)
     model.add_observation(texture, mask, depth, K, np.eye(3, dtype=np.float32), np.zeros(3, np.float32), n_features=1500,
                           n_levels=3, scale_factor=1.2, pattern=pattern)
+    if args.compact:
+        # a second view, 5 degrees on and shifted: p_cam = R2 p_obj + t2, which is what cameraToWorld undoes
+        dist, ham = args.compact.split(",")
+        th2, shift2 = np.deg2rad(5.0), (7.0, -5.0)
+        c2, s2 = np.cos(th2), np.sin(th2)
+        R2 = np.array([[c2, -s2, 0], [s2, c2, 0], [0, 0, 1]], np.float32)
+        t2 = np.array([shift2[0] * Z / F, shift2[1] * Z / F, 0.0], np.float32) + (np.eye(3, dtype=np.float32) - R2) @ np.array([0, 0, Z], np.float32)
+        model.add_observation(render(texture, th2, shift2), mask, depth, K, R2, t2.astype(np.float32), n_features=1500, n_levels=3,
+                              scale_factor=1.2, pattern=pattern)
+        before, after = model.compact(float(dist), int(ham))
+        print("compact: %d rows before, %d after" % (before, after))
     desc, pts = model.finish(); model.close()
     print("model: %d descriptors with 3D points" % len(desc))
     spans = ctx.db_load(desc, pts, np.array([0, len(desc)], np.uint32))

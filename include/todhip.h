@@ -468,6 +468,34 @@ int  todhip_model_finish(todhip_ctx*, todhip_model*, uint8_t* desc, float* pts_x
  * With todhip_db_load_device a freshly trained model reaches the matcher without visiting the host (the reference writes it to
  * CouchDB, ModelFiller.cpp:23-24, and DescriptorMatcher::parameter_callback reads it back, DescriptorMatcher.cpp:60-129). */
 int  todhip_model_device(todhip_ctx*, todhip_model*, const void** d_desc, const void** d_pts_xyz, uint32_t* n);
+/* Append n already-trained rows (host memory; desc n x 32, pts_xyz n x 3) behind the model's rows, as many as still fit below its
+ * capacity: *n_added (may be NULL). How a stored model (ModelFiller.cpp:23-24) is taken up again before further observations, and how
+ * rows of any origin reach todhip_model_compact. n == 0 is allowed (the pointers may then be NULL). Synchronizes the context's stream. */
+int  todhip_model_add_rows(todhip_ctx*, todhip_model*, const uint8_t* desc, const float* pts_xyz, uint32_t n, uint32_t* n_added);
+/* Merge near-duplicate rows of the model in place. A model is the concatenation of its views' rows (mergePoints, training.cpp:147-173),
+ * so a surface point seen in v views is v rows; this keeps one of them. Off unless called, and without a counterpart in the reference.
+ * Definition (exact, deterministic), rows in model order 0 .. n-1:
+ *   ham(i, j) = popcount of the xor of the two 32-byte descriptors.
+ *   d2(i, j)  = (dx*dx + dy*dy) + dz*dz with dx = x_i - x_j (dy, dz alike), every operation in IEEE binary32, rounded once, no fused
+ *               multiply-add: exactly symmetric in i and j. r2 = merge_dist * merge_dist in binary32.
+ *   conflict(i, j) <=> ham(i, j) <= max_hamming and d2(i, j) <= r2, both bounds inclusive. A NaN in either point makes the float
+ *               comparison false: such a row conflicts with nothing and is always kept.
+ *   Row i is kept iff no KEPT row j < i has conflict(i, j) (greedy in row order, not transitive: if A conflicts with B, B with C and A
+ *               not with C, then A and C are kept and B goes).
+ *   The kept rows move stably to the front: descriptors and points unchanged, relative order unchanged; the model's row count
+ *               becomes their number.
+ *   support[r] (optional) of the r-th kept row = 1 + the dropped rows whose lowest-index conflicting kept row it is; their sum is
+ *               *rows_before.
+ * merge_dist == 0 merges only rows with d2 == 0: equal points (+0 == -0), or differences whose squares all underflow to 0 (below
+ * 2^-75; subnormal results are kept, not flushed). max_hamming == 256 ignores the descriptors. An empty model is TODHIP_OK with 0 -> 0. Compacting again with the same arguments changes nothing (no two kept rows conflict).
+ * TODHIP_EINVAL, the model untouched: merge_dist negative or not finite, max_hamming > 256, a null context or model, support without
+ * n_support, or a model of more than 2^18 rows (the pair test is quadratic in the rows; device scratch is linear in them).
+ * support: capacity *n_support in, *n_support = *rows_after out (n_support alone, support == NULL, just receives the count); when the
+ * capacity is too small: TODHIP_ECAPACITY with *n_support = *rows_after, the model already compacted. rows_before / rows_after may be
+ * NULL. Synchronizes the context's stream, as todhip_model_device does; todhip_model_add_observation, _add_rows, _device and _finish
+ * then work on the compacted model. */
+int  todhip_model_compact(todhip_ctx*, todhip_model*, float merge_dist, uint32_t max_hamming, uint32_t* rows_before,
+                          uint32_t* rows_after, uint32_t* support /* capacity *n_support in, may be NULL */, uint32_t* n_support);
 void todhip_model_free(todhip_ctx*, todhip_model*);
 
 /* ---- training: an rBRIEF test pattern learned from training views (Rublee et al., ORB, section 4.3) ------------------ */

@@ -84,6 +84,7 @@ EXPORTS = [
     "todhip_verify_batch_device", "todhip_verify_batch_device_depth",
     "todhip_match_l2", "todhip_match_l2_device",
     "todhip_model_begin", "todhip_model_add_observation", "todhip_model_finish", "todhip_model_device", "todhip_model_free",
+    "todhip_model_add_rows", "todhip_model_compact",
     "todhip_rescale_depth", "todhip_rescale_depth_device", "todhip_verify_2d", "todhip_verify_2d_device", "todhip_verify_2d_batch_device", "todhip_set_lsh",
     "todhip_set_db_bit_order", "todhip_db_bit_order",
     "todhip_pipeline_default_params", "todhip_pipeline_create", "todhip_pipeline_destroy", "todhip_pipeline_matcher",
@@ -93,6 +94,9 @@ EXPORTS = [
     "todhip_pattern_learn_responses", "todhip_pattern_learn_free", "todhip_pipeline_set_pattern",
     "todhip_db_select_objects", "todhip_db_selection", "todhip_pipeline_select_objects",
 ]
+
+# Model.compact's default descriptor bound: the setting of DESIGN 6f's end-to-end check, well inside the matcher's radius (35 or 55)
+DEFAULT_COMPACT_HAMMING = 24
 
 _lib = None
 
@@ -129,6 +133,11 @@ def lib():
             L.todhip_db_select_objects.argtypes, L.todhip_db_select_objects.restype = [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int
             L.todhip_db_selection.argtypes, L.todhip_db_selection.restype = [C.c_void_p] * 4, C.c_int
             L.todhip_pipeline_select_objects.argtypes, L.todhip_pipeline_select_objects.restype = [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int
+        if hasattr(L, "todhip_model_compact"):                        # (as above)
+            L.todhip_model_add_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.todhip_model_add_rows.restype = C.c_int
+            L.todhip_model_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_uint32] + [C.c_void_p] * 4
+            L.todhip_model_compact.restype = C.c_int
         _lib = L
     return _lib
 
@@ -581,6 +590,28 @@ class Model:
                                                 C.c_float(scale_factor), None if pat is None else _np_ptr(pat), C.byref(n))
         _check(rc, "todhip_model_add_observation")
         return n.value
+
+    def add_rows(self, desc, pts):
+        """Already-trained rows (desc u8[n, 32], pts f32[n, 3]) behind the model's rows, cut at its capacity -> rows added."""
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+        if len(d) != len(p):
+            raise ValueError("desc and pts differ in rows")
+        n = C.c_uint32(0)
+        _check(lib().todhip_model_add_rows(self._ctx._h, self._h, _np_ptr(d) if len(d) else None, _np_ptr(p) if len(d) else None, len(d), C.byref(n)),
+               "todhip_model_add_rows")
+        return n.value
+
+    def compact(self, merge_dist, max_hamming=DEFAULT_COMPACT_HAMMING, want_support=False):
+        """Merge near-duplicate rows in place (todhip_model_compact: a row goes when a kept row before it lies within merge_dist of its
+        point and within max_hamming bits of its descriptor) -> (rows_before, rows_after[, support u32[rows_after]])."""
+        before, after, ns = C.c_uint32(0), C.c_uint32(0), C.c_uint32(self._cap if want_support else 0)
+        sup = np.zeros(max(self._cap, 1), np.uint32) if want_support else None
+        _check(lib().todhip_model_compact(self._ctx._h, self._h, merge_dist, max_hamming, C.byref(before), C.byref(after),
+                                          _np_ptr(sup) if want_support else None, C.byref(ns)), "todhip_model_compact")
+        if want_support:
+            return before.value, after.value, sup[:ns.value].copy()
+        return before.value, after.value
 
     def device(self):
         """(device pointer of the descriptors, device pointer of the points, rows) -- valid until close()."""

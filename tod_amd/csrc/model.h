@@ -1,0 +1,11 @@
+// A model being trained (todhip_model of include/todhip.h): shared by train.hip, which fills it, and model_compact.hip, which thins it.
+#pragma once
+
+#include "ctx.h"
+
+// desc: cap x 32 bytes, pts: cap x 3 f32; small[0] = the model's rows (device-resident: no call needs it on the host to append),
+// small[1] = rows added by the last call, small[2] = the last observation's keypoints. The rest is one observation's scratch.
+struct todhip_model {
+  DevBuf desc, pts, kp_xy, kp_aux, kp_desc, img, mask, er_tmp, er, depth, flags, offs, small;
+  uint32_t cap = 0;
+};

@@ -3,16 +3,12 @@
 // (equal-size case), validateKeyPoints, depthTo3dSparse, cameraToWorld, mergePoints. A model is accumulated in HBM
 // observation by observation and read back once; its rows (32-byte descriptors + object-frame points) are exactly
 // what todhip_db_load ingests, so DBs built here match this repo's ORB.
+#include <algorithm>
 #include <cfloat>
 #include <cstring>
 #include <new>
 
-#include "ctx.h"
-
-struct todhip_model {
-  DevBuf desc, pts, kp_xy, kp_aux, kp_desc, img, mask, er_tmp, er, depth, flags, offs, small;
-  uint32_t cap = 0;
-};
+#include "model.h"
 
 namespace {
 
@@ -286,6 +282,29 @@ int todhip_rescale_depth(todhip_ctx* ctx, const void* depth_in, int depth_is_u16
   if (rc == TODHIP_OK && hipMemcpyAsync(depth_out, out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = TODHIP_EHIP;
   (void)hipStreamSynchronize(ctx->stream);                    // (in and out are freed on return, after the copies)
   return rc;
+}
+
+// Rows trained earlier (a stored model, ModelFiller.cpp:23-24) behind the model's rows, cut at its capacity.
+int todhip_model_add_rows(todhip_ctx* ctx, todhip_model* m, const uint8_t* desc, const float* pts_xyz, uint32_t n, uint32_t* n_added) {
+  if (n_added) *n_added = 0;
+  if (!ctx || !m || (n && (!desc || !pts_xyz))) return TODHIP_EINVAL;
+  if (n == 0) return TODHIP_OK;
+  TOD_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  uint32_t rows = 0;
+  TOD_HIP(hipMemcpyAsync(&rows, m->small.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));
+  if (rows > m->cap) return TODHIP_EINVAL;
+  const uint32_t add = std::min(n, m->cap - rows);
+  const uint32_t h[2] = {rows + add, add};                  // as append_kernel leaves the counters
+  if (add) {
+    TOD_HIP(hipMemcpyAsync(m->desc.as<uint8_t>() + (size_t)rows * 32, desc, (size_t)add * 32, hipMemcpyHostToDevice, st));
+    TOD_HIP(hipMemcpyAsync(m->pts.as<float>() + (size_t)rows * 3, pts_xyz, (size_t)add * 12, hipMemcpyHostToDevice, st));
+  }
+  TOD_HIP(hipMemcpyAsync(m->small.p, h, sizeof(h), hipMemcpyHostToDevice, st));
+  TOD_HIP(hipStreamSynchronize(st));                        // desc, pts_xyz and h may go once this returns
+  if (n_added) *n_added = add;
+  return TODHIP_OK;
 }
 
 // mergePoints (training.cpp:147-173) + ModelFiller (ModelFiller.cpp:20-26): the stacked descriptors and points.

@@ -56,10 +56,11 @@ def render_views(textures_gpu, obj_ids, thetas_deg, shifts_px, noise_seed, noise
     return torch.clamp(torch.round(img), 0, 255).to(torch.uint8), inside
 
 
-def train_db(ctx, textures, n_features=1300, n_levels=3, views=TRAIN_VIEWS, rows_per_object=None, pattern=None):
+def train_db(ctx, textures, n_features=1300, n_levels=3, views=TRAIN_VIEWS, rows_per_object=None, pattern=None, compact=None):
     """One model per texture from `views` (todhip_model_*). Returns (desc u8[N, 32], pts f32[N, 3], obj_off u32[n + 1]).
     rows_per_object: keep at most that many rows of each model (the first ones: whole early views). pattern: the ORB test pattern
-    (None = built-in; capi.PatternLearner)."""
+    (None = built-in; capi.PatternLearner). compact: None, or (merge_dist, max_hamming) -- every model's near-duplicate rows are
+    merged (capi.Model.compact) before it is read back."""
     import torch
     from . import capi
     n_obj = len(textures)
@@ -78,6 +79,8 @@ def train_db(ctx, textures, n_features=1300, n_levels=3, views=TRAIN_VIEWS, rows
             R, t = view_pose(theta, shift)
             model.add_observation(imgs[vi], masks[vi], depth, K, R, t, n_features=n_features, n_levels=n_levels, scale_factor=1.2,
                                   pattern=pattern)
+        if compact is not None:
+            model.compact(compact[0], compact[1])
         d, p = model.finish()
         model.close()
         if rows_per_object is not None:
