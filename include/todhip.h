@@ -230,6 +230,45 @@ int todhip_merge_shards_device(todhip_ctx*, const void* d_keys_all, uint32_t n_s
 int todhip_merge_shards_device_on(todhip_ctx*, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq,
                                   uint32_t k, uint32_t radius, void* d_counts, void* d_matches, void* d_matches_xyz);
 
+/* The true radius search: every searched row within `radius` bits of a query, not the k <= 8 nearest cut at the radius. The
+ * reference documents `radius` as "for epsilon nearest neighbor search" (DescriptorMatcher.cpp:137) and falls back to knnMatch(5)
+ * plus a cut only because "this does not work for LSH on OpenCV 2.4" (:201-220); this is cv::DescriptorMatcher::radiusMatch, the
+ * third member of match / knnMatch / radiusMatch. On self-similar texture a query has hundreds of model rows inside the radius (a
+ * surface point is one row per training view) and k = 5 hands the verifier five of them without saying so.
+ * Definition (exact, deterministic):
+ *   d(q, r)      = popcount of the xor of the two 32-byte descriptors.
+ *   R(q)         = the searched rows with d(q, r) <= radius (inclusive, as the cut of todhip_match drops distance > radius);
+ *                  radius >= 256 puts every searched row in R(q).
+ *   in_radius[q] = |R(q)|, exact, never truncated.
+ *   matches of q = R(q) in the library's total order (distance ascending, then row of the full DB ascending), cut after the first
+ *                  max_per_query; counts[q] = min(|R(q)|, max_per_query). queryIdx, trainIdx, imgIdx, distance and the gathered model
+ *                  point of a row are exactly what todhip_match writes for it.
+ *   searched rows = what todhip_match* searches on this context: the resident shard, in the numbering of the full DB. On a context
+ *                  loaded with shard_count > 1 each rank answers for its own rows; the keys (distance, row) are unique over the ranks,
+ *                  so a caller merges the ranks' answers by concatenating and sorting them (in_radius adds up). todhip_db_select_objects
+ *                  is honoured: the result is that of a context loaded with the selected objects alone, imgIdx in the full DB's
+ *                  numbering; an empty selection gives all counts 0. todhip_set_db_bit_order is honoured: the queries are permuted as
+ *                  the other forms permute them, the results do not change.
+ *   The ratio test and the LSH mode do NOT apply: this is the exact search over all searched rows whatever todhip_set_ratio_test and
+ *   todhip_set_lsh say.
+ * Host form: CSR like todhip_match. *n_matches: capacity of matches / matches_xyz (in matches) in, row_ptr[nq] out; when it is too
+ * small: TODHIP_ECAPACITY with the needed count in *n_matches, row_ptr and in_radius filled, matches untouched. in_radius may be NULL.
+ * Device form: fixed stride max_per_query like todhip_match_device's stride k -- d_counts[nq] u32, d_matches[nq * max_per_query],
+ * d_matches_xyz[nq * max_per_query * 3], d_in_radius[nq] u32 (may be NULL); the slots behind counts[q] are not written, as
+ * todhip_match_device leaves them.
+ * TODHIP_EINVAL: a null context, query or output pointer, nq == 0, radius == 0, max_per_query == 0 or > 1024, a float DB
+ * (desc_bytes == 512). TODHIP_ENODB without a DB. todhip_get_counters: last_nq, last_k = max_per_query, last_matches (host form);
+ * todhip_set_kernel_timing brackets the DB pass.
+ * Workspace: a candidate buffer of nq * C * 8 bytes, C = 2 * max_per_query rounded up to a power of two, at least 64, plus
+ * nq * (min(radius, 256) + 2) * 4 bytes of counters. A query with at most C rows inside the radius is answered from the one DB pass;
+ * one with more is answered by a second, ordered pass over the rows for that query (same result). */
+int todhip_match_radius(todhip_ctx*, const uint8_t* q_desc, uint32_t nq, uint32_t radius, uint32_t max_per_query,
+                        uint32_t* row_ptr /*[nq+1]*/, todhip_dmatch* matches, float* matches_xyz,
+                        uint32_t* n_matches /* capacity in, count out */, uint32_t* in_radius /*[nq], may be NULL*/);
+int todhip_match_radius_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t radius, uint32_t max_per_query,
+                               void* d_counts /*[nq] u32*/, void* d_matches /*[nq*max_per_query]*/,
+                               void* d_matches_xyz /*[nq*max_per_query*3]*/, void* d_in_radius /*[nq] u32, may be NULL*/);
+
 /* ---- stage C: GuessGenerator ------------------------------------------------------------------- */
 void todhip_rng_seed(todhip_rng*, uint32_t seed);   /* srand(seed); the reference never seeds => seed 1 */
 /* Replaces GuessGenerator::process (GuessGenerator.cpp:127-250) and everything under src/common.

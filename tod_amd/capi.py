@@ -93,7 +93,20 @@ EXPORTS = [
     "todhip_pattern_learn_begin", "todhip_pattern_learn_add_view", "todhip_pattern_learn_add_view_device", "todhip_pattern_learn_finish",
     "todhip_pattern_learn_responses", "todhip_pattern_learn_free", "todhip_pipeline_set_pattern",
     "todhip_db_select_objects", "todhip_db_selection", "todhip_pipeline_select_objects",
+    "todhip_match_radius", "todhip_match_radius_device",
 ]
+
+MAX_PER_QUERY_LIMIT = 1024
+
+
+def radius_capacity(max_per_query):
+    """C of todhip_match_radius: the keys a query's candidate buffer holds (2 * max_per_query rounded up to a power of two, at least
+    64). A query with more rows than that inside the radius is answered by the ordered second pass."""
+    c = 64
+    while c < 2 * max_per_query:
+        c *= 2
+    return c
+
 
 # Model.compact's default descriptor bound: the setting of DESIGN 6f's end-to-end check, well inside the matcher's radius (35 or 55)
 DEFAULT_COMPACT_HAMMING = 24
@@ -138,6 +151,11 @@ def lib():
             L.todhip_model_add_rows.restype = C.c_int
             L.todhip_model_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_uint32] + [C.c_void_p] * 4
             L.todhip_model_compact.restype = C.c_int
+        if hasattr(L, "todhip_match_radius"):                         # (as above)
+            L.todhip_match_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
+            L.todhip_match_radius.restype = C.c_int
+            L.todhip_match_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+            L.todhip_match_radius_device.restype = C.c_int
         _lib = L
     return _lib
 
@@ -325,6 +343,24 @@ class Context:
     def match(self, q_desc, k, radius):
         """Host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
         return self._match_host(lib().todhip_match, "todhip_match", np.ascontiguousarray(q_desc, np.uint8), k, C.c_uint32(radius))
+
+    def match_radius(self, q_desc, radius, max_per_query):
+        """The true radius search, host-buffer form (todhip_match_radius): every searched row within `radius` bits, the nearest
+        max_per_query of them per query. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3], in_radius u32[nq])."""
+        q = np.ascontiguousarray(q_desc, np.uint8)
+        nq = q.shape[0]
+        cap = max(nq * max_per_query, 1)
+        row_ptr, in_radius = np.zeros(nq + 1, np.uint32), np.zeros(nq, np.uint32)
+        m, xyz = np.empty(cap, DMATCH_DTYPE), np.empty((cap, 3), np.float32)
+        n = C.c_uint32(cap)
+        _check(lib().todhip_match_radius(self._h, _np_ptr(q), nq, radius, max_per_query, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz),
+                                         C.addressof(n), _np_ptr(in_radius)), "todhip_match_radius")
+        return row_ptr, m[:n.value].copy(), xyz[:n.value].copy(), in_radius
+
+    def match_radius_device(self, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
+        """Device-pointer form (ints from tensor.data_ptr()), fixed stride max_per_query; d_in_radius may be None."""
+        _check(lib().todhip_match_radius_device(self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius),
+               "todhip_match_radius_device")
 
     def match_l2(self, q_desc, k, radius):
         """Float descriptors, host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""

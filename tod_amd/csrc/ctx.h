@@ -95,7 +95,7 @@ struct HostBuf {
 // A stage's workspace: defined in the stage's translation unit (struct XWs : TodWs with kSlot = its slot), created on first use by
 // tod_ws<XWs>(ctx), owned by the context. Its destructor is the stage's whole teardown. The slots are released in this order.
 struct TodWs { virtual ~TodWs() {} };
-enum TodWsSlot { kWsVerify, kWsOrb, kWsL2, kWsPnp, kWsLsh, kWsLearn, kWsCompact, kWsSlots };
+enum TodWsSlot { kWsVerify, kWsOrb, kWsL2, kWsPnp, kWsLsh, kWsLearn, kWsCompact, kWsRadius, kWsSlots };
 
 struct todhip_ctx {
   int device = 0;

@@ -147,22 +147,7 @@ __global__ __launch_bounds__(kBlock) void finalize_kernel(const uint64_t* __rest
   for (uint32_t j = 0; j < n_picked && j < k_out; ++j) {
     const uint32_t d = (uint32_t)(picked[j] >> 32);
     if ((float)d > (float)radius) break;                    // radius truncation, :212-220 (float vs unsigned compare)
-    const uint32_t row = (uint32_t)picked[j];
-    uint32_t lo = 0, hi = n_objs;            // last object whose first row is <= row
-    while (hi - lo > 1) {
-      uint32_t mid = (lo + hi) >> 1;
-      if (obj_off[mid] <= row) lo = mid; else hi = mid;
-    }
-    todhip_dmatch m;
-    m.queryIdx = (int32_t)qi;
-    m.trainIdx = (int32_t)(row - obj_off[lo]);
-    m.imgIdx = (int32_t)lo;
-    m.distance = (float)d;
-    matches[(size_t)qi * k_out + kept] = m;
-    float* o = xyz + ((size_t)qi * k_out + kept) * 3;
-    o[0] = pts[(size_t)row * 3 + 0];
-    o[1] = pts[(size_t)row * 3 + 1];
-    o[2] = pts[(size_t)row * 3 + 2];
+    store_match(qi, d, (uint32_t)picked[j], (size_t)qi * k_out + kept, obj_off, n_objs, pts, matches, xyz);
     ++kept;
   }
   counts[qi] = kept;
