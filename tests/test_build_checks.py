@@ -53,6 +53,32 @@ def test_k4x_waves_leave_room_in_the_register_file(match_asm):
     assert seen == 8, "expected the four block forms of hamming_topk_mfma<1 / 2, 6, ...>"
 
 
+R1_REGISTERS = {2: 112, 4: 185, 6: 228}                                # per QT, as measured when the check was written
+
+
+def test_r1_waves_stay_two_per_simd_without_scratch():
+    """The radius search's DB pass (radius_collect_mfma in tod_amd/csrc/match_radius.hip) is launched under
+    __launch_bounds__(kBlock, 2): two waves per SIMD, which the six-block form keeps only while it stays inside 256 registers --
+    it sits at 228 -- and without scratch. It shares its block primitives with K4x (match_fp4.h), so a change made for either
+    kernel can move the other's allocation; only the generated code can tell. No form may use more registers than it did."""
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not installed")
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "match_radius.s")
+        subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-S", "--cuda-device-only",
+                        "-o", out, os.path.join(ROOT, "tod_amd", "csrc", "match_radius.hip")], check=True, stderr=subprocess.DEVNULL)
+        asm = open(out).read()
+    seen = set()
+    for m in re.finditer(r"\.name:\s+(\S*radius_collect_mfmaILi([246])ELb([01])E\S*)", asm):
+        blk = asm[m.start():m.start() + 1500]
+        vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1))
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
+        qt, imax = int(m.group(2)), int(m.group(3))
+        assert vgpr <= R1_REGISTERS[qt] and scratch == 0, "radius_collect_mfma<%d, %d>: %d registers, %d bytes of scratch" % (qt, imax, vgpr, scratch)
+        seen.add((qt, imax))
+    assert seen == {(qt, imax) for qt in (2, 4, 6) for imax in (0, 1)}, "expected the six forms of radius_collect_mfma<QT, IMAX>"
+
+
 def test_k4_prefetched_sgprs_are_untouched_until_their_wait(match_asm):
     asm = match_asm
     kernels, cur = [], None                                            # (name, [instruction lines]) per instantiation

@@ -64,21 +64,26 @@ def test_all_k(ctx, k):
     _assert_same(ctx, desc, pts, off, fr["q_desc"], k, 255)   # radius 255: nothing is cut for 256-bit rows
 
 
-@pytest.mark.parametrize("nq", [1, 63, 64, 65, 255, 256, 257, 1000])
+@pytest.mark.parametrize("nq", [1, 32, 33, 63, 64, 65, 129, 255, 256, 257, 1000])
 def test_ragged_query_counts(ctx, nq):
+    """1 and 32: the one-block kernel; 33 and 64: two blocks, one of them padding; 65 and 129: four, with whole blocks of padding
+    queries (they repeat the last one)"""
     desc, pts, off = synth.make_db(4, per_object=777)
     fr = synth.make_frame(desc, pts, off, nq, frame=nq, visible_object=2)
     _assert_same(ctx, desc, pts, off, fr["q_desc"], 2, 55)
 
 
-@pytest.mark.parametrize("n_rows", [1, 2, 3, 4, 5, 7, 63, 64, 65, 257, 4099])
+@pytest.mark.parametrize("n_rows", [1, 2, 3, 4, 5, 7, 31, 32, 33, 63, 64, 65, 95, 257, 4099, 8193])
 def test_tiny_and_odd_databases(ctx, n_rows):
-    """fewer rows than k, tails that are not a multiple of the 4-row group, single tiles"""
+    """fewer rows than k, tails that are not a multiple of the 4-row group, single tiles; on the matrix cores: one tile whose last
+    32-row step is partial or whole (its load reaches into the slack behind the rows), and 8 193 rows, several tiles of which the
+    last is a single partial step. Radius 200 takes the float block test, 35 the integer one."""
     desc, pts, off = synth.make_db_ragged([n_rows], seed=n_rows)
     rng = np.random.Generator(np.random.PCG64(n_rows))
     q = rng.integers(0, 256, (70, 32), dtype=np.uint8)
     q[:min(70, n_rows)] = desc[:min(70, n_rows)]
     _assert_same(ctx, desc, pts, off, q, 5, 200)
+    _assert_same(ctx, desc, pts, off, q, 5, 35)
 
 
 def test_ties_resolve_by_ascending_row(ctx):

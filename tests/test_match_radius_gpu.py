@@ -339,6 +339,37 @@ def test_many_tiles_and_query_waves(dev):
     assert np.array_equal(m["distance"], R.POPCOUNT[desc[rows] ^ q[m["queryIdx"]]].sum(axis=1).astype(np.float32))
 
 
+@pytest.mark.parametrize("n_rows,nqs", [(1, (1, 32, 33, 64, 65, 129, 1025)), (31, (1, 33, 65)), (32, (32, 64, 129)), (33, (1, 33, 65)),
+                                        (95, (1, 32, 33, 64, 65, 129, 1025)), (8193, (1, 32, 33, 64, 65, 129))])
+def test_steps_tiles_and_query_blocks_at_their_edges(n_rows, nqs):
+    """What the DB pass shares with the top-k kernels (match_fp4.h), at the shapes where it can go wrong. Rows: one tile whose last
+    32-row step is partial or whole and whose load reaches into the slack behind the rows; 8 193 rows: several tiles, the last a
+    single partial step. Queries: two blocks per wave (<= 64), four (<= 1024) and six, each with a ragged last block and with whole
+    blocks of padding queries, which repeat query nq - 1. Radius 35: the integer block test; 200: the float one. Against the numpy
+    statement of the definition, bit for bit."""
+    rng = np.random.Generator(np.random.PCG64(n_rows))
+    desc = rng.integers(0, 256, (n_rows, 32), dtype=np.uint8)
+    pts = rng.standard_normal((n_rows, 3)).astype(np.float32)
+    off = np.array([0, n_rows // 3, n_rows], np.uint32)
+    q = rng.integers(0, 256, (max(nqs), 32), dtype=np.uint8)
+    for i in range(len(q)):                                             # six of seven queries: a row with 0..20 flipped bits
+        if i % 7 != 6:
+            bits = np.unpackbits(desc[(i * 37) % n_rows])
+            bits[rng.choice(256, i % 21, replace=False)] ^= 1
+            q[i] = np.packbits(bits)
+    c = capi.Context(0)
+    try:
+        c.set_matcher_engine("mfma")
+        c.db_load(desc, pts, off)
+        for radius in (35, 200):
+            want = R.match_radius(desc, off, pts, q, radius, 8)
+            assert want[3][::7].min() >= 1
+            for nq in nqs:
+                same(c.match_radius(q[:nq], radius, 8), prefix(want, nq), (n_rows, nq, radius))
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------------------------------------------- refusals
 def test_refusals(ctx, db):
     import ctypes as C

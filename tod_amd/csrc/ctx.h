@@ -12,6 +12,7 @@
 #include "../../include/todhip.h"
 #include "db_select.h"
 #include "match_split.h"
+#include "match_tiles.h"
 
 #define TOD_HIP(call)                                  \
   do {                                                 \
@@ -184,6 +185,13 @@ extern "C" uint32_t tod_cu_partition();                     // todhip_set_cu_par
 int tod_timing_begin(todhip_ctx* ctx, int* slot);
 int tod_timing_end(todhip_ctx* ctx, int slot);
 int tod_timing_drain(todhip_ctx* ctx, uint64_t keep);
+// The optional HIP-event bracket around a DB pass (todhip_set_kernel_timing)
+struct KernelTimer {
+  todhip_ctx* ctx;
+  int slot = -1;
+  int begin() { return ctx->time_kernels ? tod_timing_begin(ctx, &slot) : TODHIP_OK; }
+  int end() { return slot >= 0 ? tod_timing_end(ctx, slot) : TODHIP_OK; }
+};
 int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
                     uint32_t* n_lists);
 size_t tod_match_lists_bytes(uint32_t nq, uint32_t k);

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "row_ops.h"
 
 namespace {
 
@@ -485,8 +486,7 @@ __global__ __launch_bounds__(256) void l2_finalize_kernel(const uint64_t* __rest
     const float dist = sqrtf(__uint_as_float((uint32_t)(key >> 32)));
     if (dist > radius) break;
     const uint32_t row = (uint32_t)key;
-    uint32_t lo = 0, hi = n_objs;                           // last object whose first row is <= row
-    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (obj_off[mid] <= row) lo = mid; else hi = mid; }
+    const uint32_t lo = object_of_row(obj_off, n_objs, row);
     todhip_dmatch m;
     m.queryIdx = (int)qi; m.trainIdx = (int)(row - obj_off[lo]); m.imgIdx = (int)lo; m.distance = dist;
     matches[(size_t)qi * k + kept] = m;

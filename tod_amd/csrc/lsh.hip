@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "row_ops.h"
 
 namespace {
 
@@ -119,8 +120,7 @@ __global__ __launch_bounds__(256) void lsh_query_kernel(const uint8_t* __restric
         const uint32_t row = rows_t[__shfl(beg, (int)j) + (ii - __shfl(excl, (int)j))];
         if (valid) {
           const uint4 a = reinterpret_cast<const uint4*>(db + (size_t)row * 32)[0], b = reinterpret_cast<const uint4*>(db + (size_t)row * 32)[1];
-          const uint32_t d = __popc(a.x ^ qw[0]) + __popc(a.y ^ qw[1]) + __popc(a.z ^ qw[2]) + __popc(a.w ^ qw[3]) + __popc(b.x ^ qw[4]) +
-                             __popc(b.y ^ qw[5]) + __popc(b.z ^ qw[6]) + __popc(b.w ^ qw[7]);
+          const uint32_t d = hamming256(a, b, qw);
           const uint64_t key = ((uint64_t)d << 32) | (shard_first + row);
           if (key < best[K - 1]) {
             bool dup = false;

@@ -18,23 +18,25 @@
 //                          group, the second half of those rows is never touched. Exact for any data; how
 //                          often it fires depends on the data (always, but for ~1e-4 of the groups, on
 //                          descriptors with independent bits and radius 35).
-// K4x hamming_topk_mfma    the same search on the matrix cores (fp4 x fp4 MFMAs, exact): match_mfma.h.
+// K4x hamming_topk_mfma    the same search on the matrix cores (fp4 x fp4 MFMAs, exact): match_fp4.h, match_mfma.h.
 // K4m merge_tiles_kernel   per query: merge the per-tile lists into k global keys.
 // K4f finalize_kernel      per query: merge shard lists, radius cut, object lookup, 3D gather.
 // This file is the matcher's one translation unit: the engine choice, the timing ring and the tod_match_* entry points. The rest
-// is included below: match_keys.h (constants, sorted lists, the pick over lists), match_valu.h (K4), match_mfma.h (K4x), match_merge.h
-// (K4m, K4s, K4f), match_launch.h (knobs, tiling plan, launchers); the block-split controller, match_split.h, comes with ctx.h.
+// is included below: match_keys.h (constants, sorted lists, the pick over lists), match_valu.h (K4), match_fp4.h + match_mfma.h (K4x: block
+// primitives, kernels), match_merge.h (K4m, K4s, K4f), match_launch.h (knobs, tiling plan, launchers); with ctx.h: match_split.h, KernelTimer.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
 #include "ctx.h"
+#include "row_ops.h"
 
 namespace {
 
 #include "match_keys.h"
 #include "match_valu.h"
+#include "match_fp4.h"
 #include "match_mfma.h"
 #include "match_merge.h"
 #include "match_launch.h"

@@ -1,7 +1,7 @@
 // What both matcher engines and the merges share: the launch constants, the per-lane sorted list of partial keys (distance << 22 |
 // tile-local row; the merges widen them to distance << 32 | global row, the order (distance asc, global row asc) of decision D1) and
-// the pick over ascending lists of global keys, and the store of one kept match (object lookup, DescriptorMatcher.cpp:60-129, and
-// 3D gather, :231-244). Included by match.hip and match_radius.hip inside their anonymous namespaces, after ctx.h.
+// the pick over ascending lists of global keys, and the store of one kept match (object lookup, row_ops.h, and 3D gather,
+// DescriptorMatcher.cpp:231-244). Included by match.hip and match_radius.hip inside their anonymous namespaces, after ctx.h and row_ops.h.
 
 constexpr int kWords = 8;          // 256-bit descriptors (ORB / rBRIEF), 32 bytes per row
 constexpr int kGroupRows = 4;      // DB rows per SGPR group (two s_load_dwordx16)
@@ -42,16 +42,12 @@ __device__ __forceinline__ uint64_t next_key_over_lists(const uint64_t* __restri
   return nxt;
 }
 
-// One kept match into output slot `slot`: the global row becomes (imgIdx, trainIdx) through the object prefix sums (DB load order,
-// DescriptorMatcher.cpp:60-129) and brings its model point (:231-244). What K4f and the radius search's finalize both end in.
+// One kept match into output slot `slot`: the global row becomes (imgIdx, trainIdx) through the object prefix sums (object_of_row)
+// and brings its model point (DescriptorMatcher.cpp:231-244). What K4f and the radius search's finalize both end in.
 __device__ __forceinline__ void store_match(uint32_t qi, uint32_t d, uint32_t row, size_t slot, const uint32_t* __restrict__ obj_off,
                                             uint32_t n_objs, const float* __restrict__ pts, todhip_dmatch* __restrict__ matches,
                                             float* __restrict__ xyz) {
-  uint32_t lo = 0, hi = n_objs;            // last object whose first row is <= row
-  while (hi - lo > 1) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (obj_off[mid] <= row) lo = mid; else hi = mid;
-  }
+  const uint32_t lo = object_of_row(obj_off, n_objs, row);
   todhip_dmatch m;
   m.queryIdx = (int32_t)qi;
   m.trainIdx = (int32_t)(row - obj_off[lo]);

@@ -1,7 +1,7 @@
-// Host planning of the matcher's launches: the environment knobs, the tiling plan, the workspace set-up, the timing bracket, the
+// Host planning of the matcher's launches: the environment knobs, the tiling plan, the workspace set-up, the
 // merge launch and the launchers of both engines. Each engine keeps its own, measured policy for how many tiles to ask for; what
 // follows that policy is shared. The k of the reference's knnMatch is DescriptorMatcher.cpp:211, its radius cut :212-220.
-// Included by match.hip inside its anonymous namespace, after match_keys.h, match_valu.h, match_mfma.h and match_merge.h.
+// Included by match.hip inside its anonymous namespace, after match_keys.h, match_valu.h, match_fp4.h, match_mfma.h and match_merge.h.
 
 int k4_engine(const todhip_ctx* ctx, uint32_t nq);   // match.hip, behind this header
 
@@ -59,14 +59,6 @@ uint8_t* prepare_lists(todhip_ctx* ctx, uint32_t n_tiles, uint32_t nq_pad, uint3
   return ctx->m_bound.as<uint8_t>() + bound_bytes;
 }
 
-// The optional HIP-event bracket around the DB pass (tod_timing_*, match.hip)
-struct KernelTimer {
-  todhip_ctx* ctx;
-  int slot = -1;
-  int begin() { return ctx->time_kernels ? tod_timing_begin(ctx, &slot) : TODHIP_OK; }
-  int end() { return slot >= 0 ? tod_timing_end(ctx, slot) : TODHIP_OK; }
-};
-
 // K4m behind a DB pass. wave: a handful of queries over thousands of tiles, a wave per (query, group). d_stats: the DB pass's
 // split-block counters, which the counting form carries to pinned memory (K4xSplit::take_report reads them there).
 template <int K>
@@ -95,7 +87,7 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
   // Rounds of waves: the chip holds 8 of these waves per CU (2 per SIMD, by registers). A launch whose wave count is just
   // under a whole number of rounds has no straggling last round (measured, tools/k4x_sweep.py, 16 000 x 1M: 16 waves per
   // CU = 2 rounds 1.13 ms, 14 = 1.6 rounds 1.37 ms, 8 = all resident 1.36 ms, 32 .. 128 1.11 ms); four rounds while a tile
-  // then still has >= 48 steps (a tile starts with empty lists), two otherwise. Tiles are whole 32-row steps.
+  // then still has >= 48 steps (a tile starts with empty lists), two otherwise. Tiles: mfma_tile_rows, of >= 256 rows.
   uint32_t wpc = 32;
   if ((uint64_t)n_rows * n_qw < (uint64_t)ctx->n_cu * wpc * 1536u) wpc = 16;
   // A tile starts with empty lists and the radius as its threshold, and every row inside the threshold costs a walk of its block
@@ -106,12 +98,8 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
   // (tools/k4x_chained_frame.sh, tools/k4x_synth_frame.sh).
   if ((uint64_t)n_rows * n_qw < (uint64_t)ctx->n_cu * 16u * 4096u) wpc = 8;
   if (env.k4x_wpc > 0) wpc = (uint32_t)env.k4x_wpc;
-  uint32_t n_tiles = std::max(1u, (uint32_t)ctx->n_cu * wpc / n_qw);
-  n_tiles = std::min(n_tiles, std::max(1u, n_rows / 256u));
-  n_tiles = std::min(n_tiles, 8192u);
-  if (n_tiles >= 16) n_tiles &= ~7u;                                  // whole tiles per XCD, never more waves than asked for
   Tiling t;
-  if (!finish_tiling(n_rows, ((n_rows + n_tiles - 1) / n_tiles + 31u) & ~31u, n_qw, &t)) return TODHIP_EINVAL;
+  if (!finish_tiling(n_rows, mfma_tile_rows(n_rows, (uint32_t)ctx->n_cu * wpc / n_qw, 256u, true), n_qw, &t)) return TODHIP_EINVAL;
   uint8_t* const d_stored = prepare_lists<K>(ctx, t.n_tiles, nq_pad, n_qw64);
   if (!d_stored) return TODHIP_EHIP;
   KernelTimer timer{ctx};
@@ -149,10 +137,8 @@ int launch_topk_mfma_q32(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint
   const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu >> kLocalBits : radius + 1u;
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx), n_qw64 = 1u, nq_pad = 64u;
   // one wave per tile; about 32 waves per CU in all (each holds four 1 KB loads in flight), tiles of >= 2048 rows
-  uint32_t n_tiles = std::max(1u, std::min<uint32_t>((uint32_t)ctx->n_cu * 32u, n_rows / 2048u));
-  n_tiles = std::min(n_tiles, 8192u);
   Tiling t;
-  if (!finish_tiling(n_rows, ((n_rows + n_tiles - 1) / n_tiles + 31u) & ~31u, 1u, &t)) return TODHIP_EINVAL;
+  if (!finish_tiling(n_rows, mfma_tile_rows(n_rows, (uint32_t)ctx->n_cu * 32u, 2048u, false), 1u, &t)) return TODHIP_EINVAL;
   uint8_t* const d_stored = prepare_lists<K>(ctx, t.n_tiles, nq_pad, n_qw64);
   if (!d_stored) return TODHIP_EHIP;
   KernelTimer timer{ctx};

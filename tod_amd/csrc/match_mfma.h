@@ -1,66 +1,13 @@
-// K4x, the exact search on the matrix cores: the fp4 expansion, the 32 x 32 accumulator blocks and their tests (whole and split),
-// the 32-row step, hamming_topk_mfma and its <= 32-query form hamming_topk_mfma_q32. TOD_K4X_ABLATE / TOD_K4X_COUNT_WALKS are
-// diagnostics builds (tools/k4x_ablate.sh, tools/k4x_walks.sh). The radius bound restates DescriptorMatcher.cpp:212-220.
-// Included by match.hip inside its anonymous namespace, after match_keys.h.
-//
-// K4x  hamming_topk_mfma   the same exact search on the matrix cores. With every descriptor bit b written as the
-//                          MX-fp4 (E2M1) value 1 - 2b, the dot product of two descriptors is 256 - 2 * hamming: products
-//                          are +-1, the f32 accumulator holds integers <= 256, so the result is EXACT.
-//                          v_mfma_f32_32x32x64_f8f6f4 (fp4 x fp4, unit scales) takes 64 bit positions of 32 DB rows x 32
-//                          queries per issue: 4 MFMAs = 1024 complete distances in 128 matrix-pipe cycles (8 pairs per
-//                          clock and SIMD; the VALU form above peaks at 1, or ~2 when its elimination fires) and the
-//                          rate does not depend on the data.
-//                          One WAVE = (DB tile, 32 QT queries). The query fragments stay in registers (16 VGPRs per
-//                          32 queries); every lane loads 16 packed bytes of one DB row per 32-row step (a wave load = 32
-//                          rows = 1 KB contiguous, served by L2: all query waves of a tile read the same lines), expands
-//                          them to fp4 with 7 VALU ops per 32 bits, no LDS, no barrier. A and B use the same
-//                          (lane, register, nibble) -> bit assignment, so the sum runs over matching bit positions whatever
-//                          the hardware's internal k order is.
-//                          Accumulator layout (dtype independent): lane = query column (l & 31), 16 registers = 16 DB
-//                          rows (i & 3) + 8 (i >> 2) + 4 (l >> 5). A lane keeps its k best keys in registers exactly as
-//                          K4 does; the test per 32 x 32 block is max over the 16 registers > threshold (8 v_max3 + 1
-//                          compare, in the shadow of the next block's MFMAs) and only a block with a hit walks its registers.
-//                          Bounds are exchanged between tiles through the same per-query word as K4 (loaded one period
-//                          ahead, so the latency of the load is never waited for). Output = K4's partial-key layout.
-typedef int mfma_i32x8 __attribute__((ext_vector_type(8)));
-typedef float mfma_f32x16 __attribute__((ext_vector_type(16)));
-
-// 32 descriptor bits -> 32 fp4 values (4 dwords): nibble i of out[j] = 0x2 | (bit (4 i + j) << 3)  (+1.0 / -1.0 in E2M1).
-// The two constants live in registers (gfx9 VOP3 takes no literal), so each dword is one shift + one v_and_or_b32.
-struct Fp4Consts { uint32_t sign, one; };
-__device__ __forceinline__ Fp4Consts fp4_consts() {
-  Fp4Consts k;
-  asm volatile("s_mov_b32 %0, 0x88888888" : "=s"(k.sign));
-  asm volatile("v_mov_b32 %0, 0x22222222" : "=v"(k.one));
-  return k;
-}
-__device__ __forceinline__ mfma_i32x8 expand_word(uint32_t x, const Fp4Consts& k) {
-  const int a = (int)(((x << 3) & k.sign) | k.one), b = (int)(((x << 2) & k.sign) | k.one),
-            c = (int)(((x << 1) & k.sign) | k.one), d = (int)((x & k.sign) | k.one);
-  return mfma_i32x8{a, b, c, d, 0, 0, 0, 0};
-}
-
-struct Fp4Row { mfma_i32x8 s[4]; };   // the lane's 128 bits of one row: 4 MFMA steps x 4 dwords (upper halves unused by fp4)
-
-__device__ __forceinline__ void expand_row(const uint4& p, Fp4Row& f, const Fp4Consts& k) {
-  f.s[0] = expand_word(p.x, k); f.s[1] = expand_word(p.y, k); f.s[2] = expand_word(p.z, k); f.s[3] = expand_word(p.w, k);
-}
-
-__device__ __forceinline__ float thr_of_limit(uint32_t limit) { return 256.f - 2.f * (float)limit; }   // dot > thr <=> d < limit
-
-// 256 bit positions of 32 DB rows (A) x 32 queries (B): acc[i] of lane l = dot(row (i & 3) + 8 (i >> 2) + 4 (l >> 5), query l & 31)
-__device__ __forceinline__ mfma_f32x16 dot_block(const Fp4Row& a, const Fp4Row& b) {
-  mfma_f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[s], b.s[s], acc, 4, 4, 0, 0, 0, 0);
-  return acc;
-}
-
+// K4x, the exact top-k search on the matrix cores: the tests of the 32 x 32 accumulator blocks (whole and split), the 32-row step,
+// hamming_topk_mfma and its <= 32-query form hamming_topk_mfma_q32, on match_fp4.h's arithmetic, layout and block primitives.
+// TOD_K4X_ABLATE / TOD_K4X_COUNT_WALKS are diagnostics builds (tools/k4x_ablate.sh, tools/k4x_walks.sh). The radius bound restates
+// DescriptorMatcher.cpp:212-220. Included by match.hip inside its anonymous namespace, after match_keys.h and match_fp4.h.
+// A lane keeps its k best keys in registers exactly as K4 does, and the threshold of its block test follows the list's k-th entry.
+// Bounds are exchanged between tiles through the same per-query word as K4 (loaded one period ahead, so the latency of the load is
+// never waited for). Output = K4's partial-key layout.
 // The test of one accumulator block: nothing to do unless some lane's best dot product beats its threshold (rare: the
 // thresholds follow the k-th best distance found so far, anywhere in the DB); then walk the block's 16 rows. MASK: rows at
-// or beyond n_lim do not exist (the last, partial step of the DB). IMAX: thresholds are >= 0 (radius < 128; they only rise),
-// so the 16-way maximum may be taken on the raw bits as integers -- among non-negative floats the order is the same, and a
-// negative dot product can never beat a non-negative threshold -- which spares the float maximum's NaN-quieting moves.
+// or beyond n_lim do not exist (the last, partial step of the DB). IMAX: thresholds are >= 0 (block_reaches).
 #ifdef TOD_K4X_COUNT_WALKS                                   // diagnostics build only (tools/k4x_walks.sh): blocks tested / blocks that walked
 __device__ unsigned long long g_k4x_blocks[2];
 #endif
@@ -71,29 +18,14 @@ __device__ __forceinline__ void mfma_block_test(const mfma_f32x16& acc, float& t
   if (!MASK && (threadIdx.x & 63u) == 0u) atomicAdd(&g_k4x_blocks[0], 1ull);
 #endif
   if (!MASK) {
-    bool any;
-    if (IMAX) {                                            // (a tree: see mfma_block_test_part)
-      int g[5];
-#pragma unroll
-      for (int j = 0; j < 5; ++j) g[j] = max(max(__float_as_int(acc[3 * j]), __float_as_int(acc[3 * j + 1])), __float_as_int(acc[3 * j + 2]));
-      const int m = max(max(max(g[0], g[1]), g[2]), max(max(g[3], g[4]), __float_as_int(acc[15])));
-      any = m > __float_as_int(thr);
-    } else {
-      float m = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
-#pragma unroll
-      for (int i = 3; i < 15; i += 2) m = fmaxf(fmaxf(m, acc[i]), acc[i + 1]);
-      m = fmaxf(m, acc[15]);
-      any = m > thr;
-    }
-    if (__builtin_amdgcn_ballot_w64(any) == 0ull) return;
+    if (__builtin_amdgcn_ballot_w64(block_reaches<IMAX, false>(acc, thr)) == 0ull) return;
 #ifdef TOD_K4X_COUNT_WALKS
     if ((threadIdx.x & 63u) == 0u) atomicAdd(&g_k4x_blocks[1], 1ull);
 #endif
   }
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    // the block's row i = r_lane | ((i & 3) + 8 (i >> 2)): r_lane = 32 step + 4 (lane >> 5) leaves bits 0, 1, 3, 4 free
-    const uint32_t ri = (uint32_t)((i & 3) + 8 * (i >> 2));
+    const uint32_t ri = block_row(i);                      // r_lane = lane_row_base(step): r_lane | ri is the tile-local row
     const bool hit = MASK ? (acc[i] > thr && (r_lane | ri) < n_lim) : (acc[i] > thr);
     if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {
       // key = distance << 22 | row: (256 - dot) * 2^21 is an exact integer below 2^31. A stale (looser) threshold only
@@ -105,15 +37,7 @@ __device__ __forceinline__ void mfma_block_test(const mfma_f32x16& acc, float& t
   thr = fmaxf(thr, thr_of_limit(best[K - 1] >> kLocalBits));       // thresholds only ever tighten
 }
 
-// The same in two parts: the first SPLIT (2 or 3) of the block's 4 MFMAs, the rest behind a test (mfma_block_test_part)
-template <int SPLIT>
-__device__ __forceinline__ mfma_f32x16 dot_part0(const Fp4Row& a, const Fp4Row& b) {
-  mfma_f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < SPLIT; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[s], b.s[s], acc, 4, 4, 0, 0, 0, 0);
-  return acc;
-}
-// Partial-distance elimination on the matrix cores (K4's idea, a block at a time): after P = 64 SPLIT of the 256 bit positions the
+// The same in two parts (dot_part0, then the rest behind this test). Partial-distance elimination on the matrix cores (K4's idea, a block at a time): after P = 64 SPLIT of the 256 bit positions the
 // accumulator holds P - 2 dP with dP <= d, so a pair whose partial dot product is not above thr - (256 - P) (dP >= limit) cannot
 // be a hit whatever the other positions say -- exact for any data. On independent bits d128 of a non-match is 64 +- 5.7 and
 // the radius 35: one block in five thousand goes on to its other two MFMAs (SPLIT 2). Real rBRIEF bits are biased and correlated
@@ -123,18 +47,11 @@ __device__ __forceinline__ mfma_f32x16 dot_part0(const Fp4Row& a, const Fp4Row& 
 template <int K, int SPLIT>
 __device__ __forceinline__ bool mfma_block_test_part(mfma_f32x16& acc, const Fp4Row& rows, const Fp4Row& q, float& thr, float& thrp,
                                                      uint32_t r_lane, uint32_t n_lim, uint32_t (&best)[K]) {
-  // the 16-way maximum as a tree (5 independent max3, then 2 + 1): in this form the kernel is bound by vector issue, not by the matrix
-  // pipe (tools/mfma_valu_overlap.hip: 2 MFMAs + chain + expansion 113 cycles per block and SIMD, + tree 103), and the tree's
-  // independent operations fill the issue slots a chain leaves to its own latency. The part thresholds (thrp = thr - 64 (4 - SPLIT))
-  // live in registers of their own beside the whole ones: one instruction less per block (1.82 -> 1.73 ms in the pipeline) for six
-  // registers, 218 -> 224, still inside the budget that lets the other stages' kernels start beside the matcher's waves
-  // (launch_topk_mfma; tests/test_build_checks.py holds the line). Keeping ONLY the part form -- no extra registers on paper -- made
-  // hipcc allocate 243.
-  int g[5];
-#pragma unroll
-  for (int j = 0; j < 5; ++j) g[j] = max(max(__float_as_int(acc[3 * j]), __float_as_int(acc[3 * j + 1])), __float_as_int(acc[3 * j + 2]));
-  const int m = max(max(max(g[0], g[1]), g[2]), max(max(g[3], g[4]), __float_as_int(acc[15])));
-  if (__builtin_amdgcn_ballot_w64(m > __float_as_int(thrp)) == 0ull) return false;
+  // The part thresholds (thrp = thr - 64 (4 - SPLIT)) live in registers of their own beside the whole ones: one instruction less
+  // per block (1.82 -> 1.73 ms in the pipeline) for six registers, 218 -> 224, still inside the budget that lets the other stages'
+  // kernels start beside the matcher's waves (launch_topk_mfma; tests/test_build_checks.py holds the line). Keeping ONLY the part
+  // form -- no extra registers on paper -- made hipcc allocate 243.
+  if (__builtin_amdgcn_ballot_w64(block_reaches<true, false>(acc, thrp)) == 0ull) return false;
 #pragma unroll
   for (int s = SPLIT; s < 4; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(rows.s[s], q.s[s], acc, 4, 4, 0, 0, 0, 0);
   mfma_block_test<K, false, true>(acc, thr, r_lane, n_lim, best);
@@ -220,15 +137,12 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_mfma(const uint32_t* _
   const uint32_t q0 = qw * (32u * QT);
 
   const Fp4Consts kc = fp4_consts();
-  // query blocks beyond nq repeat the last query: their results are never stored
   Fp4Row qb[QT];
   uint32_t best[QT][K];
   float thr[QT], thrp[QT];                                         // thrp: the part thresholds of the split blocks (mfma_block_test_part)
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
-    const uint32_t qi = q0 + 32u * t + c;
-    const uint4 p = *reinterpret_cast<const uint4*>(q + (size_t)(qi < nq ? qi : nq - 1u) * kWords + 4u * h);
-    expand_row(p, qb[t], kc);
+    load_query_block(q, q0 + 32u * t + c, nq, h, qb[t], kc);
 #pragma unroll
     for (int j = 0; j < K; ++j) best[t][j] = 0xFFFFFFFFu;
     // cut = radius + 1: a row beyond the radius is dropped by the truncation (DescriptorMatcher.cpp:212-220) whatever its rank
@@ -240,20 +154,15 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_mfma(const uint32_t* _
   const uint32_t row_end = min(n_rows, row0 + rows_per_tile);
   const uint32_t n_local = row_end - row0;                          // > 0: tile < n_tiles
   const uint32_t n_full = n_local / 32u, n_steps = (n_local + 31u) / 32u;   // the DB's last step may be partial
-  // this lane's 16 bytes of DB row (row0 + 32 step + c). No per-lane clamp: the DB's last step may reach up to 31 rows past its end
-  // -- into the slack todhip_db_load leaves behind the descriptors (kDbSlackBytes), rows that are masked, never used -- and the
-  // address stays a wave-uniform base plus a constant lane offset (no vector instruction per load: the kernel is bound by those)
-  const uint32_t lane_off = (c * kWords + 4u * h) * 4u;              // bytes from the step's first row
-  auto load_step = [&](uint32_t step) -> uint4 {
-    const uint32_t first = row0 + 32u * min(step, n_steps - 1u);    // wave-uniform
+  const StepLoader rows(db, row0, n_steps, c, h);
 #if defined(TOD_K4X_ABLATE) && TOD_K4X_ABLATE == 1           // diagnostics build only (tools/k4x_ablate.sh): no DB loads
-    const uint32_t r = first + c;
+  auto load_step = [&](uint32_t step) -> uint4 {
+    const uint32_t r = rows.first_row(step) + c;
     return uint4{r * 2654435761u, r ^ step, r + h, r * 40503u};
-#else
-    const char* base = reinterpret_cast<const char*>(db) + (size_t)first * (kWords * 4u);
-    return *reinterpret_cast<const uint4*>(base + lane_off);
-#endif
   };
+#else
+  const StepLoader& load_step = rows;
+#endif
   Fp4Row a0, a1;
   {
     const uint4 p = load_step(0);
@@ -263,7 +172,7 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_mfma(const uint32_t* _
   uint4 pa = load_step(1), pb = PF2 ? load_step(2) : pa;
   mfma_f32x16 acc_even, acc_odd;                                    // acc_odd: pending block of the previous step -- none yet
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc_odd[i] = -4096.f;                      // below every threshold (256 - 2 * 1023 at the least)
+  for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
   uint32_t seen[QT];
 #pragma unroll
   for (int t = 0; t < QT; ++t) seen[t] = 0xFFFFFFFFu;              // "nothing published"
@@ -277,14 +186,14 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_mfma(const uint32_t* _
   uint32_t n_pass = 0;
   for (; step + 2u <= n_full; step += 2u) {
     // two steps per trip: the expanded rows ping-pong between a0 and a1, the packed ones between pa and pb
-    n_pass += mfma_step<K, QT, false, IMAX, HALF>(a0, a1, pa, qb, thr, thrp, best, acc_even, acc_odd, 32u * step + 4u * h, n_local, kc);
+    n_pass += mfma_step<K, QT, false, IMAX, HALF>(a0, a1, pa, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local, kc);
     if (PF2) {
       pa = load_step(step + 3u);
-      n_pass += mfma_step<K, QT, false, IMAX, HALF>(a1, a0, pb, qb, thr, thrp, best, acc_even, acc_odd, 32u * step + 32u + 4u * h, n_local, kc);
+      n_pass += mfma_step<K, QT, false, IMAX, HALF>(a1, a0, pb, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, kc);
       pb = load_step(step + 4u);
     } else {
       pa = load_step(step + 2u);
-      n_pass += mfma_step<K, QT, false, IMAX, HALF>(a1, a0, pa, qb, thr, thrp, best, acc_even, acc_odd, 32u * step + 32u + 4u * h, n_local, kc);
+      n_pass += mfma_step<K, QT, false, IMAX, HALF>(a1, a0, pa, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, kc);
       pa = load_step(step + 3u);
     }
     if (step + 2u >= next_share) {                                  // wave-uniform
@@ -306,18 +215,18 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_mfma(const uint32_t* _
   // the last unmasked step's last block is still a half: it completes here, with that step's rows (a1: the second step of the
   // loop's last trip ran on them) -- the masked steps and the drain below work on whole blocks
   if (HALF && step > 0u) {
-    n_pass += mfma_block_test_part<K, HALF ? HALF : 2>(acc_odd, a1, qb[QT - 1], thr[QT - 1], thrp[QT - 1], 32u * (step - 1u) + 4u * h, n_local, best[QT - 1]) ? 1u : 0u;
+    n_pass += mfma_block_test_part<K, HALF ? HALF : 2>(acc_odd, a1, qb[QT - 1], thr[QT - 1], thrp[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 1]) ? 1u : 0u;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc_odd[i] = -4096.f;
+    for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
     if (lane == 0 && half_stats) { atomicAdd(half_stats, n_pass); atomicAdd(half_stats + 1, step * (uint32_t)QT); }
   }
   // at most one full and one partial step are left: the masked form serves both
   for (; step < n_steps; ++step) {
-    mfma_step<K, QT, true, IMAX>(a0, a1, pa, qb, thr, thrp, best, acc_even, acc_odd, 32u * step + 4u * h, n_local, kc);
+    mfma_step<K, QT, true, IMAX>(a0, a1, pa, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local, kc);
     a0 = a1;
     pa = PF2 ? pb : load_step(step + 2u);
   }
-  mfma_block_test<K, true, IMAX>(acc_odd, thr[QT - 1], 32u * (n_steps - 1u) + 4u * h, n_local, best[QT - 1]);   // drain
+  mfma_block_test<K, true, IMAX>(acc_odd, thr[QT - 1], lane_row_base(n_steps - 1u, h), n_local, best[QT - 1]);   // drain
 
   // lanes l and l + 32 hold the two halves of a query's rows: merge the partner's list, then K4's output format
   // (partial keys + one flag byte per (tile, 64 queries); two query blocks share a flag, so both are stored when
@@ -363,10 +272,7 @@ __global__ __launch_bounds__(kBlock) void hamming_topk_mfma_q32(const uint32_t* 
   const uint32_t lane = threadIdx.x & 63u, c = lane & 31u, h = lane >> 5;
   const Fp4Consts kc = fp4_consts();
   Fp4Row qb;
-  {
-    const uint4 p = *reinterpret_cast<const uint4*>(q + (size_t)(c < nq ? c : nq - 1u) * kWords + 4u * h);
-    expand_row(p, qb, kc);
-  }
+  load_query_block(q, c, nq, h, qb, kc);
   uint32_t best[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) best[j] = 0xFFFFFFFFu;
@@ -382,23 +288,23 @@ __global__ __launch_bounds__(kBlock) void hamming_topk_mfma_q32(const uint32_t* 
   uint4 p0 = load_step(0), p1 = load_step(1), p2 = load_step(2), p3 = load_step(3);
   mfma_f32x16 acc_a, acc_b;                                          // acc_b: pending block of the previous step -- none yet
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc_b[i] = -4096.f;                        // below every threshold (256 - 2 * 1023 at the least)
+  for (int i = 0; i < 16; ++i) acc_b[i] = kNoBlock;
   uint32_t* my_bound = bound + (c < nq ? c : nq - 1u);
   uint32_t seen = 0xFFFFFFFFu, next_share = 2u, step = 0;
   for (; step + 4u <= n_full; step += 4u) {                          // four steps per trip: p0..p3 rotate by name, nothing is copied
     Fp4Row a;
     expand_row(p0, a, kc); p0 = load_step(step + 4u);
     acc_a = dot_block(a, qb);
-    mfma_block_test<K, false, IMAX>(acc_b, thr, 32u * step - 32u + 4u * h, n_local, best);
+    mfma_block_test<K, false, IMAX>(acc_b, thr, lane_row_base(step - 1u, h), n_local, best);
     expand_row(p1, a, kc); p1 = load_step(step + 5u);
     acc_b = dot_block(a, qb);
-    mfma_block_test<K, false, IMAX>(acc_a, thr, 32u * step + 4u * h, n_local, best);
+    mfma_block_test<K, false, IMAX>(acc_a, thr, lane_row_base(step, h), n_local, best);
     expand_row(p2, a, kc); p2 = load_step(step + 6u);
     acc_a = dot_block(a, qb);
-    mfma_block_test<K, false, IMAX>(acc_b, thr, 32u * step + 32u + 4u * h, n_local, best);
+    mfma_block_test<K, false, IMAX>(acc_b, thr, lane_row_base(step, h) + 32u, n_local, best);
     expand_row(p3, a, kc); p3 = load_step(step + 7u);
     acc_b = dot_block(a, qb);
-    mfma_block_test<K, false, IMAX>(acc_a, thr, 32u * step + 64u + 4u * h, n_local, best);
+    mfma_block_test<K, false, IMAX>(acc_a, thr, lane_row_base(step, h) + 64u, n_local, best);
     if (step + 4u >= next_share) {                                   // wave-uniform; as hamming_topk_mfma
       next_share += share_period;
       const uint32_t worst_d = best[K - 1] >> kLocalBits;
@@ -408,13 +314,13 @@ __global__ __launch_bounds__(kBlock) void hamming_topk_mfma_q32(const uint32_t* 
     }
   }
   // the pending block of the last full trip, then up to three full and one partial step, one at a time (masked form)
-  mfma_block_test<K, true, IMAX>(acc_b, thr, 32u * step - 32u + 4u * h, step ? n_local : 0u, best);
+  mfma_block_test<K, true, IMAX>(acc_b, thr, lane_row_base(step - 1u, h), step ? n_local : 0u, best);
   for (; step < n_steps; ++step) {
     Fp4Row a;
     expand_row(p0, a, kc);
     p0 = p1; p1 = p2; p2 = p3; p3 = load_step(step + 4u);
     acc_a = dot_block(a, qb);
-    mfma_block_test<K, true, IMAX>(acc_a, thr, 32u * step + 4u * h, n_local, best);
+    mfma_block_test<K, true, IMAX>(acc_a, thr, lane_row_base(step, h), n_local, best);
   }
   uint32_t other[K];
 #pragma unroll

@@ -5,8 +5,8 @@
 // (cv::DescriptorMatcher::radiusMatch).
 //
 //   R1 radius_collect_mfma   the DB pass. One wave = (DB tile, 32 QT queries), the distances of a 32 x 32 block on the matrix cores
-//                            in K4x's +-1 fp4 form (match_mfma.h: dot = 256 - 2 d, exact). No lists, no bounds: a block is tested
-//                            for "any dot >= 256 - 2 radius" (one 16-way maximum in the shadow of the next block's MFMAs) and only
+//                            in K4x's +-1 fp4 form (match_fp4.h: dot = 256 - 2 d, exact). No lists, no bounds: a block is tested
+//                            for "any dot >= 256 - 2 radius" (block_reaches, in the shadow of the next block's MFMAs) and only
 //                            a block with a hit walks its 16 registers. A pair inside the radius adds 1 to hist[q][d], takes a
 //                            position from the query's cursor and, while that is below the buffer's capacity C, stores its key
 //                            (d << 32 | searched row) there. The cursor ends as |R(q)|, whatever C is.
@@ -24,11 +24,12 @@
 #include <algorithm>
 
 #include "ctx.h"
+#include "row_ops.h"
 
 namespace {
 
 #include "match_keys.h"
-#include "match_mfma.h"
+#include "match_fp4.h"
 
 constexpr uint32_t kMaxPerQuery = 1024;
 constexpr uint32_t kMaxCap = 2048;                          // radius_capacity(kMaxPerQuery): R2's LDS image of one buffer (16 KB)
@@ -56,30 +57,15 @@ struct CollectOut {
   uint64_t* cand;
 };
 
-// The test of one accumulator block. thr = 256 - 2 min(radius, 256): dot >= thr <=> d <= radius. IMAX (radius < 128: thr > 0): the
-// maximum on the raw bits as integers, as mfma_block_test. The walk masks what the block test cannot: rows behind the tile's end
-// (n_local) and the padding queries behind nq (q_ok).
+// The test of one accumulator block. thr = 256 - 2 min(radius, 256): dot >= thr <=> d <= radius. IMAX: radius < 128, thr > 0. The
+// walk masks what the block test cannot: rows behind the tile's end (n_local) and the padding queries behind nq (q_ok).
 template <bool IMAX>
 __device__ __forceinline__ void radius_block_test(const mfma_f32x16& acc, float thr, uint32_t r_lane, uint32_t n_local, uint32_t row0,
                                                   uint32_t qi, bool q_ok, const CollectOut& o) {
-  bool any;
-  if (IMAX) {
-    int g[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) g[j] = max(max(__float_as_int(acc[3 * j]), __float_as_int(acc[3 * j + 1])), __float_as_int(acc[3 * j + 2]));
-    const int m = max(max(max(g[0], g[1]), g[2]), max(max(g[3], g[4]), __float_as_int(acc[15])));
-    any = m >= __float_as_int(thr);
-  } else {
-    float m = fmaxf(fmaxf(acc[0], acc[1]), acc[2]);
-#pragma unroll
-    for (int i = 3; i < 15; i += 2) m = fmaxf(fmaxf(m, acc[i]), acc[i + 1]);
-    m = fmaxf(m, acc[15]);
-    any = m >= thr;
-  }
-  if (__builtin_amdgcn_ballot_w64(any) == 0ull) return;
+  if (__builtin_amdgcn_ballot_w64(block_reaches<IMAX, true>(acc, thr)) == 0ull) return;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const uint32_t row = r_lane + (uint32_t)((i & 3) + 8 * (i >> 2));   // tile-local; r_lane = 32 step + 4 (lane >> 5)
+    const uint32_t row = r_lane + block_row(i);             // tile-local; r_lane = lane_row_base(step)
     const bool hit = acc[i] >= thr && row < n_local && q_ok;
     if (__builtin_amdgcn_ballot_w64(hit) == 0ull) continue;
     if (hit) {
@@ -105,34 +91,23 @@ __global__ __launch_bounds__(kBlock, 2) void radius_collect_mfma(const uint32_t*
   const uint32_t lane = threadIdx.x & 63u, c = lane & 31u, h = lane >> 5;
   const uint32_t q0 = qw * (32u * QT);
   const Fp4Consts kc = fp4_consts();
-  Fp4Row qb[QT];                                            // query blocks beyond nq repeat the last query: the walk masks them
+  Fp4Row qb[QT];
 #pragma unroll
-  for (int t = 0; t < QT; ++t) {
-    const uint32_t qi = q0 + 32u * t + c;
-    const uint4 p = *reinterpret_cast<const uint4*>(q + (size_t)(qi < nq ? qi : nq - 1u) * kWords + 4u * h);
-    expand_row(p, qb[t], kc);
-  }
+  for (int t = 0; t < QT; ++t) load_query_block(q, q0 + 32u * t + c, nq, h, qb[t], kc);
   const uint32_t row0 = tile * rows_per_tile;               // < n_rows: tile < n_tiles
   const uint32_t n_local = min(rows_per_tile, n_rows - row0);
   const uint32_t n_steps = (n_local + 31u) / 32u;
-  // this lane's 16 bytes of row (row0 + 32 step + c). The DB's last step may reach up to 31 rows past its end, into the slack behind
-  // the rows (kDbSlackBytes, also behind a view): rows the walk masks
-  const uint32_t lane_off = (c * kWords + 4u * h) * 4u;
-  auto load_step = [&](uint32_t step) -> uint4 {
-    const uint32_t first = row0 + 32u * min(step, n_steps - 1u);
-    const char* base = reinterpret_cast<const char*>(db) + (size_t)first * (kWords * 4u);
-    return *reinterpret_cast<const uint4*>(base + lane_off);
-  };
+  const StepLoader load_step(db, row0, n_steps, c, h);
   uint4 p = load_step(0);
   mfma_f32x16 acc_even, acc_odd;                            // acc_odd: the previous step's last block -- none yet
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc_odd[i] = -4096.f;        // below every threshold (-256 at the least)
+  for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
   const uint32_t q_last = q0 + 32u * (QT - 1) + c;
   for (uint32_t step = 0; step < n_steps; ++step) {
     Fp4Row a;
     expand_row(p, a, kc);
     p = load_step(step + 1u);
-    const uint32_t r_lane = 32u * step + 4u * h;
+    const uint32_t r_lane = lane_row_base(step, h);
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
       if (t & 1) acc_odd = dot_block(a, qb[t]); else acc_even = dot_block(a, qb[t]);
@@ -140,7 +115,7 @@ __global__ __launch_bounds__(kBlock, 2) void radius_collect_mfma(const uint32_t*
       else radius_block_test<IMAX>((t & 1) ? acc_even : acc_odd, thr, r_lane, n_local, row0, q0 + 32u * (t - 1) + c, q0 + 32u * (t - 1) + c < nq, o);
     }
   }
-  radius_block_test<IMAX>(acc_odd, thr, 32u * (n_steps - 1u) + 4u * h, n_local, row0, q_last, q_last < nq, o);
+  radius_block_test<IMAX>(acc_odd, thr, lane_row_base(n_steps - 1u, h), n_local, row0, q_last, q_last < nq, o);
 }
 
 // R2 (the comment at the head of the file). keys: the query's buffer, slots [min(n, C), C) still hold the fill value ~0.
@@ -206,8 +181,7 @@ __global__ __launch_bounds__(kBlock) void radius_select_kernel(const uint32_t* _
       dist[u] = 0xFFFFu;
       if (r < n_rows) {
         const uint4 a = rows[2 * (size_t)r], b = rows[2 * (size_t)r + 1];
-        dist[u] = (uint32_t)(__popc(a.x ^ qw[0]) + __popc(a.y ^ qw[1]) + __popc(a.z ^ qw[2]) + __popc(a.w ^ qw[3]) +
-                             __popc(b.x ^ qw[4]) + __popc(b.y ^ qw[5]) + __popc(b.z ^ qw[6]) + __popc(b.w ^ qw[7]));
+        dist[u] = hamming256(a, b, qw);
       }
     }
 #pragma unroll
@@ -260,11 +234,9 @@ template <int QT>
 void launch_collect(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, const CollectOut& o) {
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
   const uint32_t n_qw = (nq + 32u * QT - 1u) / (32u * QT);
-  // about 16 waves per CU (two rounds of the 8 that fit), tiles of whole 32-row steps and at least 256 rows
-  uint32_t n_tiles = std::max(1u, (uint32_t)ctx->n_cu * 16u / n_qw);
-  n_tiles = std::min(std::min(n_tiles, std::max(1u, n_rows / 256u)), 8192u);
-  const uint32_t rows_per_tile = (uint32_t)((((uint64_t)n_rows + n_tiles - 1u) / n_tiles + 31u) & ~31ull);
-  n_tiles = (uint32_t)(((uint64_t)n_rows + rows_per_tile - 1u) / rows_per_tile);
+  // about 16 waves per CU (two rounds of the 8 that fit), tiles of at least 256 rows
+  const uint32_t rows_per_tile = mfma_tile_rows(n_rows, (uint32_t)ctx->n_cu * 16u / n_qw, 256u, false);
+  const uint32_t n_tiles = (uint32_t)(((uint64_t)n_rows + rows_per_tile - 1u) / rows_per_tile);
   const uint32_t blocks = (n_tiles * n_qw + kWavesPerBlock - 1u) / kWavesPerBlock;
   const float thr = 256.f - 2.f * (float)std::min(radius, 256u);
   auto kern = radius < 128u ? radius_collect_mfma<QT, true> : radius_collect_mfma<QT, false>;
@@ -296,13 +268,13 @@ int radius_search(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t radius
   TOD_HIP(hipMemsetAsync(ws->cand.p, 0xFF, cand_bytes, ctx->stream));
   const CollectOut o{hist_stride, cap, ws->count.as<uint32_t>(), ws->count.as<uint32_t>() + nq, ws->cand.as<uint64_t>()};
   const uint32_t* q = reinterpret_cast<const uint32_t*>(d_q);
-  int slot = -1;                                            // todhip_set_kernel_timing: the DB pass between two events, as K4 / K4x
-  if (ctx->time_kernels) { int rc = tod_timing_begin(ctx, &slot); if (rc != TODHIP_OK) return rc; }
+  KernelTimer timer{ctx};                                   // the DB pass between two events, as K4 / K4x
+  if (int rc = timer.begin()) return rc;
   // query blocks per wave: two for a handful of queries, six (96 query registers beside no lists at all) for many frames' worth
   if (nq <= 64u) launch_collect<2>(ctx, q, nq, radius, o);
   else if (nq <= 1024u) launch_collect<4>(ctx, q, nq, radius, o);
   else launch_collect<6>(ctx, q, nq, radius, o);
-  if (slot >= 0) { int rc = tod_timing_end(ctx, slot); if (rc != TODHIP_OK) return rc; }
+  if (int rc = timer.end()) return rc;
   TOD_HIP(hipGetLastError());
   hipLaunchKernelGGL(radius_select_kernel, dim3(nq), dim3(kBlock), 0, ctx->stream, reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), q,
                      n_rows, radius, mpq, cap, hist_stride, o.cursor, o.hist, o.cand, d_counts, d_in_radius);
