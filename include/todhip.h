@@ -319,7 +319,9 @@ int todhip_verify_batch_device_depth(todhip_ctx*, uint32_t n_frames, const void*
                                      uint32_t* n_poses, uint32_t* pose_ptr, uint32_t* inlier_kp, uint32_t* n_inlier_kp);
 
 /* ---- stage A: ORB features (ecto_opencv FeatureDescriptor -> cv::ORB; detector.py:10,27) --------- */
-/* gray: H x W u8, row stride `stride`. Outputs up to n_features keypoints: kp_xy (x,y level-0 pixels),
+/* gray: H x W u8, row stride `stride` >= W: (H - 1) * stride + W bytes, nothing behind the last row's pixels is read (a region of
+ * a larger image). A pyramid level that rounds to fewer than 63 pixels either way yields nothing; an image without any other level
+ * returns 0 keypoints. Outputs up to n_features keypoints: kp_xy (x,y level-0 pixels),
  * kp_aux (size, angle_deg, response, octave) and 32-byte rBRIEF descriptors. *n_out: capacity in, count out.
  * pattern: 256 x 4 int8 (x0,y0,x1,y1) test pairs, or NULL for the built-in seeded pattern. */
 int todhip_orb(todhip_ctx*, const uint8_t* gray, uint32_t H, uint32_t W, uint32_t stride, uint32_t n_features,

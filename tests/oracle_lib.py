@@ -284,20 +284,37 @@ def verify_2d(kp_xy, K, row_ptr, matches, matches_xyz, spans_per_obj, min_inlier
 
 
 # ------------------------------------------------------------------------------------------ stage A
-def orb(gray, n_features=1000, n_levels=3, scale_factor=1.2, pattern=None, mask=None):
+def strided_rows(a, stride, W=None):
+    """(array, H, W) of a 2-D u8 array whose row pitch is `stride` bytes and whose first W columns (default: all) are the image;
+    nothing is copied, so a view of a buffer that ends with the last row's W pixels stays what it is."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2 or (a.shape[0] > 1 and a.strides[0] != stride) or a.strides[1] != 1:
+        raise ValueError("need a 2-D uint8 array of row pitch %d" % stride)
+    W = a.shape[1] if W is None else W
+    if not 0 < W <= min(a.shape[1], stride):
+        raise ValueError("W outside the rows")
+    return a, a.shape[0], W
+
+
+def orb(gray, n_features=1000, n_levels=3, scale_factor=1.2, pattern=None, mask=None, cap=None, stride=None, W=None):
     """oracle/orb_oracle.c. Returns kp_xy f32[n,2], aux f32[n,4] (size, angle, response, octave), desc u8[n,32],
-    lvl_xy i32[n,2] (integer position inside the level)."""
-    g = np.ascontiguousarray(gray, np.uint8)
-    H, W = g.shape
-    cap = n_features
-    kp = np.zeros((cap, 2), np.float32)
-    aux = np.zeros((cap, 4), np.float32)
-    desc = np.zeros((cap, 32), np.uint8)
-    lvl = np.zeros((cap, 2), np.int32)
+    lvl_xy i32[n,2] (integer position inside the level). cap: output capacity (default n_features). stride: gray is a 2-D array of
+    that row pitch whose first W columns are the image (the mask keeps pitch W)."""
+    if stride is None:
+        g = np.ascontiguousarray(gray, np.uint8)
+        H, W = g.shape
+        stride = W
+    else:
+        g, H, W = strided_rows(gray, stride, W)
+    cap = n_features if cap is None else cap
+    kp = np.zeros((max(cap, 1), 2), np.float32)
+    aux = np.zeros((max(cap, 1), 4), np.float32)
+    desc = np.zeros((max(cap, 1), 32), np.uint8)
+    lvl = np.zeros((max(cap, 1), 2), np.int32)
     pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
     mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
     n = lib().orb_detect_masked(_p(g, C.c_uint8), None if mk is None else _p(mk, C.c_uint8), C.c_uint32(H), C.c_uint32(W),
-                                C.c_uint32(W), C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor),
+                                C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor),
                                 None if pat is None else _p(pat, C.c_int8), C.c_uint32(cap), _p(kp, C.c_float),
                                 _p(aux, C.c_float), _p(desc, C.c_uint8), _p(lvl, C.c_int32))
     return kp[:n].copy(), aux[:n].copy(), desc[:n].copy(), lvl[:n].copy()

@@ -185,6 +185,17 @@ def _ids_in(ids):
     return _np_ptr(keep), int(a.size), keep
 
 
+def _strided_rows(a, stride, W=None):
+    """(array, H, W) of a 2-D u8 array whose row pitch is `stride` bytes and whose first W columns (default: all) are the image"""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2 or (a.shape[0] > 1 and a.strides[0] != stride) or a.strides[1] != 1:
+        raise ValueError("need a 2-D uint8 array of row pitch %d" % stride)
+    W = a.shape[1] if W is None else W
+    if not 0 < W <= min(a.shape[1], stride):
+        raise ValueError("W outside the rows")
+    return a, a.shape[0], W
+
+
 def _k9(K):
     return np.ascontiguousarray(K, np.float32).reshape(9)
 
@@ -543,17 +554,26 @@ class Context:
         return int(out[0]), int(out[1]), int(out[2])
 
     # ---------------------------------------------------------------- stage A
-    def orb(self, gray, n_features=1000, n_levels=3, scale_factor=1.2, pattern=None, mask=None):
-        g = np.ascontiguousarray(gray, np.uint8)
-        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-        H, W = g.shape
-        kp = np.zeros((n_features, 2), np.float32)
-        aux = np.zeros((n_features, 4), np.float32)
-        desc = np.zeros((n_features, 32), np.uint8)
-        n_out = C.c_uint32(n_features)
+    def orb(self, gray, n_features=1000, n_levels=3, scale_factor=1.2, pattern=None, mask=None, cap=None, stride=None, W=None):
+        """todhip_orb_masked. cap: output capacity (default n_features). stride: gray (and mask) are 2-D arrays of that row pitch in
+        bytes whose first W columns (default: all) are the image; they are passed as they are, not copied, so a view that ends with
+        the last row's W pixels is what the library gets."""
+        if stride is None:
+            g = np.ascontiguousarray(gray, np.uint8)
+            mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+            H, W = g.shape
+            stride = W
+        else:
+            g, H, W = _strided_rows(gray, stride, W)
+            mk = None if mask is None else _strided_rows(mask, stride, W)[0]
+        cap = n_features if cap is None else cap
+        kp = np.zeros((max(cap, 1), 2), np.float32)
+        aux = np.zeros((max(cap, 1), 4), np.float32)
+        desc = np.zeros((max(cap, 1), 32), np.uint8)
+        n_out = C.c_uint32(cap)
         pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
         rc = lib().todhip_orb_masked(self._h, _np_ptr(g), None if mk is None else _np_ptr(mk), C.c_uint32(H), C.c_uint32(W),
-                                     C.c_uint32(W), C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor),
+                                     C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor),
                                      None if pat is None else _np_ptr(pat), _np_ptr(kp), _np_ptr(aux), _np_ptr(desc),
                                      C.byref(n_out))
         _check(rc, "todhip_orb_masked")

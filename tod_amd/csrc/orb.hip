@@ -455,22 +455,57 @@ void features_per_level(uint32_t n_features, uint32_t n_levels, float scale_fact
   out[n_levels - 1] = rest > 0 ? (uint32_t)rest : 0u;
 }
 
+// what every form refuses before it touches the device or the caller's memory; (level, frame) pairs ride in a grid dimension
+int check_args(uint32_t F, uint32_t H, uint32_t W, uint32_t n_features, uint32_t n_levels, float scale_factor, uint32_t cap) {
+  if (n_levels == 0 || n_levels > (uint32_t)kMaxLevels || !(scale_factor > 1.f) || H < 8 || W < 8 || n_features == 0 || F == 0 ||
+      F > 65535u || (size_t)n_levels * F > 65535u)
+    return TODHIP_EINVAL;
+  return cap == 0 ? TODHIP_ECAPACITY : TODHIP_OK;
+}
+
+// the pyramid of one geometry: sizes, scales and how many keypoints each level is asked for. A level too small for a keypoint
+// (down to 0 x 0 pixels, where the scale has outgrown the image) stays in the table with want == 0. Returns the largest want.
+uint32_t level_table(uint32_t H, uint32_t W, uint32_t F, uint32_t n_features, uint32_t n_levels, float scale_factor, LevelTab* T) {
+  uint32_t per_level[kMaxLevels], want_max = 0;
+  features_per_level(n_features, n_levels, scale_factor, per_level);
+  std::memset(T, 0, sizeof(*T));
+  T->n_levels = n_levels; T->F = F;
+  for (uint32_t lvl = 0; lvl < n_levels; ++lvl) {
+    float scale = 1.f;
+    for (uint32_t i = 0; i < lvl; ++i) scale = scale * scale_factor;
+    const uint32_t w = (uint32_t)rintf((float)W / scale), h = (uint32_t)rintf((float)H / scale);
+    T->h[lvl] = h; T->w[lvl] = w; T->scale[lvl] = scale;
+    T->want[lvl] = (h <= 2u * kEdge || w <= 2u * kEdge) ? 0u : per_level[lvl];     // too small: the level count stays 0
+    want_max = std::max(want_max, T->want[lvl]);
+  }
+  return want_max;
+}
+
 // d_gray: F frames of H x W u8 on the device (row stride `stride`, frame stride gray_fs bytes). Results stay on the
 // device: frame f's keypoints at row f * cap of the three outputs; n_out[f] is read back.
 int orb_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uint8_t* d_mask, uint32_t F, uint32_t H, uint32_t W,
                uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
                float* d_kp_xy, float* d_kp_aux, uint8_t* d_desc, uint32_t cap, uint32_t* n_out) {
-  if (n_levels == 0 || n_levels > (uint32_t)kMaxLevels || scale_factor <= 1.f || H < 8 || W < 8 || n_features == 0 || F == 0 ||
-      F > 65535u)
-    return TODHIP_EINVAL;
-  if (cap == 0) return TODHIP_ECAPACITY;
+  if (const int bad = check_args(F, H, W, n_features, n_levels, scale_factor, cap)) return bad;
   OrbWs* ws = tod_ws<OrbWs>(ctx);
   hipStream_t st = ctx->stream;
   const size_t px = (size_t)H * W;
   const uint32_t cand_cap = (uint32_t)(px / 4 + 64);
   const uint32_t sel1_cap = 2u * n_features + 16u, sel2_cap = n_features + 16u;
   const size_t V = (size_t)n_levels * F;                    // virtual frames: (level, frame) pairs, level major
-  if (V > 65535u) return TODHIP_EINVAL;
+  LevelTab T;
+  const uint32_t want_max = level_table(H, W, F, n_features, n_levels, scale_factor, &T);
+  if (want_max == 0) {
+    // no level is large enough for a keypoint: nothing to launch (and no empty graph to capture), no keypoints, outputs untouched.
+    // The captured sequence of another geometry goes, so that ws->tab always describes what the next replay would run.
+    if (ws->graph_exec) { (void)hipGraphExecDestroy(ws->graph_exec); ws->graph_exec = nullptr; }
+    if (ws->graph) { (void)hipGraphDestroy(ws->graph); ws->graph = nullptr; }
+    ws->key = {};
+    ws->tab = T; ws->want_max = 0; ws->sel_fs = sel2_cap;
+    for (uint32_t f = 0; f < F; ++f) n_out[f] = 0;
+    TOD_HIP(hipStreamSynchronize(st));                     // as every return: a host form's copies of the caller's image are done
+    return TODHIP_OK;
+  }
   TOD_HIP(ws->pyr.reserve(V * px));
   TOD_HIP(ws->blur.reserve(V * px)); TOD_HIP(ws->tmp.reserve(V * px));
   TOD_HIP(ws->cand.reserve(V * cand_cap * sizeof(Cand)));
@@ -493,8 +528,6 @@ int orb_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uin
     TOD_HIP(hipMemcpyAsync(ws->pattern.p, hpat, 1024, hipMemcpyHostToDevice, st));
     TOD_HIP(hipStreamSynchronize(st));                   // hpat lives on this stack frame
   }
-  uint32_t per_level[kMaxLevels];
-  features_per_level(n_features, n_levels, scale_factor, per_level);
   uint32_t* d_small = ws->small.as<uint32_t>();           // per virtual frame: the level's control words (W_*)
   uint32_t* d_cnt = d_small + V * kCtlWords;              // per frame: [8 + l] = keypoints of level l
   uint32_t* d_totals = d_cnt + (size_t)F * kCtlWords;
@@ -519,49 +552,40 @@ int orb_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uin
     if (use_graph) TOD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     {
       // the pyramid first (level l from level l - 1), then every kernel once for all levels and frames
-      LevelTab T;
-      std::memset(&T, 0, sizeof(T));
-      T.n_levels = n_levels; T.F = F;
-      uint32_t ph = H, pw = W, want_max = 0;
       for (uint32_t lvl = 0; lvl < n_levels; ++lvl) {
-        float scale = 1.f;
-        for (uint32_t i = 0; i < lvl; ++i) scale = scale * scale_factor;
-        const uint32_t w = (uint32_t)rintf((float)W / scale), h = (uint32_t)rintf((float)H / scale);
+        const uint32_t h = T.h[lvl], w = T.w[lvl];
         uint8_t* img = ws->pyr.as<uint8_t>() + (size_t)lvl * F * px;
-        if (lvl > 0) {
-          hipLaunchKernelGGL(resize_kernel, dim3((h * w + 255u) / 256u, F), dim3(256), 0, st, img - (size_t)F * px, ph, pw, img, h, w, px);
-          ph = h; pw = w;
-        }
-        T.img[lvl] = img; T.h[lvl] = h; T.w[lvl] = w; T.scale[lvl] = scale;
-        T.want[lvl] = (h <= 2u * kEdge || w <= 2u * kEdge) ? 0u : per_level[lvl];     // too small: the level count stays 0
-        want_max = std::max(want_max, T.want[lvl]);
+        // a level of zero pixels has nothing to resize (an empty grid is no launch); the sizes only shrink, so no later level
+        // reads it, and with want == 0 no kernel looks at its image
+        if (lvl > 0 && h * w > 0u)
+          hipLaunchKernelGGL(resize_kernel, dim3((h * w + 255u) / 256u, F), dim3(256), 0, st, img - (size_t)F * px, T.h[lvl - 1],
+                             T.w[lvl - 1], img, h, w, px);
+        T.img[lvl] = img;
       }
       ws->tab = T; ws->want_max = want_max; ws->sel_fs = sel2_cap;
-      if (want_max > 0) {
-        const uint32_t Vg = (uint32_t)V;
-        hipLaunchKernelGGL(fast_nms_kernel, dim3((W + kNmsTileW - 1) / kNmsTileW, (H + kNmsTileH - 1) / kNmsTileH, Vg), dim3(256), 0, st,
-                           T, ws->cand.as<Cand>(), cand_cap, d_small, d_small + W_HIST, d_mask, H, W, px);
-        hipLaunchKernelGGL(fast_threshold_kernel, dim3(Vg), dim3(64), 0, st, T, d_small, cand_cap);
-        hipLaunchKernelGGL(split_kernel, dim3((cand_cap + 255u) / 256u, Vg), dim3(256), 0, st, T, ws->cand.as<Cand>(), d_small,
-                           ws->sel1.as<Cand>(), ws->eq.as<Cand>(), cand_cap, sel1_cap);
-        // ties at the threshold: the first need_eq of them in (y, x) order, placed behind the count(> T) sure ones
-        hipLaunchKernelGGL(rank_tiled_kernel, dim3((cand_cap + 255u) / 256u, Vg), dim3(256), 0, st, ws->eq.as<Cand>(), d_small + W_NEQ,
-                           d_small + W_NEED_EQ, 0u, 0, ws->sel1.as<Cand>(), d_small + W_NGT, (uint32_t*)nullptr, cand_cap, sel1_cap, 0u);
-        hipLaunchKernelGGL(harris_kernel, dim3((2u * want_max + 255u) / 256u, Vg), dim3(256), 0, st, T, ws->sel1.as<Cand>(),
-                           d_small + W_NSEL1, px, sel1_cap);
-        hipLaunchKernelGGL(rank_tiled_kernel, dim3((2u * want_max + 255u) / 256u, Vg), dim3(256), 0, st, ws->sel1.as<Cand>(),
-                           d_small + W_NSEL1, d_small + W_WANT, 0u, 1, ws->sel2.as<Cand>(), (const uint32_t*)nullptr, d_cnt + 8,
-                           sel1_cap, sel2_cap, F);
-        hipLaunchKernelGGL(blur_h_kernel, dim3(px_blocks, Vg), dim3(256), 0, st, T, ws->tmp.as<uint8_t>(), px);
-        hipLaunchKernelGGL(blur_v_kernel, dim3(px_blocks, Vg), dim3(256), 0, st, T, ws->tmp.as<uint8_t>(), ws->blur.as<uint8_t>(), px);
-        DescribeArgs D;
-        std::memset(&D, 0, sizeof(D));
-        disc_umax(D.umax);
-        D.blur = ws->blur.as<uint8_t>(); D.sel = ws->sel2.as<Cand>();
-        D.level_counts = d_cnt + 8; D.cap = cap; D.pattern = ws->pattern.as<int8_t>();
-        D.kp_xy = d_kp_xy; D.kp_aux = d_kp_aux; D.desc = d_desc; D.fs = px; D.sel_fs = sel2_cap;
-        hipLaunchKernelGGL(describe_kernel, dim3((want_max + 3u) / 4u, Vg), dim3(256), 0, st, T, D);
-      }
+      const uint32_t Vg = (uint32_t)V;
+      hipLaunchKernelGGL(fast_nms_kernel, dim3((W + kNmsTileW - 1) / kNmsTileW, (H + kNmsTileH - 1) / kNmsTileH, Vg), dim3(256), 0, st,
+                         T, ws->cand.as<Cand>(), cand_cap, d_small, d_small + W_HIST, d_mask, H, W, px);
+      hipLaunchKernelGGL(fast_threshold_kernel, dim3(Vg), dim3(64), 0, st, T, d_small, cand_cap);
+      hipLaunchKernelGGL(split_kernel, dim3((cand_cap + 255u) / 256u, Vg), dim3(256), 0, st, T, ws->cand.as<Cand>(), d_small,
+                         ws->sel1.as<Cand>(), ws->eq.as<Cand>(), cand_cap, sel1_cap);
+      // ties at the threshold: the first need_eq of them in (y, x) order, placed behind the count(> T) sure ones
+      hipLaunchKernelGGL(rank_tiled_kernel, dim3((cand_cap + 255u) / 256u, Vg), dim3(256), 0, st, ws->eq.as<Cand>(), d_small + W_NEQ,
+                         d_small + W_NEED_EQ, 0u, 0, ws->sel1.as<Cand>(), d_small + W_NGT, (uint32_t*)nullptr, cand_cap, sel1_cap, 0u);
+      hipLaunchKernelGGL(harris_kernel, dim3((2u * want_max + 255u) / 256u, Vg), dim3(256), 0, st, T, ws->sel1.as<Cand>(),
+                         d_small + W_NSEL1, px, sel1_cap);
+      hipLaunchKernelGGL(rank_tiled_kernel, dim3((2u * want_max + 255u) / 256u, Vg), dim3(256), 0, st, ws->sel1.as<Cand>(),
+                         d_small + W_NSEL1, d_small + W_WANT, 0u, 1, ws->sel2.as<Cand>(), (const uint32_t*)nullptr, d_cnt + 8,
+                         sel1_cap, sel2_cap, F);
+      hipLaunchKernelGGL(blur_h_kernel, dim3(px_blocks, Vg), dim3(256), 0, st, T, ws->tmp.as<uint8_t>(), px);
+      hipLaunchKernelGGL(blur_v_kernel, dim3(px_blocks, Vg), dim3(256), 0, st, T, ws->tmp.as<uint8_t>(), ws->blur.as<uint8_t>(), px);
+      DescribeArgs D;
+      std::memset(&D, 0, sizeof(D));
+      disc_umax(D.umax);
+      D.blur = ws->blur.as<uint8_t>(); D.sel = ws->sel2.as<Cand>();
+      D.level_counts = d_cnt + 8; D.cap = cap; D.pattern = ws->pattern.as<int8_t>();
+      D.kp_xy = d_kp_xy; D.kp_aux = d_kp_aux; D.desc = d_desc; D.fs = px; D.sel_fs = sel2_cap;
+      hipLaunchKernelGGL(describe_kernel, dim3((want_max + 3u) / 4u, Vg), dim3(256), 0, st, T, D);
     }
     if (use_graph) {
       hipGraph_t g = nullptr;
@@ -645,15 +669,20 @@ int todhip_orb_masked(todhip_ctx* ctx, const uint8_t* gray, const uint8_t* mask,
   OrbWs* ws = tod_ws<OrbWs>(ctx);
   const uint32_t cap = *n_out;
   *n_out = 0;
-  if (cap == 0) return TODHIP_ECAPACITY;
-  const size_t img_bytes = (size_t)H * stride;
+  if (const int bad = check_args(1, H, W, n_features, n_levels, scale_factor, cap)) return bad;   // before anything is read
+  // the image arrives with row pitch W: of a caller's wider rows only the W pixels are read (H x W with row stride `stride` ends
+  // with the last row's pixels, not with its pitch: a region of a larger image)
+  const size_t img_bytes = (size_t)H * W;
   TOD_HIP(ws->in_img.reserve(mask ? 2 * img_bytes : img_bytes));       // the mask rides behind the image
   // the outputs land in pinned host memory, written by the last kernel itself (56 B per keypoint over PCIe): no device-to-host
   // copies and no second synchronization behind orb_device's own
   TOD_HIP(ws->h_kp.reserve((size_t)cap * 56 + 64));
   float* const p_xy = ws->h_kp.as<float>(); float* const p_aux = p_xy + (size_t)cap * 2;
   uint8_t* const p_desc = reinterpret_cast<uint8_t*>(p_aux + (size_t)cap * 4);
-  TOD_HIP(hipMemcpyAsync(ws->in_img.p, gray, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (stride == W)
+    TOD_HIP(hipMemcpyAsync(ws->in_img.p, gray, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  else
+    TOD_HIP(hipMemcpy2DAsync(ws->in_img.p, W, gray, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
   const uint8_t* d_mask = nullptr;
   if (mask) {
     // orb_device reads the mask with row pitch W: repack rows when the caller's stride is larger
@@ -662,7 +691,7 @@ int todhip_orb_masked(todhip_ctx* ctx, const uint8_t* gray, const uint8_t* mask,
     d_mask = dm;
   }
   uint32_t n = 0;
-  const int rc = orb_device(ctx, ws->in_img.as<uint8_t>(), 0, d_mask, 1, H, W, stride, n_features, n_levels, scale_factor, pattern,
+  const int rc = orb_device(ctx, ws->in_img.as<uint8_t>(), 0, d_mask, 1, H, W, W, n_features, n_levels, scale_factor, pattern,
                             p_xy, p_aux, p_desc, cap, &n);           // (synchronizes the stream before it returns)
   if (rc != TODHIP_OK) return rc;
   if (n) {

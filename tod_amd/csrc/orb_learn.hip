@@ -248,15 +248,18 @@ int todhip_pattern_learn_add_view(todhip_ctx* ctx, todhip_pattern_learner* L, co
   if (!ctx || !L || !gray || stride < W || H == 0 || W == 0) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
   LearnWs* ws = tod_ws<LearnWs>(ctx);
-  const size_t img_bytes = (size_t)H * stride;
-  TOD_HIP(ws->in_img.reserve(img_bytes + (mask ? (size_t)H * W : 0)));   // the mask rides behind the image, rows packed to pitch W
-  TOD_HIP(hipMemcpyAsync(ws->in_img.p, gray, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  const size_t img_bytes = (size_t)H * W;                                // of the caller's rows only the W pixels are read
+  TOD_HIP(ws->in_img.reserve(mask ? 2 * img_bytes : img_bytes));         // the mask rides behind the image, both at row pitch W
+  if (stride == W)
+    TOD_HIP(hipMemcpyAsync(ws->in_img.p, gray, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  else
+    TOD_HIP(hipMemcpy2DAsync(ws->in_img.p, W, gray, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
   uint8_t* dm = nullptr;
   if (mask) {
     dm = ws->in_img.as<uint8_t>() + img_bytes;
     TOD_HIP(hipMemcpy2DAsync(dm, W, mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
   }
-  return todhip_pattern_learn_add_view_device(ctx, L, ws->in_img.p, dm, H, W, stride, n_features, n_levels, scale_factor, n_added);
+  return todhip_pattern_learn_add_view_device(ctx, L, ws->in_img.p, dm, H, W, W, n_features, n_levels, scale_factor, n_added);
 }
 
 int todhip_pattern_learn_responses(todhip_ctx* ctx, todhip_pattern_learner* L, uint32_t first, uint32_t count, uint32_t* words) {
