@@ -118,9 +118,22 @@ struct DescriptorMatcher
       throw std::runtime_error("todhip_set_lsh failed");
     }
   }
-  // DescriptorMatcher.cpp:60-129. `docs`: per object the "descriptors" (n x 32 CV_8U) and "points" attachments.
+  // DescriptorMatcher.cpp:60-129. `docs`: per object the "descriptors" (n x 32 or n x 64 CV_8U: ORB, or BRISK / FREAK / AKAZE padded
+  // to 64 -- one width for all objects) and "points" attachments. The reference hands any cv::Mat to its cv::DescriptorMatcher; here
+  // the width is taken from the documents and anything the library cannot search is refused by name, never read at another stride.
   struct ObjectModel { ObjectId id; cv::Mat descriptors, points; };
   void load_models(const std::vector<ObjectModel>& docs) {
+    int width = 0;                                                       // of the non-empty models; an empty one adopts it
+    for (size_t i = 0; i < docs.size(); ++i) {
+      const cv::Mat& d = docs[i].descriptors;
+      if (d.rows == 0) continue;
+      if (d.type() != CV_8U || (d.cols != 32 && d.cols != 64))
+        throw std::runtime_error("object " + docs[i].id + ": descriptors must be CV_8U with 32 or 64 columns");
+      if (width && d.cols != width)
+        throw std::runtime_error("object " + docs[i].id + ": descriptors of another width than the objects before it");
+      width = d.cols;
+    }
+    if (!width) width = 32;                                              // no rows at all: todhip_db_load loads an empty DB
     object_ids_.clear();
     std::vector<todhip_object> objs;
     keep_.clear();
@@ -137,8 +150,9 @@ struct DescriptorMatcher
       object_ids_.push_back(docs[i].id);
     }
     std::vector<float> spans(docs.size());
-    const int rc = todhip_db_load(ctx_, objs.data(), (uint32_t)objs.size(), 32, 0, 1, spans.data());
+    const int rc = todhip_db_load(ctx_, objs.data(), (uint32_t)objs.size(), (uint32_t)width, 0, 1, spans.data());
     if (rc != TODHIP_OK) throw std::runtime_error("todhip_db_load failed");
+    desc_cols_ = width;
     spans_.clear();
     for (size_t i = 0; i < docs.size(); ++i) spans_[docs[i].id] = spans[i];
     keep_.clear();
@@ -165,6 +179,8 @@ struct DescriptorMatcher
     std::vector<todhip_dmatch> flat((size_t)nq * k);
     std::vector<float> xyz((size_t)nq * k * 3);
     if (radius_) {                                                       // :202
+      if (desc_cols_ && nq && (descriptors.type() != CV_8U || descriptors.cols != desc_cols_))   // never read at the wrong stride
+        throw std::runtime_error("descriptors: CV_8U with the " + std::to_string(desc_cols_) + " columns of the loaded models expected");
       cv::Mat q = descriptors.isContinuous() ? descriptors : descriptors.clone();
       const int rc = todhip_match(ctx_, q.template ptr<uint8_t>(0), nq, k, radius_, row_ptr.data(), flat.data(), xyz.data());
       if (rc == TODHIP_ENODB) return ecto::OK;                           // "No descriptors loaded", :204-208
@@ -195,6 +211,7 @@ struct DescriptorMatcher
   todhip_ctx* ctx_ = nullptr;
   unsigned int radius_ = 0, ratio_ = 0;
   float lowe_ratio_ = 0.f;
+  int desc_cols_ = 0;                                                    // width of the loaded models (0: nothing loaded)
   std::vector<ObjectId> object_ids_;
   std::map<ObjectId, float> spans_;
   std::vector<cv::Mat> keep_;

@@ -119,6 +119,31 @@ int todhip_db_load_device(todhip_ctx*, const todhip_object* objs, uint32_t n_obj
                           uint32_t shard_rank, uint32_t shard_count, float* spans_out);
 int todhip_db_info(const todhip_ctx*, uint64_t* total_rows, uint64_t* shard_first_row, uint64_t* shard_rows,
                    uint32_t* n_objs);
+/* The desc_bytes of the resident DB (0 before the first load): what a query row of todhip_match* must measure. */
+int todhip_db_desc_bytes(const todhip_ctx*, uint32_t* desc_bytes);
+
+/* Descriptor widths. desc_bytes == 32: 256-bit binary rows (ORB / rBRIEF), Hamming. desc_bytes == 512: 128 x f32, L2
+ * (todhip_match_l2*, one device). desc_bytes == 64: 512-bit binary rows -- BRISK, FREAK, BRIEF-64 -- Hamming, any shard_count, host
+ * or device source. Anything else: TODHIP_EINVAL. A narrower binary descriptor (AKAZE's 61 bytes) is used by zero-padding rows AND
+ * queries to 64 bytes: the padding adds nothing to any distance.
+ * On a DB loaded with desc_bytes == 64, todhip_match, todhip_match_device and todhip_match_shard_device with
+ * todhip_merge_shards_device[_on] perform the same exact search as on a 32-byte DB, definition unchanged: Hamming distance over all
+ * 512 bits; the k <= 8 nearest rows in the order (distance ascending, global row ascending), truncated at the first
+ * distance > radius; (imgIdx, trainIdx) and the 3D point resolved as before; `distance` is the integer as a float, 0 ... 512;
+ * queries are nq x 64 bytes. radius >= 512 cuts nothing (pass >= 512 to todhip_match_shard_device for the plain top-k),
+ * radius == 0 stays TODHIP_EINVAL. todhip_set_ratio_test applies unchanged (the true two nearest rows, however far),
+ * todhip_db_select_objects too (the view then takes 64 bytes per selected row). The definition is oracle/tod_oracle.cpp
+ * orc_match_ratio(desc_bytes = 64).
+ * One engine serves every launch size at this width (the matrix cores, 8 instructions per 32 x 32 block, dot = 512 - 2 d, whole
+ * blocks): todhip_set_matcher_engine and todhip_set_matcher_block_split are accepted and have no effect, last_block_split reports
+ * 4, todhip_set_kernel_timing brackets the DB pass as on a 32-byte DB.
+ * What a 64-byte DB refuses or ignores:
+ *   todhip_match_radius[_device], todhip_match_l2[_device]   TODHIP_EINVAL.
+ *   the match calls while todhip_set_lsh is enabled          TODHIP_EINVAL before any device work (no index is built at this width).
+ *   todhip_set_db_bit_order                                  the mode may be set; the rows stay in identity order and the results
+ *                                                            are those of the definition.
+ *   todhip_pipeline_db_load[_device]                         TODHIP_EINVAL (the pipeline's ORB stage emits 32 bytes).
+ *   todhip_model_*                                           trained models stay 32 bytes per row. */
 
 /* Restrict every later match on this context to the rows of the listed objects (indices into the objs[] of the last
  * todhip_db_load[_device]); ids == NULL: all objects again (the state after a load). The list may be in any order and may
@@ -131,9 +156,9 @@ int todhip_db_info(const todhip_ctx*, uint64_t* total_rows, uint64_t* shard_firs
  * index in the full DB, and the u64 keys of the sharded form carry rows of the full DB -- so ranks that hold different parts of S
  * merge as before. The ratio test sees the two nearest SELECTED rows, the LSH mode indexes the selected rows, a bit order
  * (todhip_set_db_bit_order) stays the one the load computed. Spans, todhip_db_info, the model points and the verifier's
- * span-by-object-index input do not change. The selected rows of this context's shard are copied into a second buffer (32 bytes per
+ * span-by-object-index input do not change. The selected rows of this context's shard are copied into a second buffer (desc_bytes per
  * row beside the full DB; none while all objects are selected).
- * desc_bytes == 32 only: on a float DB (desc_bytes == 512) TODHIP_EINVAL. Without a DB TODHIP_ENODB. Synchronizes the context's
+ * Binary DBs only (desc_bytes == 32 or 64): on a float DB (desc_bytes == 512) TODHIP_EINVAL. Without a DB TODHIP_ENODB. Synchronizes the context's
  * stream, as todhip_db_load does; after TODHIP_EHIP all objects are selected. */
 int todhip_db_select_objects(todhip_ctx*, const uint32_t* ids, uint32_t n_ids);
 /* what is selected now: number of distinct selected objects, their rows in the whole DB and in this context's shard (any pointer
@@ -257,7 +282,7 @@ int todhip_merge_shards_device_on(todhip_ctx*, void* hip_stream, const void* d_k
  * d_matches_xyz[nq * max_per_query * 3], d_in_radius[nq] u32 (may be NULL); the slots behind counts[q] are not written, as
  * todhip_match_device leaves them.
  * TODHIP_EINVAL: a null context, query or output pointer, nq == 0, radius == 0, max_per_query == 0 or > 1024, a float DB
- * (desc_bytes == 512). TODHIP_ENODB without a DB. todhip_get_counters: last_nq, last_k = max_per_query, last_matches (host form);
+ * (desc_bytes == 512) or a 64-byte binary one. TODHIP_ENODB without a DB. todhip_get_counters: last_nq, last_k = max_per_query, last_matches (host form);
  * todhip_set_kernel_timing brackets the DB pass.
  * Workspace: a candidate buffer of nq * C * 8 bytes, C = 2 * max_per_query rounded up to a power of two, at least 64, plus
  * nq * (min(radius, 256) + 2) * 4 bytes of counters. A query with at most C rows inside the radius is answered from the one DB pass;

@@ -94,6 +94,7 @@ EXPORTS = [
     "todhip_pattern_learn_responses", "todhip_pattern_learn_free", "todhip_pipeline_set_pattern",
     "todhip_db_select_objects", "todhip_db_selection", "todhip_pipeline_select_objects",
     "todhip_match_radius", "todhip_match_radius_device",
+    "todhip_db_desc_bytes",
 ]
 
 MAX_PER_QUERY_LIMIT = 1024
@@ -156,6 +157,8 @@ def lib():
             L.todhip_match_radius.restype = C.c_int
             L.todhip_match_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
             L.todhip_match_radius_device.restype = C.c_int
+        if hasattr(L, "todhip_db_desc_bytes"):                        # (as above)
+            L.todhip_db_desc_bytes.argtypes, L.todhip_db_desc_bytes.restype = [C.c_void_p, C.c_void_p], C.c_int
         _lib = L
     return _lib
 
@@ -291,8 +294,9 @@ class Context:
 
     # ---------------------------------------------------------------- stage B
     def db_load(self, desc, pts, obj_off, shard_rank=0, shard_count=1):
-        """desc u8[N,32] (binary, Hamming) or f32[N,128] (float, L2), pts f32[N,3], obj_off u32[n_obj+1] (rows of object o
-        are obj_off[o]:obj_off[o+1])."""
+        """desc u8[N,32] (256-bit binary: ORB) or u8[N,64] (512-bit binary: BRISK, FREAK; AKAZE's 61 bytes zero-padded to 64), both
+        Hamming, or f32[N,128] (float, L2); pts f32[N,3], obj_off u32[n_obj+1] (rows of object o are obj_off[o]:obj_off[o+1]).
+        The width of desc is the DB's desc_bytes: the match calls take queries of that width."""
         desc = np.ascontiguousarray(desc, np.float32 if np.asarray(desc).dtype == np.float32 else np.uint8)
         pts = np.ascontiguousarray(pts, np.float32)
         obj_off = np.asarray(obj_off, np.int64)
@@ -330,6 +334,21 @@ class Context:
                "todhip_db_info")
         return dict(total_rows=tot.value, shard_first=first.value, shard_rows=rows.value, n_objs=nobj.value)
 
+    def desc_bytes(self):
+        """Bytes per row of the resident DB (32, 64 or 512; 0 before the first load): todhip_db_desc_bytes"""
+        b = C.c_uint32()
+        _check(lib().todhip_db_desc_bytes(self._h, C.byref(b)), "todhip_db_desc_bytes")
+        return b.value
+
+    def _query_rows(self, q_desc, what):
+        """q_desc as contiguous u8[nq, desc_bytes]. A query matrix of another width than a binary DB's is refused here with
+        TodError(EINVAL): the library sees a pointer and would read it at the DB's stride."""
+        q = np.ascontiguousarray(q_desc, np.uint8)
+        B = self.desc_bytes() if hasattr(lib(), "todhip_db_desc_bytes") else 0
+        if B in (32, 64) and q.ndim == 2 and q.shape[1] != B:
+            raise TodError(EINVAL, "%s (queries of shape %s against a DB of %d-byte descriptors)" % (what, q.shape, B))
+        return q
+
     def select_objects(self, ids):
         """Search only the rows of the listed objects (indices of the last db_load, any order, repeats allowed) from now on; None:
         all objects again, []: nothing. imgIdx and the sharded keys keep the numbering of the full DB (todhip_db_select_objects)."""
@@ -352,8 +371,10 @@ class Context:
         return row_ptr, m[:n].copy(), xyz[:n].copy()
 
     def match(self, q_desc, k, radius):
-        """Host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
-        return self._match_host(lib().todhip_match, "todhip_match", np.ascontiguousarray(q_desc, np.uint8), k, C.c_uint32(radius))
+        """Host-buffer form: q_desc u8[nq, 32] or u8[nq, 64] -- the query width must equal the DB's (desc_bytes(); TodError(EINVAL)
+        otherwise). On a 64-byte DB distances run 0 ... 512 and a radius >= 512 cuts nothing.
+        Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
+        return self._match_host(lib().todhip_match, "todhip_match", self._query_rows(q_desc, "todhip_match"), k, C.c_uint32(radius))
 
     def match_radius(self, q_desc, radius, max_per_query):
         """The true radius search, host-buffer form (todhip_match_radius): every searched row within `radius` bits, the nearest
@@ -383,7 +404,8 @@ class Context:
         _check(rc, "todhip_match_l2_device")
 
     def match_device(self, d_q, nq, k, radius, d_counts, d_matches, d_xyz):
-        """Device-pointer form (ints from tensor.data_ptr())."""
+        """Device-pointer form (ints from tensor.data_ptr()). d_q: nq rows of the DB's width, 32 or 64 bytes (desc_bytes()) -- the
+        query width must equal the DB's, and a pointer carries no shape: the caller answers for it."""
         rc = lib().todhip_match_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius),
                                        C.c_void_p(d_counts), C.c_void_p(d_matches), C.c_void_p(d_xyz))
         _check(rc, "todhip_match_device")
@@ -796,16 +818,17 @@ class Pipeline:
         return _Borrowed(lib().todhip_pipeline_matcher(self._h))
 
     def db_load(self, desc, pts, obj_off):
-        """As Context.db_load; returns the status."""
+        """As Context.db_load, for u8[N,32] only (the ORB stage emits 32 bytes: EINVAL for any other width); returns the status."""
         desc = np.ascontiguousarray(desc, np.uint8)
+        B = desc.shape[1] if desc.ndim == 2 else 32
         pts = np.ascontiguousarray(pts, np.float32)
         obj_off = np.asarray(obj_off, np.int64)
         n_obj = len(obj_off) - 1
         objs = (TodObject * max(n_obj, 1))()
         for o in range(n_obj):
             lo, hi = int(obj_off[o]), int(obj_off[o + 1])
-            objs[o].desc, objs[o].pts_xyz, objs[o].n = desc.ctypes.data + lo * 32, pts.ctypes.data + lo * 12, hi - lo
-        return lib().todhip_pipeline_db_load(self._h, objs, C.c_uint32(n_obj), C.c_uint32(32))
+            objs[o].desc, objs[o].pts_xyz, objs[o].n = desc.ctypes.data + lo * B, pts.ctypes.data + lo * 12, hi - lo
+        return lib().todhip_pipeline_db_load(self._h, objs, C.c_uint32(n_obj), C.c_uint32(B))
 
     def db_load_models(self, models):
         objs = (TodObject * len(models))()

@@ -143,6 +143,9 @@ int todhip_set_matcher_block_split(todhip_ctx* ctx, int split) {
   return TODHIP_OK;
 }
 
+// a 64-byte DB has no LSH index (lsh.hip builds none): its match calls refuse while todhip_set_lsh is on, before any device work
+static bool wide_db_with_lsh(const todhip_ctx* ctx) { return ctx->desc_bytes == 64 && tod_lsh_enabled(ctx); }
+
 int todhip_set_ratio_test(todhip_ctx* ctx, float ratio) {
   if (!ctx || !(ratio >= 0.f) || ratio > 1.f) return TODHIP_EINVAL;
   ctx->ratio = ratio;
@@ -191,8 +194,9 @@ __global__ __launch_bounds__(256) void spans_kernel(const float* __restrict__ pt
 static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_objs, uint32_t desc_bytes,
                         uint32_t shard_rank, uint32_t shard_count, float* spans_out, bool device_src) {
   if (!ctx || (!objs && n_objs) || shard_count == 0 || shard_rank >= shard_count) return TODHIP_EINVAL;
-  // 32: 256-bit binary descriptors (ORB), Hamming; 512: 128 x f32 (SIFT-like), L2 -- one device only
-  if (desc_bytes != 32 && !(desc_bytes == 512 && shard_count == 1)) return TODHIP_EINVAL;
+  // 32: 256-bit binary descriptors (ORB), 64: 512-bit ones (BRISK, FREAK; match_wide.hip), Hamming; 512: 128 x f32 (SIFT-like), L2 --
+  // one device only
+  if (desc_bytes != 32 && desc_bytes != 64 && !(desc_bytes == 512 && shard_count == 1)) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
   tod_view_reset(ctx);                                      // todhip_db_select_objects: a load selects all objects
   ctx->h_obj_off.assign(n_objs + 1, 0u);
@@ -296,6 +300,12 @@ int todhip_db_info(const todhip_ctx* ctx, uint64_t* total_rows, uint64_t* shard_
   return TODHIP_OK;
 }
 
+int todhip_db_desc_bytes(const todhip_ctx* ctx, uint32_t* desc_bytes) {
+  if (!ctx || !desc_bytes) return TODHIP_EINVAL;
+  *desc_bytes = ctx->desc_bytes;                            // 0 until a load has succeeded
+  return TODHIP_OK;
+}
+
 // stream nullptr: the context's
 static int merge_shards(todhip_ctx* ctx, hipStream_t stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k,
                         uint32_t radius, void* d_counts, void* d_matches, void* d_matches_xyz) {
@@ -313,6 +323,7 @@ int todhip_match_shard_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq
   if (!ctx || !d_q_desc || !d_keys || k == 0 || k > 8 || radius == 0) return TODHIP_EINVAL;
   if (ctx->ratio > 0.f && k < 2) return TODHIP_EINVAL;        // the ratio test needs every shard's two nearest
   if (ctx->total_rows == 0) return TODHIP_ENODB;
+  if (wide_db_with_lsh(ctx)) return TODHIP_EINVAL;
   return tod_match_shard_keys(ctx, d_q_desc, nq, k, radius, reinterpret_cast<uint64_t*>(d_keys));
 }
 
@@ -333,6 +344,7 @@ int todhip_match_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint
   if (k == 0 || k > 8 || radius == 0) return TODHIP_EINVAL;   // radius 0: DescriptorMatcher.cpp:237 is UB there
   if (ctx->total_rows == 0) return TODHIP_ENODB;
   if (ctx->shard_rows != ctx->total_rows) return TODHIP_EINVAL; // sharded DBs use the two-step form
+  if (wide_db_with_lsh(ctx)) return TODHIP_EINVAL;
   if (nq == 0) return TODHIP_OK;
   // single device: the stage-1 merge lists go straight into the finalize kernel (lists == "shards")
   const uint32_t k_in = (ctx->ratio > 0.f && k < 2) ? 2u : k;          // the ratio test looks at the two nearest
@@ -352,6 +364,7 @@ int todhip_match(todhip_ctx* ctx, const uint8_t* q_desc, uint32_t nq, uint32_t k
   if (!ctx || !row_ptr || (nq && (!q_desc || !matches || !matches_xyz))) return TODHIP_EINVAL;
   if (k == 0 || k > 8 || radius == 0) return TODHIP_EINVAL;
   if (ctx->total_rows == 0) return TODHIP_ENODB;
+  if (wide_db_with_lsh(ctx)) return TODHIP_EINVAL;
   if (nq == 0) { row_ptr[0] = 0; return TODHIP_OK; }
   TOD_HIP(hipSetDevice(ctx->device));
   const size_t nm = (size_t)nq * k;

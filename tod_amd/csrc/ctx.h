@@ -33,6 +33,8 @@
 
 // bytes todhip_db_load allocates behind the last descriptor row: hamming_topk_mfma loads whole 32-row steps without a per-lane clamp
 constexpr size_t kDbSlackBytes = 2048;
+// (and hamming_topk_wide, match_wide.hip: the last 32-row step of 64-byte rows reaches 31 rows behind the end -- it fits, only just)
+static_assert(31 * 64 <= kDbSlackBytes, "a 32-row step of the widest binary row must end inside the slack");
 
 // A buffer frees itself with its owner and is never copied (release() is for freeing early on purpose). Nothing that holds one may
 // have static storage duration: its destructor would call hipFree after the runtime has shut down.
@@ -195,6 +197,9 @@ struct KernelTimer {
 int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
                     uint32_t* n_lists);
 size_t tod_match_lists_bytes(uint32_t nq, uint32_t k);
+// match_wide.hip: tod_match_lists' contract on a 64-byte DB (tod_match_lists dispatches on ctx->desc_bytes)
+int tod_match_lists_wide(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
+                         uint32_t* n_lists);
 int tod_match_shard_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_keys);
 // k_in: entries per list; k_out: matches per query in the outputs (k_in > k_out only for the ratio test with k == 1)
 int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k_in, uint32_t k_out,

@@ -6,7 +6,7 @@
 // full DB, so everything downstream -- shard merge, ratio test, radius cut, object lookup, 3D gather, the verifier's spans -- reads
 // the numbering of the whole DB. Host-side tables: db_select.h.
 //
-//   DS1 gather_view_kernel   wave = 128 view rows (4 KB): one wave-uniform binary search of the segment table for the wave's first
+//   DS1 gather_view_kernel   wave = 128 view rows of 32 bytes or 64 of 64 bytes (4 KB): one wave-uniform binary search of the segment table for the wave's first
 //                            row, a per-lane walk forward from there (objects are mostly longer than a wave's rows: no step at
 //                            all), then lane = 16 bytes of a row, four loads in flight, four stores. Bound by HBM: every selected
 //                            row is read once and written once.
@@ -17,14 +17,16 @@
 
 namespace {
 
-constexpr uint32_t kGatherSteps = 4;                        // 32-row steps per wave
-constexpr uint32_t kGatherRows = 32u * kGatherSteps;
+constexpr uint32_t kGatherSteps = 4;                        // 1 KB steps per wave
 
-// src: the shard's rows as stored (row i of the shard = global row shard_first + i); dst: view_rows rows. Two lanes per row.
+// src: the shard's rows as stored (row i of the shard = global row shard_first + i); dst: view_rows rows. L lanes of 16 bytes per
+// row: two for 32-byte rows, four for 64-byte ones.
+template <uint32_t L>
 __global__ __launch_bounds__(256) void gather_view_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst,
                                                           const uint32_t* __restrict__ seg_view, const uint32_t* __restrict__ seg_global,
                                                           uint32_t n_segs, uint32_t view_rows, uint32_t shard_first) {
   const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6)), lane = threadIdx.x & 63u;
+  constexpr uint32_t kStepRows = 64u / L, kGatherRows = kStepRows * kGatherSteps;
   const uint32_t r0 = wave * kGatherRows;
   if (r0 >= view_rows) return;                               // whole waves leave together
   uint32_t lo = 0, hi = n_segs;                              // wave-uniform: the last segment whose first view row is <= r0
@@ -36,18 +38,18 @@ __global__ __launch_bounds__(256) void gather_view_kernel(const uint4* __restric
   uint4 v[kGatherSteps];
 #pragma unroll
   for (uint32_t g = 0; g < kGatherSteps; ++g) {
-    const uint32_t r = r0 + 32u * g + (lane >> 1);
+    const uint32_t r = r0 + kStepRows * g + lane / L;
     v[g] = uint4{0u, 0u, 0u, 0u};
     if (r < view_rows) {
       while (r >= seg_view[s + 1]) ++s;                      // ends: r < view_rows = seg_view[n_segs]
       const size_t row = (size_t)(seg_global[s] - shard_first) + (r - seg_view[s]);
-      v[g] = src[row * 2u + (lane & 1u)];
+      v[g] = src[row * L + lane % L];
     }
   }
 #pragma unroll
   for (uint32_t g = 0; g < kGatherSteps; ++g) {
-    const uint32_t r = r0 + 32u * g + (lane >> 1);
-    if (r < view_rows) dst[(size_t)r * 2u + (lane & 1u)] = v[g];
+    const uint32_t r = r0 + kStepRows * g + lane / L;
+    if (r < view_rows) dst[(size_t)r * L + lane % L] = v[g];
   }
 }
 
@@ -72,15 +74,16 @@ int build_view(todhip_ctx* ctx, const TodViewTables& t) {
   const uint32_t n_segs = t.n_segs(), rows = t.view_rows();
   if (rows == 0) return TODHIP_OK;                           // nothing to search: no launch ever reads the buffers
   TOD_HIP(ctx->view_tab.reserve((size_t)(2u * n_segs + 1u) * sizeof(uint32_t)));
-  TOD_HIP(ctx->view_desc.reserve((size_t)rows * 32u + kDbSlackBytes));
+  const uint32_t desc_bytes = ctx->desc_bytes;              // 32 or 64 (todhip_db_select_objects)
+  TOD_HIP(ctx->view_desc.reserve((size_t)rows * desc_bytes + kDbSlackBytes));
   uint32_t* const d_view = ctx->view_tab.as<uint32_t>();
   uint32_t* const d_global = d_view + n_segs + 1u;
   TOD_HIP(hipMemcpyAsync(d_view, t.seg_view.data(), (size_t)(n_segs + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   TOD_HIP(hipMemcpyAsync(d_global, t.seg_global.data(), (size_t)n_segs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-  // hamming_topk_mfma loads whole 32-row steps without a per-lane clamp: up to 31 rows behind the view's last one (match_mfma.h)
-  TOD_HIP(hipMemsetAsync(ctx->view_desc.as<uint8_t>() + (size_t)rows * 32u, 0, kDbSlackBytes, ctx->stream));
-  const uint32_t waves = (rows + kGatherRows - 1u) / kGatherRows;
-  hipLaunchKernelGGL(gather_view_kernel, dim3((waves + 3u) / 4u), dim3(256), 0, ctx->stream, ctx->db_desc.as<uint4>(), ctx->view_desc.as<uint4>(),
+  // hamming_topk_mfma and hamming_topk_wide load whole 32-row steps without a per-lane clamp: up to 31 rows behind the view's last one
+  TOD_HIP(hipMemsetAsync(ctx->view_desc.as<uint8_t>() + (size_t)rows * desc_bytes, 0, kDbSlackBytes, ctx->stream));
+  const uint32_t wave_rows = 1024u / desc_bytes * kGatherSteps, waves = (rows + wave_rows - 1u) / wave_rows;
+  hipLaunchKernelGGL(desc_bytes == 64 ? gather_view_kernel<4> : gather_view_kernel<2>, dim3((waves + 3u) / 4u), dim3(256), 0, ctx->stream, ctx->db_desc.as<uint4>(), ctx->view_desc.as<uint4>(),
                      d_view, d_global, n_segs, rows, (uint32_t)ctx->shard_first);
   TOD_HIP(hipGetLastError());
   TOD_HIP(hipStreamSynchronize(ctx->stream));                // (pageable sources: complete before t may go)
@@ -109,7 +112,7 @@ int tod_view_remap(todhip_ctx* ctx, uint64_t* d_keys, size_t n) {
 extern "C" int todhip_db_select_objects(todhip_ctx* ctx, const uint32_t* ids, uint32_t n_ids) {
   if (!ctx) return TODHIP_EINVAL;
   if (ctx->total_rows == 0) return TODHIP_ENODB;
-  if (ctx->desc_bytes != 32) return TODHIP_EINVAL;           // the float DB has no view
+  if (ctx->desc_bytes != 32 && ctx->desc_bytes != 64) return TODHIP_EINVAL;   // the float DB has no view
   TodViewTables t;
   if (ids && !tod_view_build(ids, n_ids, ctx->h_obj_off.data(), ctx->n_objs, ctx->shard_first, ctx->shard_rows, &t)) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));

@@ -105,6 +105,7 @@ static int match_lists_active(todhip_ctx* ctx, const void* d_q, uint32_t nq, uin
 // Per-query candidate lists of this shard: d_lists[n_lists][nq][k] (each ascending). n_lists <= kMergeGroups.
 int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
                     uint32_t* n_lists) {
+  if (ctx->desc_bytes == 64) return tod_match_lists_wide(ctx, d_q, nq, k, radius, d_lists, n_lists);   // 512-bit rows: match_wide.hip
   if (ctx->desc_bytes != 32) return TODHIP_EINVAL;
   if (ctx->bit_order_on) {                 // todhip_set_db_bit_order: the rows are stored in another bit order, the queries follow them
     int rc = tod_bit_order_queries(ctx, d_q, nq, &d_q);

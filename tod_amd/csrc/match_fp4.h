@@ -1,5 +1,6 @@
 // The matrix-core block primitives of the exact 256-bit Hamming searches, and no kernel: what hamming_topk_mfma, hamming_topk_mfma_q32
-// (match_mfma.h) and radius_collect_mfma (match_radius.hip) share. Included inside the anonymous namespace after match_keys.h.
+// (match_mfma.h) and radius_collect_mfma (match_radius.hip) share; at the end, their 512-bit forms for hamming_topk_wide (match_wide.hip).
+// Included inside the anonymous namespace after match_keys.h.
 // With every descriptor bit b written as the MX-fp4 (E2M1) value 1 - 2b, the dot product of two descriptors is 256 - 2 * hamming:
 // products are +-1, the f32 accumulator holds integers <= 256, so the result is EXACT. v_mfma_f32_32x32x64_f8f6f4 (fp4 x fp4, unit
 // scales) takes 64 bit positions of 32 DB rows x 32 queries per issue: 4 MFMAs = 1024 complete distances in 128 matrix-pipe cycles
@@ -97,5 +98,39 @@ struct StepLoader {
   __device__ __forceinline__ uint4 operator()(uint32_t step) const {
     const char* base = reinterpret_cast<const char*>(db) + (size_t)first_row(step) * (kWords * 4u);
     return *reinterpret_cast<const uint4*>(base + lane_off);
+  }
+};
+
+// ---- 512-bit rows (match_wide.hip: BRISK, FREAK, 64-byte descriptors). A row is two 256-bit halves in the layout above: lane l
+// loads the 16 bytes at word 4 (l >> 5) of the row and the 16 bytes at word 8 + 4 (l >> 5). 8 MFMAs per 32 x 32 block give
+// dot = 512 - 2 d, still exact in f32; the accumulator layout, block_row / lane_row_base, block_reaches and kNoBlock are unchanged
+// (the least threshold of a 10-bit limit is 512 - 2 * 1023).
+constexpr int kWordsWide = 16;
+struct Fp4Row2 { Fp4Row lo, hi; };
+__device__ __forceinline__ float thr_of_limit_wide(uint32_t limit) { return 512.f - 2.f * (float)limit; }   // dot > thr <=> d < limit
+// dot_block on top of what acc already holds
+__device__ __forceinline__ mfma_f32x16 dot_block_acc(mfma_f32x16 acc, const Fp4Row& a, const Fp4Row& b) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[s], b.s[s], acc, 4, 4, 0, 0, 0, 0);
+  return acc;
+}
+__device__ __forceinline__ mfma_f32x16 dot_block_wide(const Fp4Row2& a, const Fp4Row2& b) { return dot_block_acc(dot_block(a.lo, b.lo), a.hi, b.hi); }
+__device__ __forceinline__ void load_query_block_wide(const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, Fp4Row2& qb,
+                                                      const Fp4Consts& kc) {
+  const uint32_t* row = q + (size_t)(qi < nq ? qi : nq - 1u) * kWordsWide + 4u * h;
+  expand_row(*reinterpret_cast<const uint4*>(row), qb.lo, kc);
+  expand_row(*reinterpret_cast<const uint4*>(row + 8), qb.hi, kc);
+}
+// StepLoader for 64-byte rows: the same wave-uniform base plus constant lane offset, the same reliance on the slack behind the rows
+// (31 rows of 64 bytes: ctx.h holds kDbSlackBytes to that)
+struct StepLoaderWide {
+  const uint32_t* db;
+  uint32_t row0, n_steps, lane_off;
+  __device__ __forceinline__ StepLoaderWide(const uint32_t* d, uint32_t r0, uint32_t n, uint32_t c, uint32_t h)
+      : db(d), row0(r0), n_steps(n), lane_off((c * kWordsWide + 4u * h) * 4u) {}
+  __device__ __forceinline__ void operator()(uint32_t step, uint4& lo, uint4& hi) const {
+    const char* base = reinterpret_cast<const char*>(db) + (size_t)(row0 + 32u * min(step, n_steps - 1u)) * (kWordsWide * 4u) + lane_off;
+    lo = *reinterpret_cast<const uint4*>(base);
+    hi = *reinterpret_cast<const uint4*>(base + 32);
   }
 };

@@ -1,7 +1,7 @@
 // What both matcher engines and the merges share: the launch constants, the per-lane sorted list of partial keys (distance << 22 |
 // tile-local row; the merges widen them to distance << 32 | global row, the order (distance asc, global row asc) of decision D1) and
 // the pick over ascending lists of global keys, and the store of one kept match (object lookup, row_ops.h, and 3D gather,
-// DescriptorMatcher.cpp:231-244). Included by match.hip and match_radius.hip inside their anonymous namespaces, after ctx.h and row_ops.h.
+// DescriptorMatcher.cpp:231-244). Included by match.hip, match_radius.hip and match_wide.hip inside their anonymous namespaces, after ctx.h and row_ops.h.
 
 constexpr int kWords = 8;          // 256-bit descriptors (ORB / rBRIEF), 32 bytes per row
 constexpr int kGroupRows = 4;      // DB rows per SGPR group (two s_load_dwordx16)

@@ -1,7 +1,7 @@
 // Behind the DB pass of either engine: K4m, the per-tile lists merged into kMergeGroups lists of global keys (counting form and
 // wave form); K4s, the k smallest of a shard's lists; K4f, the merge of the shards' lists with the radius truncation
 // (DescriptorMatcher.cpp:212-220), the (imgIdx, trainIdx) lookup (:60-129) and the 3D gather (:231-244).
-// Included by match.hip inside its anonymous namespace, after match_keys.h.
+// Included by match.hip and match_wide.hip inside their anonymous namespaces, after match_keys.h.
 
 // K4m: thread (query, group) merges the tiles t = group, group + G, ... ; keys become
 // (distance << 32 | global_row), unique per row, so any merge order gives the same k smallest.
