@@ -230,6 +230,37 @@ def test_many_tiles_and_query_waves(dev, n, nq):
         c.close()
 
 
+def test_the_wide_pass_at_its_edges(dev):
+    """The step loop of the DB pass (block_step_loop, match_fp4.h) where it turns: DBs of 1, 31, 32, 33 and 65 rows (a partial step,
+    exactly one, one and a row, two and a row: the block carried from step to step and the drain), 1 / 33 / 65 / 129 queries (two query
+    blocks per wave up to 64 queries; beyond, four for k <= 3 and two from k = 4 on, a last wave of one query), k on both sides of
+    that switch, a radius that cuts and one that does not (every row comes back, ties by row). Bit for bit against the numpy
+    definition (match_wide_ref.match); most queries are rows with 0..80 flipped bits, every seventh is random. One context, reloaded
+    per DB size."""
+    c = capi.Context(0)
+    try:
+        for n in (1, 31, 32, 33, 65):
+            rng = np.random.Generator(np.random.PCG64(4000 + n))
+            desc = rng.integers(0, 256, (n, 64), dtype=np.uint8)
+            pts = rng.standard_normal((n, 3)).astype(np.float32)
+            off = np.array([0, n // 2, n], np.uint32)
+            q = rng.integers(0, 256, (129, 64), dtype=np.uint8)
+            for i in range(len(q)):
+                if i % 7 != 6:
+                    q[i] = W.flip(desc[int(rng.integers(0, n))], rng.choice(512, int(rng.integers(0, 81)), replace=False))
+            c.db_load(desc, pts, off)
+            for k in (1, 3, 4, 8):
+                for radius in (70, 512):
+                    want_all = W.match(desc, off, pts, q, k, radius)
+                    assert want_all[0][-1] > 0
+                    for nq in (1, 33, 65, 129):
+                        want = prefix(want_all, nq)
+                        same(c.match(q[:nq], k, radius), want, (n, nq, k, radius, "host"))
+                        same(dev.match(c, q[:nq], k, radius), want, (n, nq, k, radius, "device"))
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------------------------------------------- 5. shards and selections
 def shard_ctxs(d, n_shards):
     ctxs = []

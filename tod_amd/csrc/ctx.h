@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/todhip.h"
@@ -183,7 +184,7 @@ uint32_t tod_pack_csr(const uint32_t* counts, const todhip_dmatch* m, const floa
 // capi.hip: a stream of the given kind (todhip_stream_create), honouring the process's CU partition
 extern "C" hipError_t tod_stream_create(hipStream_t* out, int device, int kind);
 extern "C" uint32_t tod_cu_partition();                     // todhip_set_cu_partition's current value
-// match.hip (the launchers: match_launch.h)
+// match.hip (the launchers: match_launch.h, match_plan.h)
 int tod_timing_begin(todhip_ctx* ctx, int* slot);
 int tod_timing_end(todhip_ctx* ctx, int slot);
 int tod_timing_drain(todhip_ctx* ctx, uint64_t keep);
@@ -197,9 +198,24 @@ struct KernelTimer {
 int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
                     uint32_t* n_lists);
 size_t tod_match_lists_bytes(uint32_t nq, uint32_t k);
-// match_wide.hip: tod_match_lists' contract on a 64-byte DB (tod_match_lists dispatches on ctx->desc_bytes)
-int tod_match_lists_wide(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
-                         uint32_t* n_lists);
+// match_wide.hip: the search over the active rows of a 64-byte DB, tod_match_lists' step for that width (k in 1..8, at least one row)
+int tod_wide_lists_active(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
+                          uint32_t* n_lists);
+// The list length k of a search as a template argument: fn(std::integral_constant<int, K>) for k = K in 1..8, TODHIP_EINVAL otherwise
+template <typename Fn>
+int dispatch_k(uint32_t k, Fn fn) {
+  switch (k) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 5: return fn(std::integral_constant<int, 5>{});
+    case 6: return fn(std::integral_constant<int, 6>{});
+    case 7: return fn(std::integral_constant<int, 7>{});
+    case 8: return fn(std::integral_constant<int, 8>{});
+    default: return TODHIP_EINVAL;
+  }
+}
 int tod_match_shard_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_keys);
 // k_in: entries per list; k_out: matches per query in the outputs (k_in > k_out only for the ratio test with k == 1)
 int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k_in, uint32_t k_out,

@@ -225,17 +225,7 @@ int tod_lsh_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uin
   LshWs* ws = tod_ws<LshWs>(ctx);
   if (ws->built_rows != tod_db_n_rows(ctx)) return TODHIP_EINVAL;
   *n_lists = 1;
-  switch (k) {
-    case 1: return launch_query<1>(ctx, ws, d_q, nq, d_lists);
-    case 2: return launch_query<2>(ctx, ws, d_q, nq, d_lists);
-    case 3: return launch_query<3>(ctx, ws, d_q, nq, d_lists);
-    case 4: return launch_query<4>(ctx, ws, d_q, nq, d_lists);
-    case 5: return launch_query<5>(ctx, ws, d_q, nq, d_lists);
-    case 6: return launch_query<6>(ctx, ws, d_q, nq, d_lists);
-    case 7: return launch_query<7>(ctx, ws, d_q, nq, d_lists);
-    case 8: return launch_query<8>(ctx, ws, d_q, nq, d_lists);
-    default: return TODHIP_EINVAL;
-  }
+  return dispatch_k(k, [&](auto K) { return launch_query<decltype(K)::value>(ctx, ws, d_q, nq, d_lists); });
 }
 
 extern "C" int todhip_set_lsh(todhip_ctx* ctx, uint32_t n_tables, uint32_t key_size, uint32_t multi_probe_level) {

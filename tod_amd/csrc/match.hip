@@ -23,7 +23,8 @@
 // K4f finalize_kernel      per query: merge shard lists, radius cut, object lookup, 3D gather.
 // This file is the matcher's one translation unit: the engine choice, the timing ring and the tod_match_* entry points. The rest
 // is included below: match_keys.h (constants, sorted lists, the pick over lists), match_valu.h (K4), match_fp4.h + match_mfma.h (K4x: block
-// primitives, kernels), match_merge.h (K4m, K4s, K4f), match_launch.h (knobs, tiling plan, launchers); with ctx.h: match_split.h, KernelTimer.
+// primitives, kernels), match_merge.h (K4m, K4s, K4f), match_plan.h (tiling, workspaces, merge launch: shared with match_wide.hip),
+// match_launch.h (knobs, launchers); with ctx.h: match_tiles.h, match_split.h, KernelTimer, dispatch_k.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +40,7 @@ namespace {
 #include "match_fp4.h"
 #include "match_mfma.h"
 #include "match_merge.h"
+#include "match_plan.h"
 #include "match_launch.h"
 
 // 0: K4 on the VALU, 1: K4x on the matrix cores. todhip_set_matcher_engine() decides; while it says "auto" the
@@ -89,40 +91,28 @@ static int match_lists_active(todhip_ctx* ctx, const void* d_q, uint32_t nq, uin
   if (tod_lsh_enabled(ctx)) return tod_lsh_lists(ctx, d_q, nq, k, d_lists, n_lists);   // todhip_set_lsh: candidates from the index only
   if (ctx->ratio > 0.f) radius = 256u;   // the ratio test needs the true second neighbour, however far: no radius bound in the search
   const uint32_t* q = reinterpret_cast<const uint32_t*>(d_q);
-  switch (k) {
-    case 1: return launch_topk<1>(ctx, q, nq, radius, d_lists, n_lists);
-    case 2: return launch_topk<2>(ctx, q, nq, radius, d_lists, n_lists);
-    case 3: return launch_topk<3>(ctx, q, nq, radius, d_lists, n_lists);
-    case 4: return launch_topk<4>(ctx, q, nq, radius, d_lists, n_lists);
-    case 5: return launch_topk<5>(ctx, q, nq, radius, d_lists, n_lists);
-    case 6: return launch_topk<6>(ctx, q, nq, radius, d_lists, n_lists);
-    case 7: return launch_topk<7>(ctx, q, nq, radius, d_lists, n_lists);
-    case 8: return launch_topk<8>(ctx, q, nq, radius, d_lists, n_lists);
-    default: return TODHIP_EINVAL;
-  }
+  return dispatch_k(k, [&](auto K) { return launch_topk<decltype(K)::value>(ctx, q, nq, radius, d_lists, n_lists); });
 }
 
-// Per-query candidate lists of this shard: d_lists[n_lists][nq][k] (each ascending). n_lists <= kMergeGroups.
+// Per-query candidate lists of this shard, at either binary width: d_lists[n_lists][nq][k], each ascending, keys distance << 32 |
+// global row, padding ~0. n_lists <= kMergeGroups.
 int tod_match_lists(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists,
                     uint32_t* n_lists) {
-  if (ctx->desc_bytes == 64) return tod_match_lists_wide(ctx, d_q, nq, k, radius, d_lists, n_lists);   // 512-bit rows: match_wide.hip
-  if (ctx->desc_bytes != 32) return TODHIP_EINVAL;
-  if (ctx->bit_order_on) {                 // todhip_set_db_bit_order: the rows are stored in another bit order, the queries follow them
+  const bool wide = ctx->desc_bytes == 64;   // 512-bit rows: match_wide.hip. No bit order (db_bitorder.hip leaves those rows as loaded), no LSH index
+  if ((!wide && ctx->desc_bytes != 32) || k == 0 || k > 8 || nq == 0) return TODHIP_EINVAL;
+  if (wide && tod_lsh_enabled(ctx)) return TODHIP_EINVAL;
+  if (!wide && ctx->bit_order_on) {          // todhip_set_db_bit_order: the rows are stored in another bit order, the queries follow them
     int rc = tod_bit_order_queries(ctx, d_q, nq, &d_q);
     if (rc != TODHIP_OK) return rc;
   }
-  if (!ctx->sel_on) return match_lists_active(ctx, d_q, nq, k, radius, d_lists, n_lists);
-  // todhip_db_select_objects: the same search over the view. No selected row in this shard: no DB pass, one list of padding keys
-  // (what an empty shard contributes, tod_match_shard_keys); otherwise the lists' view rows become rows of the full DB.
-  if (k == 0 || k > 8) return TODHIP_EINVAL;
-  if (tod_db_n_rows(ctx) == 0) {
-    TOD_HIP(hipMemsetAsync(d_lists, 0xFF, (size_t)nq * k * sizeof(uint64_t), ctx->stream));
+  if (tod_db_n_rows(ctx) == 0) {             // no selected row in this shard: no DB pass, one list of padding keys (what an empty shard
+    TOD_HIP(hipMemsetAsync(d_lists, 0xFF, (size_t)nq * k * sizeof(uint64_t), ctx->stream));   // contributes, tod_match_shard_keys)
     *n_lists = 1;
     return TODHIP_OK;
   }
-  int rc = match_lists_active(ctx, d_q, nq, k, radius, d_lists, n_lists);
-  if (rc != TODHIP_OK) return rc;
-  return tod_view_remap(ctx, d_lists, (size_t)*n_lists * nq * k);
+  int rc = wide ? tod_wide_lists_active(ctx, d_q, nq, k, radius, d_lists, n_lists) : match_lists_active(ctx, d_q, nq, k, radius, d_lists, n_lists);
+  if (rc != TODHIP_OK || !ctx->sel_on) return rc;
+  return tod_view_remap(ctx, d_lists, (size_t)*n_lists * nq * k);   // todhip_db_select_objects: view rows -> rows of the full DB
 }
 
 size_t tod_match_lists_bytes(uint32_t nq, uint32_t k) { return (size_t)kMergeGroups * nq * k * sizeof(uint64_t); }

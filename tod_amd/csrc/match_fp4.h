@@ -1,6 +1,7 @@
-// The matrix-core block primitives of the exact 256-bit Hamming searches, and no kernel: what hamming_topk_mfma, hamming_topk_mfma_q32
-// (match_mfma.h) and radius_collect_mfma (match_radius.hip) share; at the end, their 512-bit forms for hamming_topk_wide (match_wide.hip).
-// Included inside the anonymous namespace after match_keys.h.
+// The matrix-core block primitives of the exact Hamming searches, and no kernel: what hamming_topk_mfma, hamming_topk_mfma_q32
+// (match_mfma.h), radius_collect_mfma (match_radius.hip) and hamming_topk_wide (match_wide.hip) share; at the end, the row widths
+// (RowBits: 256 and 512 bits) and the step loop of the last two (block_step_loop).
+// Included by match.hip, match_radius.hip and match_wide.hip inside their anonymous namespaces, after match_keys.h.
 // With every descriptor bit b written as the MX-fp4 (E2M1) value 1 - 2b, the dot product of two descriptors is 256 - 2 * hamming:
 // products are +-1, the f32 accumulator holds integers <= 256, so the result is EXACT. v_mfma_f32_32x32x64_f8f6f4 (fp4 x fp4, unit
 // scales) takes 64 bit positions of 32 DB rows x 32 queries per issue: 4 MFMAs = 1024 complete distances in 128 matrix-pipe cycles
@@ -77,60 +78,99 @@ __device__ __forceinline__ bool block_reaches(const mfma_f32x16& acc, float thr)
   return INCL ? m >= thr : m > thr;
 }
 
-// One resident query fragment: this lane's 16 bytes of query qi = the block's first + (lane & 31). Queries at or beyond nq repeat
-// the last one (padding: never stored). A block at a time: K4x sets up a block's list between two loads, and its code follows that.
+// One resident query fragment: this lane's 16 bytes of query qi = the block's first + (lane & 31), rows of ROW_WORDS words. Queries at
+// or beyond nq repeat the last one (padding: never stored). A block at a time: K4x sets up a block's list between two loads, and its
+// code follows that.
+template <int ROW_WORDS = kWords>
 __device__ __forceinline__ void load_query_block(const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, Fp4Row& qb,
                                                  const Fp4Consts& kc) {
-  const uint4 p = *reinterpret_cast<const uint4*>(q + (size_t)(qi < nq ? qi : nq - 1u) * kWords + 4u * h);
+  const uint4 p = *reinterpret_cast<const uint4*>(q + (size_t)(qi < nq ? qi : nq - 1u) * ROW_WORDS + 4u * h);
   expand_row(p, qb, kc);
 }
 
-// This lane's 16 packed bytes of row (row0 + 32 step + (lane & 31)), steps beyond the tile's last repeating the last. No per-lane
-// clamp: the DB's last step may reach up to 31 rows past its end -- into the slack todhip_db_load leaves behind the descriptors
-// (kDbSlackBytes, also behind a view), rows that the walks mask, never use -- and the address stays a wave-uniform base plus a
+// This lane's 16 packed bytes of row (row0 + 32 step + (lane & 31)), `behind` bytes further on for the later 256-bit parts of a wider
+// row; steps beyond the tile's last repeat the last. No per-lane clamp: the DB's last step may reach up to 31
+// rows past its end -- into the slack todhip_db_load leaves behind the descriptors (kDbSlackBytes, also behind a view; ctx.h holds
+// it to 31 rows of the widest row), rows that the walks mask, never use -- and the address stays a wave-uniform base plus a
 // constant lane offset (no vector instruction per load: the kernels are bound by those)
-struct StepLoader {
+template <int ROW_WORDS>
+struct StepLoaderT {
   const uint32_t* db;
   uint32_t row0, n_steps, lane_off;                          // lane_off: bytes from the step's first row
-  __device__ __forceinline__ StepLoader(const uint32_t* d, uint32_t r0, uint32_t n, uint32_t c, uint32_t h)
-      : db(d), row0(r0), n_steps(n), lane_off((c * kWords + 4u * h) * 4u) {}
+  __device__ __forceinline__ StepLoaderT(const uint32_t* d, uint32_t r0, uint32_t n, uint32_t c, uint32_t h)
+      : db(d), row0(r0), n_steps(n), lane_off((c * ROW_WORDS + 4u * h) * 4u) {}
   __device__ __forceinline__ uint32_t first_row(uint32_t step) const { return row0 + 32u * min(step, n_steps - 1u); }   // wave-uniform
-  __device__ __forceinline__ uint4 operator()(uint32_t step) const {
-    const char* base = reinterpret_cast<const char*>(db) + (size_t)first_row(step) * (kWords * 4u);
-    return *reinterpret_cast<const uint4*>(base + lane_off);
+  __device__ __forceinline__ uint4 operator()(uint32_t step, uint32_t behind = 0u) const {
+    const char* base = reinterpret_cast<const char*>(db) + (size_t)first_row(step) * (ROW_WORDS * 4u);
+    return *reinterpret_cast<const uint4*>(base + lane_off + behind);
+  }
+};
+using StepLoader = StepLoaderT<kWords>;
+
+// ---- Rows of BITS = 256 or 512 bits (ORB; BRISK, FREAK and the other 64-byte descriptors) for the passes that take the width as
+// a parameter. A wider row is 256-bit parts in the layout above: lane l holds the 16 bytes at word 8 part + 4 (l >> 5). A 32 x 32
+// block is 4 MFMAs per part, dot = BITS - 2 d, still exact in f32; the accumulator layout, block_row / lane_row_base, block_reaches
+// and kNoBlock do not depend on the width (the least threshold of a 10-bit limit is 512 - 2 * 1023).
+template <int BITS>
+struct RowBits {
+  static constexpr int kParts = BITS / 256, kRowWords = BITS / 32;
+  struct Frag { Fp4Row part[kParts]; };                      // a lane's expanded share of one row or query
+  struct Packed { uint4 part[kParts]; };                     // the same as loaded
+  using Loader = StepLoaderT<kRowWords>;
+  static __device__ __forceinline__ float thr_of_limit(uint32_t limit) { return (float)BITS - 2.f * (float)limit; }   // dot > thr <=> d < limit
+  static __device__ __forceinline__ Packed load_step(const Loader& rows, uint32_t step) {
+    Packed p;
+#pragma unroll
+    for (int i = 0; i < kParts; ++i) p.part[i] = rows(step, 32u * i);
+    return p;
+  }
+  static __device__ __forceinline__ void expand(const Packed& p, Frag& f, const Fp4Consts& kc) {
+#pragma unroll
+    for (int i = 0; i < kParts; ++i) expand_row(p.part[i], f.part[i], kc);
+  }
+  static __device__ __forceinline__ void load_query_block(const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, Frag& qb,
+                                                          const Fp4Consts& kc) {
+#pragma unroll
+    for (int i = 0; i < kParts; ++i) ::load_query_block<kRowWords>(q + 8 * i, qi, nq, h, qb.part[i], kc);
+  }
+  static __device__ __forceinline__ mfma_f32x16 dot(const Frag& a, const Frag& b) {
+    mfma_f32x16 acc = dot_block(a.part[0], b.part[0]);
+#pragma unroll
+    for (int i = 1; i < kParts; ++i)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.part[i].s[s], b.part[i].s[s], acc, 4, 4, 0, 0, 0, 0);
+    return acc;
   }
 };
 
-// ---- 512-bit rows (match_wide.hip: BRISK, FREAK, 64-byte descriptors). A row is two 256-bit halves in the layout above: lane l
-// loads the 16 bytes at word 4 (l >> 5) of the row and the 16 bytes at word 8 + 4 (l >> 5). 8 MFMAs per 32 x 32 block give
-// dot = 512 - 2 d, still exact in f32; the accumulator layout, block_row / lane_row_base, block_reaches and kNoBlock are unchanged
-// (the least threshold of a 10-bit limit is 512 - 2 * 1023).
-constexpr int kWordsWide = 16;
-struct Fp4Row2 { Fp4Row lo, hi; };
-__device__ __forceinline__ float thr_of_limit_wide(uint32_t limit) { return 512.f - 2.f * (float)limit; }   // dot > thr <=> d < limit
-// dot_block on top of what acc already holds
-__device__ __forceinline__ mfma_f32x16 dot_block_acc(mfma_f32x16 acc, const Fp4Row& a, const Fp4Row& b) {
+// The DB pass of one wave over its tile (rows row0 .. row0 + n_local of db) against QT resident query blocks: what R1
+// (match_radius.hip) and W1 (match_wide.hip) are around their tests. The packed rows of step s + 1 are loaded before step s is
+// expanded and multiplied; the test of block t - 1 sits behind the MFMAs of block t; the step's last block waits in acc_odd for
+// block 0 of the next step (QT is even) and the last step's is drained at the end.
+//   test(acc, t, r_lane)   the accumulator of query block t (a constant once unrolled) over the rows r_lane | block_row(i), tile-local
+//   after_step(step)       behind each step's blocks (W1: the exchange of bounds between tiles)
+template <typename W, int QT, typename Test, typename AfterStep>
+__device__ __forceinline__ void block_step_loop(const uint32_t* __restrict__ db, uint32_t row0, uint32_t n_local, uint32_t c, uint32_t h,
+                                                const typename W::Frag (&qb)[QT], const Fp4Consts& kc, Test test, AfterStep after_step) {
+  static_assert(QT % 2 == 0 && QT >= 2, "the pending block alternates between two accumulators");
+  const uint32_t n_steps = (n_local + 31u) / 32u;
+  const typename W::Loader rows(db, row0, n_steps, c, h);
+  typename W::Packed p = W::load_step(rows, 0);
+  mfma_f32x16 acc_even, acc_odd;                            // acc_odd: the previous step's last block -- none yet
 #pragma unroll
-  for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[s], b.s[s], acc, 4, 4, 0, 0, 0, 0);
-  return acc;
-}
-__device__ __forceinline__ mfma_f32x16 dot_block_wide(const Fp4Row2& a, const Fp4Row2& b) { return dot_block_acc(dot_block(a.lo, b.lo), a.hi, b.hi); }
-__device__ __forceinline__ void load_query_block_wide(const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, Fp4Row2& qb,
-                                                      const Fp4Consts& kc) {
-  const uint32_t* row = q + (size_t)(qi < nq ? qi : nq - 1u) * kWordsWide + 4u * h;
-  expand_row(*reinterpret_cast<const uint4*>(row), qb.lo, kc);
-  expand_row(*reinterpret_cast<const uint4*>(row + 8), qb.hi, kc);
-}
-// StepLoader for 64-byte rows: the same wave-uniform base plus constant lane offset, the same reliance on the slack behind the rows
-// (31 rows of 64 bytes: ctx.h holds kDbSlackBytes to that)
-struct StepLoaderWide {
-  const uint32_t* db;
-  uint32_t row0, n_steps, lane_off;
-  __device__ __forceinline__ StepLoaderWide(const uint32_t* d, uint32_t r0, uint32_t n, uint32_t c, uint32_t h)
-      : db(d), row0(r0), n_steps(n), lane_off((c * kWordsWide + 4u * h) * 4u) {}
-  __device__ __forceinline__ void operator()(uint32_t step, uint4& lo, uint4& hi) const {
-    const char* base = reinterpret_cast<const char*>(db) + (size_t)(row0 + 32u * min(step, n_steps - 1u)) * (kWordsWide * 4u) + lane_off;
-    lo = *reinterpret_cast<const uint4*>(base);
-    hi = *reinterpret_cast<const uint4*>(base + 32);
+  for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
+  for (uint32_t step = 0; step < n_steps; ++step) {
+    typename W::Frag a;
+    W::expand(p, a, kc);
+    p = W::load_step(rows, step + 1u);
+    const uint32_t r_lane = lane_row_base(step, h);
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      if (t & 1) acc_odd = W::dot(a, qb[t]); else acc_even = W::dot(a, qb[t]);
+      if (t == 0) test(acc_odd, QT - 1, r_lane - 32u);      // the previous step's last block
+      else test((t & 1) ? acc_even : acc_odd, t - 1, r_lane);
+    }
+    after_step(step);
   }
-};
+  test(acc_odd, QT - 1, lane_row_base(n_steps - 1u, h));    // drain
+}

@@ -1,7 +1,8 @@
-// Host planning of the matcher's launches: the environment knobs, the tiling plan, the workspace set-up, the
-// merge launch and the launchers of both engines. Each engine keeps its own, measured policy for how many tiles to ask for; what
-// follows that policy is shared. The k of the reference's knnMatch is DescriptorMatcher.cpp:211, its radius cut :212-220.
-// Included by match.hip inside its anonymous namespace, after match_keys.h, match_valu.h, match_fp4.h, match_mfma.h and match_merge.h.
+// Host planning of the 32-byte matcher's launches: the environment knobs and the launchers of both engines. Each engine keeps its
+// own, measured policy for how many tiles to ask for; what follows that policy is shared (match_plan.h: tiling, workspaces, merge
+// launch). The k of the reference's knnMatch is DescriptorMatcher.cpp:211, its radius cut :212-220.
+// Included by match.hip inside its anonymous namespace, after match_keys.h, match_valu.h, match_fp4.h, match_mfma.h, match_merge.h
+// and match_plan.h.
 
 int k4_engine(const todhip_ctx* ctx, uint32_t nq);   // match.hip, behind this header
 
@@ -24,56 +25,6 @@ inline const MatchEnv& match_env() {
                     num("TODHIP_K4X_SHARE", 16), num("TODHIP_K4X_QT", 0), num("TODHIP_K4X_HALF", -1), getenv("TODHIP_K4X_HALF_DEBUG") != nullptr};
   }();
   return env;
-}
-
-struct Tiling { uint32_t n_tiles, rows_per_tile, blocks_per_xcd, tiles_per_xcd, groups; };
-
-// The shared tail: rows_per_tile is the engine's choice, rounded to its granule. The tile count it really gives, the grid of
-// 4-wave blocks per XCD (whole tiles per XCD when there are 8 k of them: the kernels' work-item decode) and the merge fan-in. False: a tile
-// would not fit the partial key's row bits.
-inline bool finish_tiling(uint32_t n_rows, uint32_t rows_per_tile, uint32_t n_qw, Tiling* t) {
-  if (rows_per_tile > kLocalMask) return false;
-  t->rows_per_tile = rows_per_tile;
-  t->n_tiles = (n_rows + rows_per_tile - 1) / rows_per_tile;
-  const uint32_t items = t->n_tiles * n_qw;
-  const uint32_t blocks = (items + kWavesPerBlock - 1) / kWavesPerBlock;
-  t->blocks_per_xcd = (blocks + 7u) / 8u;
-  t->tiles_per_xcd = 0;
-  if (t->n_tiles >= 8 && t->n_tiles % 8u == 0) {
-    t->tiles_per_xcd = t->n_tiles / 8u;
-    t->blocks_per_xcd = (t->tiles_per_xcd * n_qw + kWavesPerBlock - 1) / kWavesPerBlock;
-  }
-  t->groups = std::min(t->n_tiles, (uint32_t)kMergeGroups);
-  return true;
-}
-
-// The partial lists (m_part) and, in one buffer under one memset, the per-query bound words (0xFFFFFFFF = none published) and the
-// per-(tile, 64 queries) flag bytes (0xFF = nothing stored). Returns the flags; nullptr: a HIP error, left in the context.
-template <int K>
-uint8_t* prepare_lists(todhip_ctx* ctx, uint32_t n_tiles, uint32_t nq_pad, uint32_t n_qw64) {
-  const size_t bound_bytes = (size_t)nq_pad * sizeof(uint32_t), flag_bytes = (size_t)n_tiles * n_qw64;
-  hipError_t e = ctx->m_part.reserve((size_t)n_tiles * K * nq_pad * sizeof(uint32_t));
-  if (e == hipSuccess) e = ctx->m_bound.reserve(bound_bytes + flag_bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(ctx->m_bound.p, 0xFF, bound_bytes + flag_bytes, ctx->stream);
-  if (e != hipSuccess) { ctx->last_hip_error = (int)e; return nullptr; }
-  return ctx->m_bound.as<uint8_t>() + bound_bytes;
-}
-
-// K4m behind a DB pass. wave: a handful of queries over thousands of tiles, a wave per (query, group). d_stats: the DB pass's
-// split-block counters, which the counting form carries to pinned memory (K4xSplit::take_report reads them there).
-template <int K>
-int launch_merge(todhip_ctx* ctx, uint32_t nq, uint32_t nq_pad, const Tiling& t, const uint8_t* d_stored, uint32_t n_qw64, bool wave,
-                 const uint32_t* d_stats, uint64_t* d_lists, uint32_t* n_lists) {
-  if (wave)
-    hipLaunchKernelGGL(merge_tiles_wave_kernel<K>, dim3((nq + kWavesPerBlock - 1) / kWavesPerBlock, t.groups), dim3(kBlock), 0, ctx->stream,
-                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, tod_db_first_row(ctx), t.groups, d_stored, n_qw64, d_lists);
-  else
-    hipLaunchKernelGGL(merge_tiles_kernel<K>, dim3((nq + kBlock - 1) / kBlock, t.groups), dim3(kBlock), 0, ctx->stream,
-                       ctx->m_part.as<uint32_t>(), nq, nq_pad, t.n_tiles, t.rows_per_tile, tod_db_first_row(ctx), t.groups, d_stored, n_qw64, d_lists,
-                       d_stats, d_stats ? ctx->k4x_stats_host.as<uint32_t>() : (uint32_t*)nullptr, d_stats ? ctx->k4x.seq_sent : 0u);
-  TOD_HIP(hipGetLastError());
-  *n_lists = t.groups;
-  return TODHIP_OK;
 }
 
 template <int K, int QT>
@@ -129,7 +80,8 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
                      ctx->m_bound.as<uint32_t>(), d_stored, d_stats ? d_stats + 2u * (split - 2u) : nullptr);
   if (int rc = timer.end()) return rc;
   if (d_stats) ++ctx->k4x.seq_sent;
-  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, nq <= 64u && !d_stats && t.n_tiles >= 256u, d_stats, d_lists, n_lists);
+  if (nq <= 64u && !d_stats && t.n_tiles >= 256u) return launch_merge_wave<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, d_lists, n_lists);
+  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, d_stats, d_lists, n_lists);
 }
 
 template <int K>
@@ -148,7 +100,7 @@ int launch_topk_mfma_q32(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint
                      reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw64, cut,
                      (uint32_t)std::max(4, match_env().k4x_share), ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
   if (int rc = timer.end()) return rc;
-  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, true, nullptr, d_lists, n_lists);
+  return launch_merge_wave<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, d_lists, n_lists);
 }
 
 template <int K>
@@ -221,5 +173,5 @@ int launch_topk(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radi
                      reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw,
                      t.blocks_per_xcd, t.tiles_per_xcd, cut, ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
   if (int rc = timer.end()) return rc;
-  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw, false, nullptr, d_lists, n_lists);
+  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw, nullptr, d_lists, n_lists);
 }

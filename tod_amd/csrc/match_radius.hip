@@ -78,44 +78,30 @@ __device__ __forceinline__ void radius_block_test(const mfma_f32x16& acc, float 
 }
 
 // R1. Work item = (tile, query wave), consecutive items share a tile (its rows come from L2 for all but the first reader). The
-// packed rows of step s + 1 are loaded before step s is expanded and multiplied; the test of block t - 1 sits behind the MFMAs of
-// block t, the step's last block waits in acc_odd for block 0 of the next step (QT is even), as in hamming_topk_mfma.
+// loop over the tile's steps is match_fp4.h's block_step_loop; the test of a block is radius_block_test, nothing happens between steps.
 template <int QT, bool IMAX>
 __global__ __launch_bounds__(kBlock, 2) void radius_collect_mfma(const uint32_t* __restrict__ db, const uint32_t* __restrict__ q,
                                                                  uint32_t n_rows, uint32_t nq, uint32_t rows_per_tile, uint32_t n_tiles,
                                                                  uint32_t n_qw, float thr, CollectOut o) {
-  static_assert(QT % 2 == 0 && QT >= 2, "the pending block alternates between two accumulators");
+  using W = RowBits<256>;
   const uint32_t item = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
   const uint32_t tile = item / n_qw, qw = item % n_qw;
   if (tile >= n_tiles) return;
   const uint32_t lane = threadIdx.x & 63u, c = lane & 31u, h = lane >> 5;
   const uint32_t q0 = qw * (32u * QT);
   const Fp4Consts kc = fp4_consts();
-  Fp4Row qb[QT];
+  W::Frag qb[QT];
 #pragma unroll
-  for (int t = 0; t < QT; ++t) load_query_block(q, q0 + 32u * t + c, nq, h, qb[t], kc);
+  for (int t = 0; t < QT; ++t) W::load_query_block(q, q0 + 32u * t + c, nq, h, qb[t], kc);
   const uint32_t row0 = tile * rows_per_tile;               // < n_rows: tile < n_tiles
   const uint32_t n_local = min(rows_per_tile, n_rows - row0);
-  const uint32_t n_steps = (n_local + 31u) / 32u;
-  const StepLoader load_step(db, row0, n_steps, c, h);
-  uint4 p = load_step(0);
-  mfma_f32x16 acc_even, acc_odd;                            // acc_odd: the previous step's last block -- none yet
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
-  const uint32_t q_last = q0 + 32u * (QT - 1) + c;
-  for (uint32_t step = 0; step < n_steps; ++step) {
-    Fp4Row a;
-    expand_row(p, a, kc);
-    p = load_step(step + 1u);
-    const uint32_t r_lane = lane_row_base(step, h);
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      if (t & 1) acc_odd = dot_block(a, qb[t]); else acc_even = dot_block(a, qb[t]);
-      if (t == 0) radius_block_test<IMAX>(acc_odd, thr, r_lane - 32u, n_local, row0, q_last, q_last < nq, o);
-      else radius_block_test<IMAX>((t & 1) ? acc_even : acc_odd, thr, r_lane, n_local, row0, q0 + 32u * (t - 1) + c, q0 + 32u * (t - 1) + c < nq, o);
-    }
-  }
-  radius_block_test<IMAX>(acc_odd, thr, lane_row_base(n_steps - 1u, h), n_local, row0, q_last, q_last < nq, o);
+  block_step_loop<W, QT>(
+      db, row0, n_local, c, h, qb, kc,
+      [&](const mfma_f32x16& acc, int t, uint32_t r_lane) {
+        const uint32_t qi = q0 + 32u * t + c;
+        radius_block_test<IMAX>(acc, thr, r_lane, n_local, row0, qi, qi < nq, o);
+      },
+      [](uint32_t) {});
 }
 
 // R2 (the comment at the head of the file). keys: the query's buffer, slots [min(n, C), C) still hold the fill value ~0.
@@ -235,13 +221,11 @@ void launch_collect(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t 
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
   const uint32_t n_qw = (nq + 32u * QT - 1u) / (32u * QT);
   // about 16 waves per CU (two rounds of the 8 that fit), tiles of at least 256 rows
-  const uint32_t rows_per_tile = mfma_tile_rows(n_rows, (uint32_t)ctx->n_cu * 16u / n_qw, 256u, false);
-  const uint32_t n_tiles = (uint32_t)(((uint64_t)n_rows + rows_per_tile - 1u) / rows_per_tile);
-  const uint32_t blocks = (n_tiles * n_qw + kWavesPerBlock - 1u) / kWavesPerBlock;
+  const Tiling t = tile_plan(n_rows, mfma_tile_rows(n_rows, (uint32_t)ctx->n_cu * 16u / n_qw, 256u, false), n_qw, kWavesPerBlock, 1u);   // no merge behind it
   const float thr = 256.f - 2.f * (float)std::min(radius, 256u);
   auto kern = radius < 128u ? radius_collect_mfma<QT, true> : radius_collect_mfma<QT, false>;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(kBlock), 0, ctx->stream, reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq,
-                     rows_per_tile, n_tiles, n_qw, thr, o);
+  hipLaunchKernelGGL(kern, dim3(t.blocks), dim3(kBlock), 0, ctx->stream, reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq,
+                     t.rows_per_tile, t.n_tiles, n_qw, thr, o);
 }
 
 // Everything up to the outputs. d_counts / d_in_radius / d_matches / d_xyz: where the kernels write (device memory, or pinned host

@@ -10,7 +10,7 @@
 //                            MFMAs) and only a block with a hit walks its 16 registers. Bounds travel between tiles through the
 //                            per-query word of K4 / K4x. Whole blocks only: no split after the first 256 bits.
 // Behind it everything is shared: merge_tiles_kernel (match_merge.h) widens the partial keys, and the lists go the way of the 32-byte
-// search's (tod_match_lists' contract: select_keys_kernel, finalize_kernel, the shard merge, tod_view_remap).
+// search's (tod_match_lists, match.hip: the one wrapper of both widths; select_keys_kernel, finalize_kernel, the shard merge).
 #include <algorithm>
 
 #include "ctx.h"
@@ -21,7 +21,9 @@ namespace {
 #include "match_keys.h"
 #include "match_fp4.h"
 #include "match_merge.h"
+#include "match_plan.h"
 
+using W = RowBits<512>;
 constexpr uint32_t kNoLimit = 0xFFFFFFFFu >> kLocalBits;     // 1023: the distance field of the empty key, above every distance
 
 // The test of one accumulator block, as mfma_block_test: nothing unless some lane's best dot product beats its threshold, then the
@@ -39,76 +41,59 @@ __device__ __forceinline__ void wide_block_test(const mfma_f32x16& acc, float& t
       topk_insert<K>(best, hit ? key : 0xFFFFFFFFu);
     }
   }
-  thr = fmaxf(thr, thr_of_limit_wide(best[K - 1] >> kLocalBits));   // thresholds only ever tighten
+  thr = fmaxf(thr, W::thr_of_limit(best[K - 1] >> kLocalBits));   // thresholds only ever tighten
 }
 
-// W1. Work item = (tile, query wave), consecutive items share a tile. The packed rows of step s + 1 are loaded before step s is
-// expanded and multiplied; the test of block t - 1 sits behind the MFMAs of block t, the step's last block waits in acc_odd for
-// block 0 of the next step (QT is even). cut = radius + 1 (kNoLimit: none); IMAX: cut <= 256, every threshold >= 0.
-// Output: K4's partial lists and flag bytes (match_merge.h reads them).
+// W1. Work item = (tile, query wave), consecutive items share a tile. The loop over the tile's steps is match_fp4.h's
+// block_step_loop; the test of a block is wide_block_test, and behind a step the bounds are exchanged as in hamming_topk_mfma.
+// cut = radius + 1 (kNoLimit: none); IMAX: cut <= 256, every threshold >= 0. Output: K4's partial lists and flag bytes (match_merge.h
+// reads them).
 template <int K, int QT, bool IMAX>
 __global__ __launch_bounds__(kBlock, 2) void hamming_topk_wide(const uint32_t* __restrict__ db, const uint32_t* __restrict__ q,
                                                                uint32_t n_rows, uint32_t nq, uint32_t nq_pad, uint32_t rows_per_tile,
                                                                uint32_t n_tiles, uint32_t n_qw, uint32_t n_qw64, uint32_t cut,
                                                                uint32_t share_period, uint32_t* __restrict__ part, uint32_t* bound,
                                                                uint8_t* __restrict__ stored) {
-  static_assert(QT % 2 == 0 && QT >= 2, "two query blocks share a 64-query flag byte, the pending block alternates between two accumulators");
+  static_assert(QT % 2 == 0 && QT >= 2, "two query blocks share a 64-query flag byte");
   const uint32_t item = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
   const uint32_t tile = item / n_qw, qw = item % n_qw;
   if (tile >= n_tiles) return;
   const uint32_t lane = threadIdx.x & 63u, c = lane & 31u, h = lane >> 5;
   const uint32_t q0 = qw * (32u * QT);
   const Fp4Consts kc = fp4_consts();
-  Fp4Row2 qb[QT];
+  W::Frag qb[QT];
   uint32_t best[QT][K], seen[QT];
   float thr[QT];
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
-    load_query_block_wide(q, q0 + 32u * t + c, nq, h, qb[t], kc);
+    W::load_query_block(q, q0 + 32u * t + c, nq, h, qb[t], kc);
 #pragma unroll
     for (int j = 0; j < K; ++j) best[t][j] = 0xFFFFFFFFu;
-    thr[t] = thr_of_limit_wide(cut);
+    thr[t] = W::thr_of_limit(cut);
     seen[t] = 0xFFFFFFFFu;                                   // "nothing published"
   }
   const uint32_t row0 = tile * rows_per_tile;               // < n_rows: tile < n_tiles
   const uint32_t n_local = min(rows_per_tile, n_rows - row0);
-  const uint32_t n_steps = (n_local + 31u) / 32u;
-  const StepLoaderWide load_step(db, row0, n_steps, c, h);
-  uint4 plo, phi;
-  load_step(0, plo, phi);
-  mfma_f32x16 acc_even, acc_odd;                            // acc_odd: the previous step's last block -- none yet
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
   uint32_t next_share = 2u;                                 // first exchange after 64 rows, as K4
-  for (uint32_t step = 0; step < n_steps; ++step) {
-    Fp4Row2 a;
-    expand_row(plo, a.lo, kc);
-    expand_row(phi, a.hi, kc);
-    load_step(step + 1u, plo, phi);
-    const uint32_t r_lane = lane_row_base(step, h);
+  block_step_loop<W, QT>(
+      db, row0, n_local, c, h, qb, kc,
+      [&](const mfma_f32x16& acc, int t, uint32_t r_lane) { wide_block_test<K, IMAX>(acc, thr[t], r_lane, n_local, best[t]); },
+      [&](uint32_t step) {
+        if (step + 1u < next_share) return;                 // wave-uniform
+        next_share += share_period;
+        // take the bounds loaded one period ago (a published bound stays valid: bounds only fall), publish a full list's bound if it
+        // improves on what was seen, start the loads of the next period
 #pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      if (t & 1) acc_odd = dot_block_wide(a, qb[t]); else acc_even = dot_block_wide(a, qb[t]);
-      if (t == 0) wide_block_test<K, IMAX>(acc_odd, thr[QT - 1], r_lane - 32u, n_local, best[QT - 1]);   // previous step's last block
-      else wide_block_test<K, IMAX>((t & 1) ? acc_even : acc_odd, thr[t - 1], r_lane, n_local, best[t - 1]);
-    }
-    if (step + 1u >= next_share) {                          // wave-uniform
-      next_share += share_period;
-      // take the bounds loaded one period ago (a published bound stays valid: bounds only fall), publish a full list's bound if it
-      // improves on what was seen, start the loads of the next period
-#pragma unroll
-      for (int t = 0; t < QT; ++t) {
-        const uint32_t qi = q0 + 32u * t + c;
-        uint32_t* my_bound = bound + (qi < nq ? qi : nq - 1u);
-        const uint32_t worst_d = best[t][K - 1] >> kLocalBits;
-        if (worst_d < kNoLimit && worst_d < seen[t]) atomicMin(my_bound, worst_d);
-        // a foreign bound is applied with <=: a smaller row index elsewhere may still win a tie
-        if (seen[t] != 0xFFFFFFFFu) thr[t] = fmaxf(thr[t], thr_of_limit_wide(seen[t] + 1u));
-        seen[t] = __hip_atomic_load(my_bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
-  wide_block_test<K, IMAX>(acc_odd, thr[QT - 1], lane_row_base(n_steps - 1u, h), n_local, best[QT - 1]);   // drain
+        for (int t = 0; t < QT; ++t) {
+          const uint32_t qi = q0 + 32u * t + c;
+          uint32_t* my_bound = bound + (qi < nq ? qi : nq - 1u);
+          const uint32_t worst_d = best[t][K - 1] >> kLocalBits;
+          if (worst_d < kNoLimit && worst_d < seen[t]) atomicMin(my_bound, worst_d);
+          // a foreign bound is applied with <=: a smaller row index elsewhere may still win a tie
+          if (seen[t] != 0xFFFFFFFFu) thr[t] = fmaxf(thr[t], W::thr_of_limit(seen[t] + 1u));
+          seen[t] = __hip_atomic_load(my_bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      });
 
   // lanes l and l + 32 hold the two halves of a query's rows: merge the partner's list, then K4's output format (partial keys + one
   // flag byte per (tile, 64 queries); two query blocks share a flag, so both are stored when either kept something)
@@ -137,40 +122,28 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_wide(const uint32_t* _
   }
 }
 
-// One launch: tiling, workspaces in prepare_lists' layout (match_launch.h: the partial lists; the per-query bound words, 0xFFFFFFFF =
-// none published, and the per-(tile, 64 queries) flag bytes, 0xFF = nothing stored, under one memset), the DB pass, the tile merge.
+// One launch on the shared plan (match_plan.h): tiling, workspaces, the DB pass, the tile merge. The grid is linear: the kernel's
+// work-item decode knows no XCDs.
 template <int K, int QT>
 int launch_wide(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
   const uint32_t cut = radius >= 512u ? kNoLimit : radius + 1u;     // distances are <= 512: no cut beyond that
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
   const uint32_t n_qw = (nq + 32u * QT - 1u) / (32u * QT), n_qw64 = (nq + 63u) / 64u, nq_pad = n_qw64 * 64u;
   // about 16 waves per CU (two rounds of the 8 that fit), tiles of at least 256 rows: the radius pass's plan, not tuned further
-  const uint32_t rows_per_tile = mfma_tile_rows(n_rows, (uint32_t)ctx->n_cu * 16u / n_qw, 256u, false);
-  if (rows_per_tile > kLocalMask) return TODHIP_EINVAL;             // a tile would not fit the partial key's row bits
-  const uint32_t n_tiles = (uint32_t)(((uint64_t)n_rows + rows_per_tile - 1u) / rows_per_tile);
-  const uint64_t items = (uint64_t)n_tiles * n_qw;
-  if (items > 0x7FFFFFFFull) return TODHIP_EINVAL;
-  const size_t bound_bytes = (size_t)nq_pad * sizeof(uint32_t), flag_bytes = (size_t)n_tiles * n_qw64;
-  TOD_HIP(ctx->m_part.reserve((size_t)n_tiles * K * nq_pad * sizeof(uint32_t)));
-  TOD_HIP(ctx->m_bound.reserve(bound_bytes + flag_bytes));
-  TOD_HIP(hipMemsetAsync(ctx->m_bound.p, 0xFF, bound_bytes + flag_bytes, ctx->stream));
-  uint8_t* const d_stored = ctx->m_bound.as<uint8_t>() + bound_bytes;
+  Tiling t;
+  if (!finish_tiling(n_rows, mfma_tile_rows(n_rows, (uint32_t)ctx->n_cu * 16u / n_qw, 256u, false), n_qw, &t)) return TODHIP_EINVAL;
+  if ((uint64_t)t.n_tiles * n_qw > 0x7FFFFFFFull) return TODHIP_EINVAL;   // the kernel numbers its work items in 32 bits
+  uint8_t* const d_stored = prepare_lists<K>(ctx, t.n_tiles, nq_pad, n_qw64);
+  if (!d_stored) return TODHIP_EHIP;
   KernelTimer timer{ctx};                                           // the DB pass between two events, as K4 / K4x / R1
   if (int rc = timer.begin()) return rc;
   auto kern = cut <= 256u ? hamming_topk_wide<K, QT, true> : hamming_topk_wide<K, QT, false>;
-  hipLaunchKernelGGL(kern, dim3((uint32_t)((items + kWavesPerBlock - 1u) / kWavesPerBlock)), dim3(kBlock), 0, ctx->stream,
-                     reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, rows_per_tile, n_tiles, n_qw, n_qw64, cut,
-                     16u, ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
+  hipLaunchKernelGGL(kern, dim3(t.blocks), dim3(kBlock), 0, ctx->stream, reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq,
+                     nq_pad, t.rows_per_tile, t.n_tiles, n_qw, n_qw64, cut, 16u, ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
   if (int rc = timer.end()) return rc;
   TOD_HIP(hipGetLastError());
   ctx->counters.last_block_split = 4;                               // whole blocks: the one form there is
-  const uint32_t groups = std::min(n_tiles, (uint32_t)kMergeGroups);
-  hipLaunchKernelGGL(merge_tiles_kernel<K>, dim3((nq + kBlock - 1) / kBlock, groups), dim3(kBlock), 0, ctx->stream, ctx->m_part.as<uint32_t>(),
-                     nq, nq_pad, n_tiles, rows_per_tile, tod_db_first_row(ctx), groups, d_stored, n_qw64, d_lists, (const uint32_t*)nullptr,
-                     (uint32_t*)nullptr, 0u);
-  TOD_HIP(hipGetLastError());
-  *n_lists = groups;
-  return TODHIP_OK;
+  return launch_merge<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, nullptr, d_lists, n_lists);
 }
 
 // Query blocks per wave: a block's expanded fragments are 32 registers at this width. Four blocks (128) beside the row (32), two
@@ -183,35 +156,11 @@ int launch_wide_k(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t ra
   return launch_wide<K, kMaxQT>(ctx, d_q, nq, radius, d_lists, n_lists);
 }
 
-int wide_lists_active(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
-  if (ctx->ratio > 0.f) radius = 512u;   // the ratio test needs the true second neighbour, however far: no radius bound in the search
-  const uint32_t* q = reinterpret_cast<const uint32_t*>(d_q);
-  switch (k) {
-    case 1: return launch_wide_k<1>(ctx, q, nq, radius, d_lists, n_lists);
-    case 2: return launch_wide_k<2>(ctx, q, nq, radius, d_lists, n_lists);
-    case 3: return launch_wide_k<3>(ctx, q, nq, radius, d_lists, n_lists);
-    case 4: return launch_wide_k<4>(ctx, q, nq, radius, d_lists, n_lists);
-    case 5: return launch_wide_k<5>(ctx, q, nq, radius, d_lists, n_lists);
-    case 6: return launch_wide_k<6>(ctx, q, nq, radius, d_lists, n_lists);
-    case 7: return launch_wide_k<7>(ctx, q, nq, radius, d_lists, n_lists);
-    case 8: return launch_wide_k<8>(ctx, q, nq, radius, d_lists, n_lists);
-    default: return TODHIP_EINVAL;
-  }
-}
-
 }  // namespace
 
-// tod_match_lists for a 64-byte DB (ctx.h): d_lists[n_lists][nq][k], each ascending, keys distance << 32 | global row, padding ~0.
-// No bit order at this width (db_bitorder.hip leaves the rows as loaded) and no LSH index (lsh.hip builds none): enabled LSH is refused.
-int tod_match_lists_wide(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
-  if (ctx->desc_bytes != 64 || k == 0 || k > 8 || nq == 0) return TODHIP_EINVAL;
-  if (tod_lsh_enabled(ctx)) return TODHIP_EINVAL;
-  if (tod_db_n_rows(ctx) == 0) {             // no selected row in this shard: one list of padding keys (what an empty shard contributes)
-    TOD_HIP(hipMemsetAsync(d_lists, 0xFF, (size_t)nq * k * sizeof(uint64_t), ctx->stream));
-    *n_lists = 1;
-    return TODHIP_OK;
-  }
-  int rc = wide_lists_active(ctx, d_q, nq, k, radius, d_lists, n_lists);
-  if (rc != TODHIP_OK || !ctx->sel_on) return rc;
-  return tod_view_remap(ctx, d_lists, (size_t)*n_lists * nq * k);   // todhip_db_select_objects: view rows -> rows of the full DB
+// tod_match_lists' search at this width (ctx.h): the active rows, at least one; k in 1..8
+int tod_wide_lists_active(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t k, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
+  if (ctx->ratio > 0.f) radius = 512u;   // the ratio test needs the true second neighbour, however far: no radius bound in the search
+  const uint32_t* q = reinterpret_cast<const uint32_t*>(d_q);
+  return dispatch_k(k, [&](auto K) { return launch_wide_k<decltype(K)::value>(ctx, q, nq, radius, d_lists, n_lists); });
 }
