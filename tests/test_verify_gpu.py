@@ -377,6 +377,132 @@ def test_depth_image_form_equals_cloud_form(ctx, u16):
     assert np.array_equal(a[0]["inliers"], b[0]["inliers"]) and np.array_equal(a[0]["R"], b[0]["R"]) and np.array_equal(a[0]["t"], b[0]["t"])
 
 
+SKEW_K = np.array([[525.0, 0, 301.25], [0, 470.0, 255.5], [0, 0, 1]], np.float32)      # fx != fy, principal point off the centre and off the integers
+
+
+def _cloud_of(z, K):
+    """cv::depthTo3d's convention in float32: what the depth form must compute for the pixel under a keypoint"""
+    H, W = z.shape
+    u, v = np.meshgrid(np.arange(W, dtype=np.float32), np.arange(H, dtype=np.float32))
+    with np.errstate(invalid="ignore"):
+        return np.stack([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z], axis=2).astype(np.float32)
+
+
+def _frame_seen_by(K, desc, pts, off, n_kp, frame, u16, H=480, W=640):
+    """synth.make_frame's descriptors and 3D points, projected with K instead of its centred camera (a frame made for fx == fy shows
+    no rigid object through another K). Keypoint coordinates carry fractions 0, .5 and .999 of the pixel that holds their depth
+    (the lookup truncates: rounding would read the empty neighbour); NaN / 0 and inf lie under some keypoints.
+    Returns (kp_xy, q_desc, depth, z: the depth in float metres as the lookup sees it)."""
+    fr = synth.make_frame(desc, pts, off, n_kp, frame=frame, visible_object=0, nan_frac=0.0)
+    col0, row0 = fr["kp_xy"][:, 0].astype(np.int64), fr["kp_xy"][:, 1].astype(np.int64)
+    xyz = fr["cloud"][row0, col0].astype(np.float64)                         # (a later keypoint on the same pixel owns it: as in make_frame)
+    u = K[0, 0] * xyz[:, 0] / xyz[:, 2] + K[0, 2]
+    v = K[1, 1] * xyz[:, 1] / xyz[:, 2] + K[1, 2]
+    col, row = np.clip(np.floor(u), 0, W - 1).astype(np.int64), np.clip(np.floor(v), 0, H - 1).astype(np.int64)
+    frac = np.array([0.0, 0.5, 0.999], np.float32)
+    kp = np.stack([col.astype(np.float32) + frac[np.arange(n_kp) % 3], row.astype(np.float32) + frac[(np.arange(n_kp) // 3) % 3]], axis=1)
+    assert np.array_equal(kp.astype(np.int64), np.stack([col, row], axis=1)) and (np.rint(kp[:, 0]) != col).sum() > n_kp // 4
+    z = np.full((H, W), np.nan, np.float32)
+    z[row, col] = xyz[:, 2].astype(np.float32)
+    z[row[5::17], col[5::17]] = np.nan                                       # no measurement under every 17th keypoint
+    if not u16:
+        z[row[9::23], col[9::23]] = np.inf
+    if u16:
+        depth = np.where(np.isnan(z), 0, np.rint(z * 1000.0)).astype(np.uint16)
+        z = np.where(depth == 0, np.nan, depth.astype(np.float32) * np.float32(0.001)).astype(np.float32)
+    else:
+        depth = z
+    under = z[row, col]
+    assert np.isnan(under).sum() >= n_kp // 20 and (u16 or np.isinf(under).sum() >= n_kp // 30)
+    return kp, fr["q_desc"], depth, z
+
+
+@pytest.mark.parametrize("u16", [False, True])
+def test_depth_image_form_equals_cloud_form_with_a_general_camera(ctx, u16):
+    """as test_depth_image_form_equals_cloud_form, with a camera that tells fx from fy and cx from cy, keypoints inside their pixels
+    (fractions .5 and .999: truncated, not rounded) and NaN / 0 / inf depth under keypoints"""
+    import torch
+    desc, pts, off = synth.make_db(2, per_object=3000)
+    H, W, nq, k = 480, 640, 500, 5
+    kp, q_desc, depth, z = _frame_seen_by(SKEW_K, desc, pts, off, nq, 6, u16)
+    cloud = _cloud_of(z, SKEW_K)
+    spans = ctx.db_load(desc, pts, off)
+    d_q = torch.from_numpy(q_desc).cuda()
+    d_counts = torch.empty(nq, dtype=torch.int32, device="cuda")
+    d_m = torch.empty((nq * k, 4), dtype=torch.int32, device="cuda")
+    d_xyz = torch.empty((nq * k, 3), dtype=torch.float32, device="cuda")
+    d_kp = torch.from_numpy(kp).cuda()
+    d_cloud = torch.from_numpy(cloud).cuda()
+    d_depth = torch.from_numpy(depth.view(np.int16) if u16 else depth).cuda()
+    torch.cuda.synchronize()
+    ctx.match_device(d_q.data_ptr(), nq, k, 35, d_counts.data_ptr(), d_m.data_ptr(), d_xyz.data_ptr())
+    r1, r2 = capi.rng_new(1), capi.rng_new(1)
+    a = ctx.verify_device(d_kp.data_ptr(), nq, d_cloud.data_ptr(), H, W, d_counts.data_ptr(), d_m.data_ptr(),
+                          d_xyz.data_ptr(), k, spans, 8, 1000, 0.01, r1)
+    b = ctx.verify_device_depth(d_kp.data_ptr(), nq, d_depth.data_ptr(), u16, H, W, SKEW_K, d_counts.data_ptr(),
+                                d_m.data_ptr(), d_xyz.data_ptr(), k, spans, 8, 1000, 0.01, r2)
+    assert len(a) == len(b) == 1 and r1.draws == r2.draws
+    assert np.array_equal(a[0]["inliers"], b[0]["inliers"]) and np.array_equal(a[0]["R"], b[0]["R"]) and np.array_equal(a[0]["t"], b[0]["t"])
+    # the pose is the frame's: the object is seen rigidly only if the lookup uses fx for x, fy for y and each principal point once
+    assert a[0]["object"] == 0 and len(a[0]["inliers"]) >= 50
+    assert np.abs(a[0]["R"] - synth.pose_R()).max() < 0.03 and np.abs(a[0]["t"] - synth.POSE_T).max() < 0.01
+    # a camera with the focal lengths exchanged is another cloud, and the depth form notices
+    swapped = SKEW_K.copy(); swapped[0, 0], swapped[1, 1] = SKEW_K[1, 1], SKEW_K[0, 0]
+    c = ctx.verify_device_depth(d_kp.data_ptr(), nq, d_depth.data_ptr(), u16, H, W, swapped, d_counts.data_ptr(),
+                                d_m.data_ptr(), d_xyz.data_ptr(), k, spans, 8, 1000, 0.01, capi.rng_new(1))
+    assert not (len(c) == 1 and np.array_equal(c[0]["R"], a[0]["R"]) and np.array_equal(c[0]["t"], a[0]["t"]))
+
+
+def _clutter_on_device(u16, seed=43):
+    """a frame of clutter only (matches given, no object visible): device arrays of both forms of its 3D points"""
+    import torch
+    sc = synth.make_verify_scene(80, visible=(), matches_per_kp=5, seed=seed)
+    z = sc["cloud"][:, :, 2].copy()
+    if u16:
+        depth = np.where(np.isnan(z), 0, np.rint(z * 1000.0)).astype(np.uint16)
+        z = np.where(depth == 0, np.nan, depth.astype(np.float32) * np.float32(0.001)).astype(np.float32)
+    else:
+        depth = z
+    counts, m, xyz = _pack_scene(sc, 5)
+    dev = dict(kp=torch.from_numpy(np.ascontiguousarray(sc["kp_xy"], np.float32)).cuda(), cloud=torch.from_numpy(_cloud_of(z, SKEW_K)).cuda(),
+               depth=torch.from_numpy(depth.view(np.int16) if u16 else depth).cuda(), counts=torch.from_numpy(counts).cuda(),
+               m=torch.from_numpy(m).cuda(), xyz=torch.from_numpy(np.ascontiguousarray(xyz)).cuda())
+    torch.cuda.synchronize()
+    return sc, dev
+
+
+@pytest.mark.parametrize("u16", [False, True])
+def test_depth_and_cloud_lookup_agree_without_a_pose(ctx, u16):
+    """no object visible: both forms find nothing and draw the same number of random numbers on the way, so the same keypoints had a
+    3D point and the same points went into the samples; a keypoint outside the image is the same error in both"""
+    sc, d = _clutter_on_device(u16)
+    nq, k, (H, W) = len(sc["kp_xy"]), 5, sc["cloud"].shape[:2]
+    r1, r2 = capi.rng_new(1), capi.rng_new(1)
+    a = ctx.verify_device(d["kp"].data_ptr(), nq, d["cloud"].data_ptr(), H, W, d["counts"].data_ptr(), d["m"].data_ptr(),
+                          d["xyz"].data_ptr(), k, sc["spans"], 8, 100, 0.01, r1)
+    b = ctx.verify_device_depth(d["kp"].data_ptr(), nq, d["depth"].data_ptr(), u16, H, W, SKEW_K, d["counts"].data_ptr(),
+                                d["m"].data_ptr(), d["xyz"].data_ptr(), k, sc["spans"], 8, 100, 0.01, r2)
+    assert a == [] and b == [] and r1.draws == r2.draws and r1.draws > 0
+    assert list(r1.s) == list(r2.s) and (r1.f, r1.b) == (r2.f, r2.b)
+    import torch
+    for x, y in ((float(W), 10.0), (10.0, float(H)), (-1.0, 10.0)):
+        kp = np.ascontiguousarray(sc["kp_xy"], np.float32).copy()
+        kp[3] = (x, y)
+        d_kp = torch.from_numpy(kp).cuda()
+        torch.cuda.synchronize()
+        status = []
+        for form in ("cloud", "depth"):
+            with pytest.raises(capi.TodError) as e:
+                if form == "cloud":
+                    ctx.verify_device(d_kp.data_ptr(), nq, d["cloud"].data_ptr(), H, W, d["counts"].data_ptr(), d["m"].data_ptr(),
+                                      d["xyz"].data_ptr(), k, sc["spans"], 8, 100, 0.01, capi.rng_new(1))
+                else:
+                    ctx.verify_device_depth(d_kp.data_ptr(), nq, d["depth"].data_ptr(), u16, H, W, SKEW_K, d["counts"].data_ptr(),
+                                            d["m"].data_ptr(), d["xyz"].data_ptr(), k, sc["spans"], 8, 100, 0.01, capi.rng_new(1))
+            status.append(e.value.status)
+        assert status == [capi.ERANGE, capi.ERANGE]
+
+
 def _pack_scene(sc, k):
     nq = len(sc["kp_xy"])
     counts = np.diff(sc["row_ptr"].astype(np.int64)).astype(np.int32)
