@@ -139,6 +139,8 @@ int todhip_db_desc_bytes(const todhip_ctx*, uint32_t* desc_bytes);
  * 4, todhip_set_kernel_timing brackets the DB pass as on a 32-byte DB.
  * What a 64-byte DB refuses or ignores:
  *   todhip_match_radius[_device], todhip_match_l2[_device]   TODHIP_EINVAL.
+ *   todhip_match_radius_shard_device,
+ *   todhip_merge_radius_shards_device[_on]                   TODHIP_EINVAL.
  *   the match calls while todhip_set_lsh is enabled          TODHIP_EINVAL before any device work (no index is built at this width).
  *   todhip_set_db_bit_order                                  the mode may be set; the rows stay in identity order and the results
  *                                                            are those of the definition.
@@ -269,8 +271,8 @@ int todhip_merge_shards_device_on(todhip_ctx*, void* hip_stream, const void* d_k
  *                  max_per_query; counts[q] = min(|R(q)|, max_per_query). queryIdx, trainIdx, imgIdx, distance and the gathered model
  *                  point of a row are exactly what todhip_match writes for it.
  *   searched rows = what todhip_match* searches on this context: the resident shard, in the numbering of the full DB. On a context
- *                  loaded with shard_count > 1 each rank answers for its own rows; the keys (distance, row) are unique over the ranks,
- *                  so a caller merges the ranks' answers by concatenating and sorting them (in_radius adds up). todhip_db_select_objects
+ *                  loaded with shard_count > 1 each rank answers for its own rows; the ranks' answers are merged on the device by
+ *                  todhip_match_radius_shard_device + todhip_merge_radius_shards_device[_on] below. todhip_db_select_objects
  *                  is honoured: the result is that of a context loaded with the selected objects alone, imgIdx in the full DB's
  *                  numbering; an empty selection gives all counts 0. todhip_set_db_bit_order is honoured: the queries are permuted as
  *                  the other forms permute them, the results do not change.
@@ -293,6 +295,37 @@ int todhip_match_radius(todhip_ctx*, const uint8_t* q_desc, uint32_t nq, uint32_
 int todhip_match_radius_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t radius, uint32_t max_per_query,
                                void* d_counts /*[nq] u32*/, void* d_matches /*[nq*max_per_query]*/,
                                void* d_matches_xyz /*[nq*max_per_query*3]*/, void* d_in_radius /*[nq] u32, may be NULL*/);
+
+/* The radius search over a sharded DB, merged on the device: what todhip_match_shard_device + todhip_merge_shards_device[_on] are to
+ * todhip_match_device. R_s(q): the rows of R(q) that this context searches (its shard, under its selection).
+ * Step 1, on every rank. Row q of d_keys, nq x (max_per_query + 1) u64:
+ *   slots [0, max_per_query)   the min(|R_s(q)|, max_per_query) nearest rows of R_s(q) as keys distance << 32 | row of the full DB,
+ *                              ascending; UINT64_MAX behind them.
+ *   slot max_per_query         |R_s(q)| as a u64, exact, never truncated.
+ *   EVERY slot of the buffer is written: it goes through a collective as it is. The searched rows, selections (keys in the full DB's
+ *   numbering), the bit order and "the ratio test and LSH do not apply" are those of todhip_match_radius_device on this context; a
+ *   shard or selection without rows writes all-padding rows with count 0. Refusals: those of todhip_match_radius_device.
+ * Step 2, on the rank that owns the queries. d_keys_all: [n_shards][nq][max_per_query + 1] u64, step 1's outputs. Per query:
+ *   in_radius[q] = the sum of the shards' counts; counts[q] = min(in_radius[q], max_per_query); the matches are the first counts[q]
+ *   keys of the union of the shards' keys in key order, resolved and gathered as todhip_match_radius_device does, fixed stride
+ *   max_per_query, slots behind counts[q] not written: byte for byte what todhip_match_radius_device leaves for an unsharded context
+ *   on the same DB. Why: a key among the first max_per_query of the union of all R_s(q) is preceded by fewer than max_per_query keys
+ *   of its own shard, so it is among that shard's first max_per_query -- the global first max_per_query lie inside the union of the
+ *   per-shard first max_per_query -- and the keys (distance, row) are unique over the shards.
+ *   The merge reads only the context's object table and model points (every rank holds the full DB's), so any rank's context will
+ *   do, and the _on form may run on a stream of the caller's beside a DB pass on the context's own, as
+ *   todhip_merge_shards_device_on does; the caller orders that stream against the producer of d_keys_all and the consumers.
+ *   TODHIP_EINVAL: a null pointer other than d_in_radius, nq == 0, n_shards == 0 or > 64, max_per_query == 0 or > 1024, a DB that
+ *   is not 32-byte binary. TODHIP_ENODB without a DB.
+ * The exchange carries world * nq * (max_per_query + 1) * 8 bytes per rank and step. */
+int todhip_match_radius_shard_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t radius, uint32_t max_per_query,
+                                     void* d_keys /*[nq*(max_per_query+1)] u64*/);
+int todhip_merge_radius_shards_device(todhip_ctx*, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t max_per_query,
+                                      void* d_counts /*[nq] u32*/, void* d_matches /*[nq*max_per_query]*/,
+                                      void* d_matches_xyz /*[nq*max_per_query*3]*/, void* d_in_radius /*[nq] u32, may be NULL*/);
+int todhip_merge_radius_shards_device_on(todhip_ctx*, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq,
+                                         uint32_t max_per_query, void* d_counts, void* d_matches, void* d_matches_xyz,
+                                         void* d_in_radius /*may be NULL*/);
 
 /* ---- stage C: GuessGenerator ------------------------------------------------------------------- */
 void todhip_rng_seed(todhip_rng*, uint32_t seed);   /* srand(seed); the reference never seeds => seed 1 */

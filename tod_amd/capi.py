@@ -94,6 +94,7 @@ EXPORTS = [
     "todhip_pattern_learn_responses", "todhip_pattern_learn_free", "todhip_pipeline_set_pattern",
     "todhip_db_select_objects", "todhip_db_selection", "todhip_pipeline_select_objects",
     "todhip_match_radius", "todhip_match_radius_device",
+    "todhip_match_radius_shard_device", "todhip_merge_radius_shards_device", "todhip_merge_radius_shards_device_on",
     "todhip_db_desc_bytes",
 ]
 
@@ -157,6 +158,13 @@ def lib():
             L.todhip_match_radius.restype = C.c_int
             L.todhip_match_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
             L.todhip_match_radius_device.restype = C.c_int
+        if hasattr(L, "todhip_match_radius_shard_device"):            # (as above)
+            L.todhip_match_radius_shard_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.todhip_match_radius_shard_device.restype = C.c_int
+            L.todhip_merge_radius_shards_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+            L.todhip_merge_radius_shards_device.restype = C.c_int
+            L.todhip_merge_radius_shards_device_on.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+            L.todhip_merge_radius_shards_device_on.restype = C.c_int
         if hasattr(L, "todhip_db_desc_bytes"):                        # (as above)
             L.todhip_db_desc_bytes.argtypes, L.todhip_db_desc_bytes.restype = [C.c_void_p, C.c_void_p], C.c_int
         _lib = L
@@ -393,6 +401,21 @@ class Context:
         """Device-pointer form (ints from tensor.data_ptr()), fixed stride max_per_query; d_in_radius may be None."""
         _check(lib().todhip_match_radius_device(self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius),
                "todhip_match_radius_device")
+
+    def match_radius_shard_device(self, d_q, nq, radius, max_per_query, d_keys):
+        """The sharded radius search, step 1: this context's shard -> d_keys u64[nq, max_per_query + 1] (ascending keys
+        distance << 32 | row of the full DB, UINT64_MAX padding, the shard's exact count in the last slot; every slot written)."""
+        _check(lib().todhip_match_radius_shard_device(self._h, d_q, nq, radius, max_per_query, d_keys), "todhip_match_radius_shard_device")
+
+    def merge_radius_shards_device(self, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
+        """Step 2: d_keys_all u64[n_shards, nq, max_per_query + 1] -> what match_radius_device leaves on the unsharded DB."""
+        _check(lib().todhip_merge_radius_shards_device(self._h, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz,
+                                                       d_in_radius), "todhip_merge_radius_shards_device")
+
+    def merge_radius_shards_device_on(self, stream, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
+        """The same merge on a stream of the caller's (it only reads the context's immutable tables)."""
+        _check(lib().todhip_merge_radius_shards_device_on(self._h, stream, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches,
+                                                          d_xyz, d_in_radius), "todhip_merge_radius_shards_device_on")
 
     def match_l2(self, q_desc, k, radius):
         """Float descriptors, host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""

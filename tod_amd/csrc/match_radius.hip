@@ -21,6 +21,12 @@
 //                            lookup and 3D gather, as K4f). Slots behind counts[q] are not written.
 // Rows are numbered within what is searched (the shard, or the selection's view) until R3: both maps to the full DB are increasing,
 // so the order (distance, searched row) is the order (distance, global row) of decision D1.
+//
+// Over a sharded DB (todhip_match_radius_shard_device + todhip_merge_radius_shards_device[_on]) a rank runs R1 and R2 on
+// its shard and sends what they leave, and the owner of a query merges the ranks' answers:
+//   S1 radius_shard_keys_kernel   instead of R3: the query's first max_per_query keys with rows of the full DB, padding, and |R_s(q)|.
+//   M1 radius_merge_kernel        a rank merge of the shards' lists by binary search, then store_match. The global first
+//                                 max_per_query lie inside the union of the per-shard first max_per_query.
 #include <algorithm>
 
 #include "ctx.h"
@@ -216,6 +222,84 @@ __global__ __launch_bounds__(kBlock) void radius_emit_kernel(const uint64_t* __r
   store_match(qi, (uint32_t)(key >> 32), (uint32_t)key + first_row, slot, obj_off, n_objs, pts, matches, xyz);
 }
 
+// S1. thread = slot of the nq x (max_per_query + 1) keys a shard sends: the first min(|R_s(q)|, max_per_query) keys of the query's
+// buffer with rows of the full DB, padding behind them, |R_s(q)| in the last slot. Every slot is written. in_radius null: a shard
+// without a searched row (cand is not read).
+__global__ __launch_bounds__(kBlock) void radius_shard_keys_kernel(const uint64_t* __restrict__ cand, const uint32_t* __restrict__ in_radius,
+                                                                   uint32_t nq, uint32_t max_per_query, uint32_t cap, uint32_t first_row,
+                                                                   uint64_t* __restrict__ keys) {
+  const size_t slot = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t qi = (uint32_t)(slot / (max_per_query + 1u)), j = (uint32_t)(slot % (max_per_query + 1u));
+  if (qi >= nq) return;
+  const uint32_t n = in_radius ? in_radius[qi] : 0u;
+  uint64_t v = ~0ull;
+  if (j == max_per_query) v = n;
+  else if (j < n) v = cand[(size_t)qi * cap + j] + first_row;           // (j < max_per_query; row + first_row < 2^32: no carry)
+  keys[slot] = v;
+}
+
+// keys of an ascending list of n (padding ~0 at its end) that are below `key`
+__device__ __forceinline__ uint32_t keys_below(const uint64_t* lst, uint32_t n, uint64_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (lst[mid] < key) lo = mid + 1u; else hi = mid;
+  }
+  return lo;
+}
+
+// M1, the merge of the shards' radius answers: keys_all[n_shards][nq][max_per_query + 1] as S1 writes them. A rank merge -- the keys
+// of a query are unique over the shards (the row is part of the key), so element j of shard s stands at position
+// j + sum over t != s of (keys of shard t below it), one binary search per other shard; the padding sorts last, so a search runs over
+// all max_per_query slots. A list that was cut at max_per_query answers max_per_query for a key behind its cut; the position is then
+// >= max_per_query, as the true one is. An element whose position is below max_per_query is one of the query's first max_per_query:
+// store_match puts it there. No sort, no atomics, each output slot has one writer.
+// thread = (shard, slot) element of a query; E = n_shards * max_per_query elements per query. A workgroup takes qpb queries:
+// floor(256 / E) while E <= 128 (max_per_query = 5 on two shards: 25 queries), else one, its threads striding over the elements.
+// STAGED: the workgroup's lists fit kMergeLdsKeys keys and are searched in LDS; otherwise (up to 64 x 1024) in global memory.
+constexpr uint32_t kMergeLdsKeys = 4096;                    // 32 KB
+constexpr uint32_t kMaxMergeShards = 64;
+
+template <bool STAGED>
+__global__ __launch_bounds__(kBlock) void radius_merge_kernel(const uint64_t* __restrict__ keys_all, uint32_t n_shards, uint32_t nq,
+                                                              uint32_t max_per_query, uint32_t qpb, const uint32_t* __restrict__ obj_off,
+                                                              uint32_t n_objs, const float* __restrict__ pts, uint32_t* __restrict__ counts,
+                                                              uint32_t* __restrict__ in_radius, todhip_dmatch* __restrict__ matches,
+                                                              float* __restrict__ xyz) {
+  TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
+  __shared__ uint64_t s_keys[STAGED ? kMergeLdsKeys : 1];
+  const uint32_t tid = threadIdx.x, q0 = blockIdx.x * qpb;
+  const uint32_t stride = max_per_query + 1u, elems = n_shards * max_per_query;
+  const uint32_t n_here = min(qpb, nq - q0) * elems;        // elements of this workgroup's queries (q0 < nq by the grid)
+  if (tid < qpb && q0 + tid < nq) {                         // the count slots
+    uint64_t n = 0;
+    for (uint32_t s = 0; s < n_shards; ++s) n += keys_all[((size_t)s * nq + q0 + tid) * stride + max_per_query];
+    counts[q0 + tid] = n < max_per_query ? (uint32_t)n : max_per_query;
+    if (in_radius) in_radius[q0 + tid] = (uint32_t)n;
+  }
+  if (STAGED) {                                             // image [query][shard][slot], n_here <= kMergeLdsKeys
+    for (uint32_t i = tid; i < n_here; i += kBlock) {
+      const uint32_t ql = i / elems, e = i % elems, s = e / max_per_query, j = e % max_per_query;
+      s_keys[i] = keys_all[((size_t)s * nq + q0 + ql) * stride + j];
+    }
+    __syncthreads();
+  }
+  for (uint32_t i = tid; i < n_here; i += kBlock) {
+    const uint32_t ql = i / elems, e = i % elems, s = e / max_per_query, j = e % max_per_query;
+    const uint32_t qi = q0 + ql;
+    const uint64_t key = STAGED ? s_keys[i] : keys_all[((size_t)s * nq + qi) * stride + j];
+    if (key == ~0ull) continue;                             // padding
+    uint32_t pos = j;
+    for (uint32_t t = 0; t < n_shards && pos < max_per_query; ++t) {
+      if (t == s) continue;
+      if constexpr (STAGED) pos += keys_below(s_keys + ql * elems + t * max_per_query, max_per_query, key);
+      else pos += keys_below(keys_all + ((size_t)t * nq + qi) * stride, max_per_query, key);
+    }
+    if (pos < max_per_query)
+      store_match(qi, (uint32_t)(key >> 32), (uint32_t)key, (size_t)qi * max_per_query + pos, obj_off, n_objs, pts, matches, xyz);
+  }
+}
+
 template <int QT>
 void launch_collect(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, const CollectOut& o) {
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
@@ -228,17 +312,18 @@ void launch_collect(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t 
                      t.rows_per_tile, t.n_tiles, n_qw, thr, o);
 }
 
-// Everything up to the outputs. d_counts / d_in_radius / d_matches / d_xyz: where the kernels write (device memory, or pinned host
-// memory for the matches of the host form).
-int radius_search(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t radius, uint32_t mpq, uint32_t* d_counts, todhip_dmatch* d_matches,
-                  float* d_xyz, uint32_t* d_in_radius) {
-  TOD_HIP(hipSetDevice(ctx->device));
+// What R1 and R2 leave behind: nq x cap keys, the first min(|R(q)|, max_per_query) of a query's row its answer in key order, rows
+// those of the full DB but for tod_db_first_row
+struct RadiusKeys {
+  const uint64_t* cand;
+  uint32_t cap;
+};
+
+// R1 and R2 over the searched rows (there is at least one). d_counts / d_in_radius: where R2 writes min(|R(q)|, max_per_query) and
+// |R(q)| (device memory; d_in_radius may be null).
+int radius_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t radius, uint32_t mpq, uint32_t* d_counts, uint32_t* d_in_radius,
+                RadiusKeys* out) {
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
-  if (n_rows == 0) {                                        // an empty selection, or a shard without a (selected) row
-    TOD_HIP(hipMemsetAsync(d_counts, 0, (size_t)nq * sizeof(uint32_t), ctx->stream));
-    if (d_in_radius) TOD_HIP(hipMemsetAsync(d_in_radius, 0, (size_t)nq * sizeof(uint32_t), ctx->stream));
-    return TODHIP_OK;
-  }
   if (ctx->bit_order_on) {                                  // todhip_set_db_bit_order: the queries follow the rows
     int rc = tod_bit_order_queries(ctx, d_q, nq, &d_q);
     if (rc != TODHIP_OK) return rc;
@@ -267,10 +352,58 @@ int radius_search(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t radius
     int rc = tod_view_remap(ctx, o.cand, (size_t)nq * cap);
     if (rc != TODHIP_OK) return rc;
   }
+  *out = RadiusKeys{o.cand, cap};
+  return TODHIP_OK;
+}
+
+// Everything up to the outputs. d_counts / d_in_radius / d_matches / d_xyz: where the kernels write (device memory, or pinned host
+// memory for the matches of the host form).
+int radius_search(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t radius, uint32_t mpq, uint32_t* d_counts, todhip_dmatch* d_matches,
+                  float* d_xyz, uint32_t* d_in_radius) {
+  TOD_HIP(hipSetDevice(ctx->device));
+  if (tod_db_n_rows(ctx) == 0) {                            // an empty selection, or a shard without a (selected) row
+    TOD_HIP(hipMemsetAsync(d_counts, 0, (size_t)nq * sizeof(uint32_t), ctx->stream));
+    if (d_in_radius) TOD_HIP(hipMemsetAsync(d_in_radius, 0, (size_t)nq * sizeof(uint32_t), ctx->stream));
+    return TODHIP_OK;
+  }
+  RadiusKeys k;
+  if (int rc = radius_keys(ctx, d_q, nq, radius, mpq, d_counts, d_in_radius, &k)) return rc;
   const size_t slots = (size_t)nq * mpq;
-  hipLaunchKernelGGL(radius_emit_kernel, dim3((uint32_t)((slots + kBlock - 1u) / kBlock)), dim3(kBlock), 0, ctx->stream, o.cand, d_counts, nq,
-                     mpq, cap, (uint32_t)tod_db_first_row(ctx), ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), d_matches,
+  hipLaunchKernelGGL(radius_emit_kernel, dim3((uint32_t)((slots + kBlock - 1u) / kBlock)), dim3(kBlock), 0, ctx->stream, k.cand, d_counts, nq,
+                     mpq, k.cap, (uint32_t)tod_db_first_row(ctx), ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), d_matches,
                      d_xyz);
+  TOD_HIP(hipGetLastError());
+  return TODHIP_OK;
+}
+
+// The sharded form's first half: R1 and R2, then S1 into the caller's nq x (max_per_query + 1) keys
+int radius_shard_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t radius, uint32_t mpq, uint64_t* d_keys) {
+  TOD_HIP(hipSetDevice(ctx->device));
+  RadiusKeys k{nullptr, 0u};
+  const uint32_t* d_in = nullptr;                           // no searched row: every query's count is 0
+  if (tod_db_n_rows(ctx) != 0) {
+    RadiusWs* ws = tod_ws<RadiusWs>(ctx);
+    TOD_HIP(ws->counts.reserve((size_t)nq * sizeof(uint32_t)));
+    TOD_HIP(ws->in_radius.reserve((size_t)nq * sizeof(uint32_t)));
+    if (int rc = radius_keys(ctx, d_q, nq, radius, mpq, ws->counts.as<uint32_t>(), ws->in_radius.as<uint32_t>(), &k)) return rc;
+    d_in = ws->in_radius.as<uint32_t>();
+  }
+  const size_t slots = (size_t)nq * (mpq + 1u);
+  hipLaunchKernelGGL(radius_shard_keys_kernel, dim3((uint32_t)((slots + kBlock - 1u) / kBlock)), dim3(kBlock), 0, ctx->stream, k.cand, d_in, nq,
+                     mpq, k.cap, (uint32_t)tod_db_first_row(ctx), d_keys);
+  TOD_HIP(hipGetLastError());
+  return TODHIP_OK;
+}
+
+// The sharded form's second half, M1 on `stream` (null: the context's). It reads the context's object table and model points only.
+int radius_merge(todhip_ctx* ctx, hipStream_t stream, const uint64_t* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t mpq,
+                 uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz, uint32_t* d_in_radius) {
+  TOD_HIP(hipSetDevice(ctx->device));
+  const uint32_t elems = n_shards * mpq;                    // <= 64 * 1024
+  const uint32_t qpb = elems <= kBlock / 2 ? kBlock / elems : 1u;
+  auto kern = qpb * elems <= kMergeLdsKeys ? radius_merge_kernel<true> : radius_merge_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((nq + qpb - 1u) / qpb), dim3(kBlock), 0, stream ? stream : ctx->stream, d_keys_all, n_shards, nq, mpq, qpb,
+                     ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), d_counts, d_in_radius, d_matches, d_xyz);
   TOD_HIP(hipGetLastError());
   return TODHIP_OK;
 }
@@ -280,6 +413,17 @@ int radius_args(const todhip_ctx* ctx, uint32_t nq, uint32_t radius, uint32_t mp
   if (ctx->total_rows == 0) return TODHIP_ENODB;
   if (ctx->desc_bytes != 32) return TODHIP_EINVAL;          // a float DB has no Hamming radius
   return TODHIP_OK;
+}
+
+// stream null: the context's
+int merge_radius_shards(todhip_ctx* ctx, hipStream_t stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t mpq,
+                        void* d_counts, void* d_matches, void* d_xyz, void* d_in_radius) {
+  if (!ctx || !d_keys_all || !d_counts || !d_matches || !d_xyz) return TODHIP_EINVAL;
+  if (n_shards == 0 || n_shards > kMaxMergeShards) return TODHIP_EINVAL;
+  int rc = radius_args(ctx, nq, 1u, mpq);                   // (the radius has done its work in the shards)
+  if (rc != TODHIP_OK) return rc;
+  return radius_merge(ctx, stream, reinterpret_cast<const uint64_t*>(d_keys_all), n_shards, nq, mpq, reinterpret_cast<uint32_t*>(d_counts),
+                      reinterpret_cast<todhip_dmatch*>(d_matches), reinterpret_cast<float*>(d_xyz), reinterpret_cast<uint32_t*>(d_in_radius));
 }
 
 }  // namespace
@@ -294,6 +438,29 @@ extern "C" int todhip_match_radius_device(todhip_ctx* ctx, const void* d_q_desc,
                      reinterpret_cast<uint32_t*>(d_in_radius));
   if (rc == TODHIP_OK) { ctx->counters.last_nq = nq; ctx->counters.last_k = max_per_query; }
   return rc;
+}
+
+extern "C" int todhip_match_radius_shard_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint32_t radius, uint32_t max_per_query,
+                                                void* d_keys) {
+  if (!ctx || !d_q_desc || !d_keys) return TODHIP_EINVAL;
+  int rc = radius_args(ctx, nq, radius, max_per_query);
+  if (rc != TODHIP_OK) return rc;
+  rc = radius_shard_keys(ctx, d_q_desc, nq, radius, max_per_query, reinterpret_cast<uint64_t*>(d_keys));
+  if (rc == TODHIP_OK) { ctx->counters.last_nq = nq; ctx->counters.last_k = max_per_query; }
+  return rc;
+}
+
+extern "C" int todhip_merge_radius_shards_device_on(todhip_ctx* ctx, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq,
+                                                    uint32_t max_per_query, void* d_counts, void* d_matches, void* d_matches_xyz,
+                                                    void* d_in_radius) {
+  if (!ctx || !hip_stream) return TODHIP_EINVAL;
+  return merge_radius_shards(ctx, reinterpret_cast<hipStream_t>(hip_stream), d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches,
+                             d_matches_xyz, d_in_radius);
+}
+
+extern "C" int todhip_merge_radius_shards_device(todhip_ctx* ctx, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t max_per_query,
+                                                 void* d_counts, void* d_matches, void* d_matches_xyz, void* d_in_radius) {
+  return merge_radius_shards(ctx, nullptr, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_matches_xyz, d_in_radius);
 }
 
 extern "C" int todhip_match_radius(todhip_ctx* ctx, const uint8_t* q_desc, uint32_t nq, uint32_t radius, uint32_t max_per_query,

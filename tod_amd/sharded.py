@@ -14,6 +14,11 @@ step. One step =
 Per-rank work is constant as ranks are added (B x Q x N distances, B frames verified), the DB is fixed, and frames/s
 grows with the rank count.
 
+With `max_per_query` steps 2-4 carry the true radius search instead (todhip_match_radius_shard_device and
+todhip_merge_radius_shards_device[_on]): a key row is then max_per_query keys and the shard's count of rows inside
+the radius, max_per_query + 1 wide, and the merge returns every query's nearest max_per_query rows within the radius and
+in_radius. The choreography does not change: the key rows are opaque to it.
+
 `ShardedMatcher` is the ONE implementation of steps 1-4's choreography: bench.py runs it on the GPU (GpuOps: torch
 streams/events, RCCL through torch.distributed, libtodhip for the compute) and tests/test_sharded_cpu.py runs the same
 class over gloo with a CPU restatement as the compute. With `overlap` the collectives and the merge have a stream of
@@ -65,12 +70,17 @@ class ShardedMatcher:
 
        begin(n_steps, q_of): q_of(i) -> (this rank's descriptors of step i as a [B, Q, desc_bytes] tensor, event or None
        after which they are complete). step(i, out) issues step i and returns the stream on which `out` becomes complete.
+
+       max_per_query: the radius search (the ops were built for it too). A key row is then max_per_query + 1 wide and `k` is not used.
     """
 
-    def __init__(self, ops, world, rank, frames_per_rank, nq, k, desc_bytes=32, exchange="all_to_all", overlap=True):
+    def __init__(self, ops, world, rank, frames_per_rank, nq, k, desc_bytes=32, exchange="all_to_all", overlap=True, max_per_query=None):
         assert exchange in ("all_to_all", "all_gather")
         self.ops, self.world, self.rank = ops, world, rank
         self.B, self.nq, self.k, self.exchange = frames_per_rank, nq, k, exchange
+        self.max_per_query = max_per_query
+        if max_per_query is not None:
+            k = max_per_query + 1                           # the width of a key row; nothing below looks inside one
         self.overlap = overlap and ops.comm is not ops.compute
         n = frames_per_rank * nq
         depth = 2 if self.overlap else 1
@@ -144,14 +154,16 @@ class ShardedMatcher:
 class GpuOps:
     """ShardedMatcher backend on the GPU: torch streams/events, torch.distributed collectives (backend "nccl" is RCCL
     over xGMI; "gloo" stages through the host -- rehearsals on a one-GPU box only), libtodhip for the compute. `out` is a
-    dict of torch tensors: counts [n] i32, matches [n*k, 4] i32, xyz [n*k, 3] f32 (todhip_match_device's outputs)."""
+    dict of torch tensors: counts [n] i32, matches [n*k, 4] i32, xyz [n*k, 3] f32 (todhip_match_device's outputs). With
+    max_per_query the two calls are the radius pair: matches and xyz have stride max_per_query instead of k and `out` also holds
+    in_radius [n] i32 (todhip_match_radius_device's outputs)."""
 
-    def __init__(self, ctx, compute_stream, comm_stream, backend, k, radius):
+    def __init__(self, ctx, compute_stream, comm_stream, backend, k, radius, max_per_query=None):
         import torch
         import torch.distributed as dist
         self.torch, self.dist = torch, dist
         self.ctx, self.compute, self.comm = ctx, compute_stream, comm_stream
-        self.backend, self.k, self.radius = backend, k, radius
+        self.backend, self.k, self.radius, self.max_per_query = backend, k, radius, max_per_query
         self.world = dist.get_world_size()
 
     def alloc(self, shape, dtype_name):
@@ -187,15 +199,24 @@ class GpuOps:
             out.view(-1).copy_(o.to(out.device))
 
     def match_shard(self, q_all, n, keys_out):
-        self.ctx.match_shard_device(q_all.data_ptr(), n, self.k, self.radius, keys_out.data_ptr())
+        if self.max_per_query is not None:
+            self.ctx.match_radius_shard_device(q_all.data_ptr(), n, self.radius, self.max_per_query, keys_out.data_ptr())
+        else:
+            self.ctx.match_shard_device(q_all.data_ptr(), n, self.k, self.radius, keys_out.data_ptr())
 
     def merge(self, keys_mine, n_shards, n, out, stream):
-        args = (keys_mine.data_ptr(), n_shards, n, self.k, self.radius, out["counts"].data_ptr(), out["matches"].data_ptr(),
-                out["xyz"].data_ptr())
+        if self.max_per_query is not None:
+            args = (keys_mine.data_ptr(), n_shards, n, self.max_per_query, out["counts"].data_ptr(), out["matches"].data_ptr(),
+                    out["xyz"].data_ptr(), out["in_radius"].data_ptr())
+            plain, on = self.ctx.merge_radius_shards_device, self.ctx.merge_radius_shards_device_on
+        else:
+            args = (keys_mine.data_ptr(), n_shards, n, self.k, self.radius, out["counts"].data_ptr(), out["matches"].data_ptr(),
+                    out["xyz"].data_ptr())
+            plain, on = self.ctx.merge_shards_device, self.ctx.merge_shards_device_on
         if stream is self.compute:
-            self.ctx.merge_shards_device(*args)
+            plain(*args)
         else:       # the merge only reads the context's immutable tables: it may run beside the next DB pass
-            self.ctx.merge_shards_device_on(stream.cuda_stream, *args)
+            on(stream.cuda_stream, *args)
 
     def select_objects(self, ids):
         self.compute.synchronize()                      # the context's calls are issued on this stream
