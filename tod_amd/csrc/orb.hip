@@ -11,7 +11,7 @@
 // A batch of frames AND the pyramid levels ride in the last grid dimension of every launch: (level l, frame f) is "virtual
 // frame" l F + f and owns slice l F + f of every workspace buffer and its own row of control words, the per-level geometry
 // comes from a small table in the kernel arguments (LevelTab). A batch of any size and any number of levels therefore costs
-// 13 + (levels - 1) launches (round 1 and most of round 2: 2 + 11 per level), blocks beyond a smaller level's extent leave at once.
+// 12 + (levels - 1) launches (round 1 and most of round 2: 2 + 11 per level), blocks beyond a smaller level's extent leave at once.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -110,11 +110,18 @@ __device__ __forceinline__ int arc9_max(const int (&d)[16]) {
   return best;
 }
 
-__device__ __forceinline__ int fast_score_at(const uint8_t* __restrict__ img, uint32_t h, uint32_t w, int x, int y) {
-  if (x < kEdge - 1 || x >= (int)w - kEdge + 1 || y < kEdge - 1 || y >= (int)h - kEdge + 1) return 0;
-  const uint8_t* c = img + (size_t)y * w + x;
+// four pixels of a row at any byte offset: level rows have pitch w, so a pixel group is not dword-aligned
+__device__ __forceinline__ uint32_t load_px4(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+__device__ __forceinline__ void store_px4(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
+
+// the border rule of the score: positions whose ring or whose non-maximum neighbourhood cannot hold a keypoint score 0 and read nothing
+__device__ __forceinline__ bool fast_in_border(uint32_t h, uint32_t w, int x, int y) {
+  return x < kEdge - 1 || x >= (int)w - kEdge + 1 || y < kEdge - 1 || y >= (int)h - kEdge + 1;
+}
+
+// the score of the pixel at c in an image of row pitch W (a position outside fast_in_border)
+__device__ __forceinline__ int fast_score_at(const uint8_t* c, int W) {
   const int p = c[0];
-  const int W = (int)w;
   int d[16], nd[16];
   d[0] = c[3 * W] - p;       d[1] = c[3 * W + 1] - p;   d[2] = c[2 * W + 2] - p;   d[3] = c[W + 3] - p;
   d[4] = c[3] - p;           d[5] = c[-W + 3] - p;      d[6] = c[-2 * W + 2] - p;  d[7] = c[-3 * W + 1] - p;
@@ -126,10 +133,31 @@ __device__ __forceinline__ int fast_score_at(const uint8_t* __restrict__ img, ui
   return best > kFastThr ? best : 0;
 }
 
+// What a 9-arc above the threshold needs: any 9 contiguous ring pixels hold two cyclically adjacent ones of the compass points
+// (ring positions 0, 4, 8, 12), so two adjacent compass points are both brighter than p + kFastThr or both darker than
+// p - kFastThr wherever fast_score_at is not 0. Same pixels, same comparisons (d > kFastThr, -d > kFastThr) as the score's.
+__device__ __forceinline__ bool fast_compass(const uint8_t* c, int W) {
+  const int p = c[0];
+  const int d0 = c[3 * W] - p, d4 = c[3] - p, d8 = c[-3 * W] - p, d12 = c[-3] - p;
+  const bool b0 = d0 > kFastThr, b4 = d4 > kFastThr, b8 = d8 > kFastThr, b12 = d12 > kFastThr;
+  const bool k0 = -d0 > kFastThr, k4 = -d4 > kFastThr, k8 = -d8 > kFastThr, k12 = -d12 > kFastThr;
+  return (b0 && b4) || (b4 && b8) || (b8 && b12) || (b12 && b0) || (k0 && k4) || (k4 && k8) || (k8 && k12) || (k12 && k0);
+}
+
 // FAST score + 3x3 strict non-maximum suppression + compaction in one pass: a block scores a 64 x 16 pixel tile and
 // its 1-pixel halo into LDS (the score image never goes to memory), then suppresses and appends. The candidate order
 // is fixed later by the ranking kernels, so appends are aggregated per wave (one counter atomic per wave).
+//
+// The score is found in two passes over an LDS copy of the tile's pixels (tile + 1 pixel for the suppression + 3 for the ring,
+// loaded once as dwords; every ring read is an LDS read). Pass 1 visits all (64 + 2) x (16 + 2) positions, applies the border
+// rule and the compass test (fast_compass: necessary for a non-zero score, five pixels instead of seventeen and no arc search)
+// and appends the survivors to an LDS list (ballot + popcount, one LDS atomic per wave). Pass 2 runs the exact score over that
+// list with dense lanes. On textured images 4 % of the positions score and 6-7 % survive pass 1, but they are spread so that
+// most 64-pixel row segments hold one: an early exit that needs a whole wave to fail the test would almost never be taken, so
+// the survivors are compacted instead. On noise every position survives; the list holds them all.
 constexpr int kNmsTileW = 64, kNmsTileH = 16;
+constexpr int kNmsScoreW = kNmsTileW + 2, kNmsScoreN = (kNmsTileH + 2) * kNmsScoreW;     // scored positions: the tile and 1 pixel around
+constexpr int kNmsImgDw = (kNmsTileW + 8) / 4, kNmsImgW = 4 * kNmsImgDw, kNmsImgH = kNmsTileH + 8;   // staged pixels: 4 around
 __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, uint32_t cap, uint32_t* counter, uint32_t* hist,
                                                        const uint8_t* __restrict__ mask, uint32_t H0, uint32_t W0, size_t fs) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
@@ -139,24 +167,59 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, u
   const uint8_t* __restrict__ img = T.img[lvl] + f * fs;
   cand += (size_t)v * cap; counter += v * kCtlWords; hist += v * kCtlWords;
   if (mask) mask += f * fs;
-  __shared__ int s_score[(kNmsTileH + 2) * (kNmsTileW + 2)];
+  __shared__ int s_score[kNmsScoreN];
   __shared__ uint32_t s_hist[256];
+  __shared__ uint32_t s_img[kNmsImgH * kNmsImgDw];          // pixel (x0 - 4 + i, y0 - 4 + r) is byte r * kNmsImgW + i
+  __shared__ uint16_t s_list[kNmsScoreN];                   // pass 1's survivors (positions of s_score), in any order
+  __shared__ uint32_t s_n;
   const int x0 = (int)blockIdx.x * kNmsTileW, y0 = (int)blockIdx.y * kNmsTileH;
-  s_hist[threadIdx.x] = 0u;
-  for (int p = (int)threadIdx.x; p < (kNmsTileH + 2) * (kNmsTileW + 2); p += 256)
-    s_score[p] = fast_score_at(img, h, w, x0 - 1 + p % (kNmsTileW + 2), y0 - 1 + p / (kNmsTileW + 2));
-  __syncthreads();
   const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  s_hist[threadIdx.x] = 0u;
+  if (threadIdx.x == 0) s_n = 0u;
+  // the ring of a position outside the border rule reaches pixels [kEdge - 4, w - kEdge + 4) x [kEdge - 4, h - kEdge + 4): only pixel
+  // groups that hold one of them are loaded, and such a group lies inside its row (kEdge - 4 >= 3), so inside the frame's slice
+  for (int t = (int)threadIdx.x; t < kNmsImgH * kNmsImgDw; t += 256) {
+    const int r = t / kNmsImgDw, x = x0 - 4 + 4 * (t - r * kNmsImgDw), y = y0 - 4 + r;
+    uint32_t px = 0u;
+    if (x + 3 >= kEdge - 4 && x < (int)w - kEdge + 4 && y >= kEdge - 4 && y < (int)h - kEdge + 4) px = load_px4(img + (size_t)y * w + x);
+    s_img[t] = px;
+  }
+  __syncthreads();
+  const uint8_t* s_px = reinterpret_cast<const uint8_t*>(s_img);
+#pragma unroll
+  for (int p0 = 0; p0 < kNmsScoreN; p0 += 256) {             // pass 1
+    const int p = p0 + (int)threadIdx.x, py = p / kNmsScoreW, px = p - py * kNmsScoreW;
+    const bool valid = p < kNmsScoreN;
+    bool go = valid && !fast_in_border(h, w, x0 - 1 + px, y0 - 1 + py);
+    if (go) go = fast_compass(s_px + (py + 3) * kNmsImgW + px + 3, kNmsImgW);
+    if (valid) s_score[p] = 0;
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(go);
+    if (bal != 0ull) {
+      const uint32_t first = (uint32_t)__ffsll((long long)bal) - 1u;
+      uint32_t base = 0;
+      if (lane == first) base = atomicAdd(&s_n, (uint32_t)__popcll(bal));
+      base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)first);
+      if (go) s_list[base + (uint32_t)__popcll(bal & below)] = (uint16_t)p;
+    }
+  }
+  __syncthreads();
+  const uint32_t n_list = s_n;                               // <= kNmsScoreN: every position is appended at most once
+  for (uint32_t i = threadIdx.x; i < n_list; i += 256u) {    // pass 2
+    const int p = s_list[i], py = p / kNmsScoreW, px = p - py * kNmsScoreW;
+    s_score[p] = fast_score_at(s_px + (py + 3) * kNmsImgW + px + 3, kNmsImgW);
+  }
+  __syncthreads();
   const int tx = (int)lane;
 #pragma unroll
   for (int j = 0; j < kNmsTileH / 4; ++j) {
     const int ty = (int)(threadIdx.x >> 6) + 4 * j;
     const uint32_t x = (uint32_t)(x0 + tx), y = (uint32_t)(y0 + ty);
-    const int* c = &s_score[(ty + 1) * (kNmsTileW + 2) + tx + 1];
+    const int* c = &s_score[(ty + 1) * kNmsScoreW + tx + 1];
     const int s = c[0];
     bool keep = s != 0 && !(x < (uint32_t)kEdge || x >= w - kEdge || y < (uint32_t)kEdge || y >= h - kEdge);
     if (keep) {
-      constexpr int R = kNmsTileW + 2;
+      constexpr int R = kNmsScoreW;
       keep = c[-R - 1] < s && c[-R] < s && c[-R + 1] < s && c[-1] < s && c[1] < s && c[R - 1] < s && c[R] < s && c[R + 1] < s;
     }
     if (keep && mask) {   // level-0 mask sampled at the nearest pixel (the training cell passes obs.mask to the detector, Trainer.cpp:144-150)
@@ -170,7 +233,7 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, u
       uint32_t base = 0;
       if (lane == first) base = atomicAdd(counter, (uint32_t)__popcll(bal));
       base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)first);
-      const uint32_t i = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+      const uint32_t i = base + (uint32_t)__popcll(bal & below);
       if (keep && i < cap) {
         Cand cd; cd.x = (int)x; cd.y = (int)y; cd.score = s; cd.harris = 0.f; cand[i] = cd;
         atomicAdd(&s_hist[s & 255], 1u);
@@ -328,78 +391,129 @@ __global__ __launch_bounds__(256) void harris_kernel(LevelTab T, Cand* cand, con
 
 __constant__ int c_gauss7[7] = {18, 33, 49, 56, 49, 33, 18};
 
-__global__ __launch_bounds__(256) void blur_h_kernel(LevelTab T, uint8_t* dst, size_t fs) {
-  TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  const uint32_t lvl = blockIdx.y / T.F, f = blockIdx.y - lvl * T.F, h = T.h[lvl], w = T.w[lvl];
-  if (T.want[lvl] == 0u) return;
-  const uint8_t* __restrict__ src = T.img[lvl] + f * fs;
-  dst += blockIdx.y * fs;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= h * w) return;
-  const int x = (int)(i % w), y = (int)(i / w);
-  int s = 0;
+// The 7-tap sums of two pixels in one register: pixels in bits 0-7 and 16-23, weights summing to 256, so a half-word's sum with
+// the rounding term is at most 255 * 256 + 128 < 2^16 and never carries into its neighbour. Every half-word is the integer
+// s + 128 of sum k c_gauss7[k] * pixel[k], and its bits 8-15 are (s + 128) >> 8.
+constexpr uint32_t kPairMask = 0x00FF00FFu, kPairRound = 0x00800080u;
+__device__ __forceinline__ uint32_t gauss7_pairs(const uint32_t (&g)[7], const uint32_t* q) {
+  uint32_t s = kPairRound;
 #pragma unroll
-  for (int k = -3; k <= 3; ++k) s += c_gauss7[k + 3] * src[(size_t)y * w + clampi(x + k, 0, (int)w - 1)];
-  dst[i] = (uint8_t)((s + 128) >> 8);
+  for (int k = 0; k < 7; ++k) s += g[k] * q[k];
+  return s;
 }
-__global__ __launch_bounds__(256) void blur_v_kernel(LevelTab T, const uint8_t* __restrict__ src, uint8_t* dst, size_t fs) {
+// four result pixels from the sums of pixels (0, 2) and of pixels (1, 3)
+__device__ __forceinline__ uint32_t gauss7_px4(uint32_t even, uint32_t odd) { return ((even >> 8) & kPairMask) | (odd & ~kPairMask); }
+
+// Separable 7-tap Gaussian, replicate border, in one launch: a block writes the horizontally blurred rows of a 128 x 64 pixel tile
+// and of 3 rows above and below it into LDS, then runs the vertical pass from LDS; a lane works on four neighbouring pixels at a
+// time. x is clamped in the horizontal pass; the vertical pass clamps the row index into the horizontally blurred image, so a halo
+// row outside the image is the horizontal blur of row 0 or row h - 1.
+constexpr int kBlurTileW = 128, kBlurTileH = 64, kBlurDw = kBlurTileW / 4, kBlurRows = kBlurTileH + 6, kBlurRun = 8;
+__global__ __launch_bounds__(256) void blur_kernel(LevelTab T, uint8_t* dst, size_t fs) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  const uint32_t lvl = blockIdx.y / T.F, h = T.h[lvl], w = T.w[lvl];
-  if (T.want[lvl] == 0u) return;
-  src += blockIdx.y * fs; dst += blockIdx.y * fs;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= h * w) return;
-  const int x = (int)(i % w), y = (int)(i / w);
-  int s = 0;
+  const uint32_t v = blockIdx.z, lvl = v / T.F, f = v - lvl * T.F;
+  const int h = (int)T.h[lvl], w = (int)T.w[lvl];
+  const int x0 = (int)blockIdx.x * kBlurTileW, y0 = (int)blockIdx.y * kBlurTileH;
+  if (T.want[lvl] == 0u || x0 >= w || y0 >= h) return;      // block-uniform; want != 0: w > 2 kEdge
+  const uint8_t* __restrict__ src = T.img[lvl] + f * fs;
+  dst += v * fs;
+  __shared__ uint32_t s_h[kBlurRows * kBlurDw];             // row r: the horizontal blur of image row clamp(y0 - 3 + r), four pixels a word
+  uint32_t g[7];
 #pragma unroll
-  for (int k = -3; k <= 3; ++k) s += c_gauss7[k + 3] * src[(size_t)clampi(y + k, 0, (int)h - 1) * w + x];
-  dst[i] = (uint8_t)((s + 128) >> 8);
+  for (int k = 0; k < 7; ++k) g[k] = (uint32_t)c_gauss7[k];
+  for (int t = (int)threadIdx.x; t < kBlurRows * kBlurDw; t += 256) {
+    const int x = x0 + 4 * (t % kBlurDw);
+    if (x >= w) continue;
+    const uint8_t* row = src + (size_t)clampi(y0 - 3 + t / kBlurDw, 0, h - 1) * w;
+    // a = pixels x - 4 .. x + 7 of the row, x clamped
+    uint32_t a[3];
+    if (x + 7 < w) {
+      a[1] = load_px4(row + x); a[2] = load_px4(row + x + 4);
+    } else {                                                 // the row ends inside these eight
+      a[1] = 0u; a[2] = 0u;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a[1 + i / 4] |= (uint32_t)row[min(x + i, w - 1)] << (8 * (i % 4));
+    }
+    a[0] = x >= 4 ? load_px4(row + x - 4) : (a[1] & 0xFFu) * 0x01010101u;   // x is a multiple of 4: all four inside or all four pixel 0
+    // q[j]: pixels x - 3 + j and x - 1 + j as a pair; result pixels (x, x + 2) use q[0..6], (x + 1, x + 3) use q[1..7]
+    uint32_t q[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i0 = j + 1, i1 = j + 3;
+      q[j] = ((a[i0 / 4] >> (8 * (i0 % 4))) & 0xFFu) | (((a[i1 / 4] >> (8 * (i1 % 4))) & 0xFFu) << 16);
+    }
+    s_h[t] = gauss7_px4(gauss7_pairs(g, q), gauss7_pairs(g, q + 1));
+  }
+  __syncthreads();
+  // a lane takes four columns and kBlurRun rows: one LDS word per row and a window of seven rows
+  const int c = (int)(threadIdx.x % kBlurDw), r0 = (int)(threadIdx.x / kBlurDw) * kBlurRun, x = x0 + 4 * c;
+  if (x >= w || y0 + r0 >= h) return;
+  uint32_t even[kBlurRun + 6], odd[kBlurRun + 6];
+#pragma unroll
+  for (int i = 0; i < kBlurRun + 6; ++i) {
+    const uint32_t px = s_h[(r0 + i) * kBlurDw + c];
+    even[i] = px & kPairMask; odd[i] = (px >> 8) & kPairMask;
+  }
+#pragma unroll
+  for (int j = 0; j < kBlurRun; ++j) {
+    const int y = y0 + r0 + j;
+    if (y >= h) break;
+    const uint32_t px = gauss7_px4(gauss7_pairs(g, even + j), gauss7_pairs(g, odd + j));
+    uint8_t* o = dst + (size_t)y * w + x;
+    if (x + 3 < w) {
+      store_px4(o, px);
+    } else {
+      for (int i = 0; x + i < w; ++i) o[i] = (uint8_t)(px >> (8 * i));
+    }
+  }
 }
 
 struct DescribeArgs {
-  const uint8_t* img; const uint8_t* blur; uint32_t w;   // img, w, level, scale: filled in from the level table by the kernel
+  const uint8_t* blur;                          // the blurred level images (virtual-frame slices); image, pitch and scale: the level table
   const Cand* sel;                              // the levels' selections (virtual-frame slices)
-  const uint32_t* level_counts; uint32_t level; // per frame: word l = keypoints of level l; output base = sum of the earlier levels' counts
-  float scale; uint32_t cap;
+  const uint32_t* level_counts;                 // per frame: word l = keypoints of level l; output base = sum of the earlier levels' counts
+  uint32_t cap;
   const int8_t* pattern; int umax[kHalfPatch + 2];
   float* kp_xy; float* kp_aux; uint8_t* desc;
   size_t fs; uint32_t sel_fs;                   // frame strides: images; selection (outputs: cap rows, controls: kCtlWords)
 };
 
-// one wave per keypoint: integer moments over the radius-15 disc (lane = row), then 4 tests per lane
-__global__ __launch_bounds__(256) void describe_kernel(LevelTab T, DescribeArgs A) {
+// one wave per keypoint: integer moments over the radius-15 disc (lane = row), then 4 tests per lane. The arguments are only read:
+// umax is indexed by the lane's row, and an argument block that is also written moves to scratch as a whole.
+__global__ __launch_bounds__(256) void describe_kernel(LevelTab T, const DescribeArgs A) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  {
-    const uint32_t v = blockIdx.y, lvl = v / T.F, f = v - lvl * T.F;
-    if (T.want[lvl] == 0u) return;
-    A.img = T.img[lvl] + f * A.fs; A.w = T.w[lvl]; A.level = lvl; A.scale = T.scale[lvl];
-    A.blur += v * A.fs; A.sel += (size_t)v * A.sel_fs;
-    A.level_counts += f * kCtlWords;
-    A.kp_xy += (size_t)f * A.cap * 2; A.kp_aux += (size_t)f * A.cap * 4; A.desc += (size_t)f * A.cap * 32;
-  }
+  const uint32_t v = blockIdx.y, lvl = v / T.F, f = v - lvl * T.F;
+  if (T.want[lvl] == 0u) return;
+  const uint8_t* __restrict__ img = T.img[lvl] + f * A.fs;
+  const uint8_t* __restrict__ blur = A.blur + v * A.fs;
+  const Cand* __restrict__ sel = A.sel + (size_t)v * A.sel_fs;
+  const uint32_t* __restrict__ level_counts = A.level_counts + f * kCtlWords;
+  float* kp_xy = A.kp_xy + (size_t)f * A.cap * 2; float* kp_aux = A.kp_aux + (size_t)f * A.cap * 4;
+  uint8_t* desc = A.desc + (size_t)f * A.cap * 32;
+  const float scale = T.scale[lvl];
   const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6), l = threadIdx.x & 63u;
-  if (i >= A.level_counts[A.level]) return;
+  if (i >= level_counts[lvl]) return;
   uint32_t base = 0;
-  for (uint32_t j = 0; j < A.level; ++j) base += A.level_counts[j];
+  for (uint32_t j = 0; j < lvl; ++j) base += level_counts[j];
   const uint32_t o = base + i;
   if (o >= A.cap) return;
-  const Cand c = A.sel[i];
-  const int x = c.x, y = c.y, W = (int)A.w;
+  const Cand c = sel[i];
+  const int x = c.x, y = c.y, W = (int)T.w[lvl];
   int m10, m01;
-  patch_moments(A.img, W, x, y, A.umax, l, m10, m01);
+  patch_moments(img, W, x, y, A.umax, l, m10, m01);
   const float fm10 = (float)m10, fm01 = (float)m01;
   float ca, sa;
   steer_of(fm10, fm01, ca, sa);
   uint32_t nib = 0;
 #pragma unroll
-  for (int b = 0; b < 4; ++b) nib |= (uint32_t)steered_test(A.blur, W, x, y, ca, sa, A.pattern + 4 * (4 * (int)l + b)) << b;
+  for (int b = 0; b < 4; ++b) nib |= (uint32_t)steered_test(blur, W, x, y, ca, sa, A.pattern + 4 * (4 * (int)l + b)) << b;
   const uint32_t hi = __shfl_down(nib, 1);
-  if ((l & 1u) == 0u) A.desc[(size_t)o * 32 + (l >> 1)] = (uint8_t)(nib | (hi << 4));
+  if ((l & 1u) == 0u) desc[(size_t)o * 32 + (l >> 1)] = (uint8_t)(nib | (hi << 4));
   if (l == 0) {
     float ang = atan2f(fm01, fm10) * 57.29577951308232f;
     if (ang < 0.f) ang += 360.f;
-    A.kp_xy[2 * o] = (float)x * A.scale; A.kp_xy[2 * o + 1] = (float)y * A.scale;
-    A.kp_aux[4 * o] = 31.f * A.scale; A.kp_aux[4 * o + 1] = ang; A.kp_aux[4 * o + 2] = c.harris; A.kp_aux[4 * o + 3] = (float)A.level;
+    kp_xy[2 * o] = (float)x * scale; kp_xy[2 * o + 1] = (float)y * scale;
+    kp_aux[4 * o] = 31.f * scale; kp_aux[4 * o + 1] = ang; kp_aux[4 * o + 2] = c.harris; kp_aux[4 * o + 3] = (float)lvl;
   }
 }
 
@@ -425,7 +539,7 @@ __global__ __launch_bounds__(256) void copy_out_kernel(const uint32_t* __restric
 
 struct OrbWs : TodWs {
   static constexpr int kSlot = kWsOrb;
-  DevBuf pyr, blur, tmp, score, cand, eq, sel1, sel2, small, pattern, in_img, kp_xy, kp_aux, desc, o_xy, o_aux, o_desc, maskbuf;
+  DevBuf pyr, blur, score, cand, eq, sel1, sel2, small, pattern, in_img, kp_xy, kp_aux, desc, o_xy, o_aux, o_desc, maskbuf;
   HostBuf h_out, h_kp;                                     // h_kp: the host form's keypoints, written by copy_out_kernel itself
   bool pattern_is_default = false;
   // the per-frame launch sequence is static for a given geometry: captured once per context, replayed. It reads
@@ -507,7 +621,7 @@ int orb_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uin
     return TODHIP_OK;
   }
   TOD_HIP(ws->pyr.reserve(V * px));
-  TOD_HIP(ws->blur.reserve(V * px)); TOD_HIP(ws->tmp.reserve(V * px));
+  TOD_HIP(ws->blur.reserve(V * px));
   TOD_HIP(ws->cand.reserve(V * cand_cap * sizeof(Cand)));
   TOD_HIP(ws->eq.reserve(V * cand_cap * sizeof(Cand)));
   TOD_HIP(ws->sel1.reserve(V * sel1_cap * sizeof(Cand)));
@@ -577,8 +691,8 @@ int orb_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uin
       hipLaunchKernelGGL(rank_tiled_kernel, dim3((2u * want_max + 255u) / 256u, Vg), dim3(256), 0, st, ws->sel1.as<Cand>(),
                          d_small + W_NSEL1, d_small + W_WANT, 0u, 1, ws->sel2.as<Cand>(), (const uint32_t*)nullptr, d_cnt + 8,
                          sel1_cap, sel2_cap, F);
-      hipLaunchKernelGGL(blur_h_kernel, dim3(px_blocks, Vg), dim3(256), 0, st, T, ws->tmp.as<uint8_t>(), px);
-      hipLaunchKernelGGL(blur_v_kernel, dim3(px_blocks, Vg), dim3(256), 0, st, T, ws->tmp.as<uint8_t>(), ws->blur.as<uint8_t>(), px);
+      hipLaunchKernelGGL(blur_kernel, dim3((W + kBlurTileW - 1) / kBlurTileW, (H + kBlurTileH - 1) / kBlurTileH, Vg), dim3(256), 0, st, T,
+                         ws->blur.as<uint8_t>(), px);
       DescribeArgs D;
       std::memset(&D, 0, sizeof(D));
       disc_umax(D.umax);
