@@ -70,6 +70,8 @@ typedef struct {
   /* matrix-core matcher, launches with split blocks (partial-distance elimination): accumulator blocks started as
    * parts, and those that went on to their second part -- cumulative over the context's life, as of the last report read */
   uint64_t k4x_half_blocks, k4x_half_blocks_completed;
+  uint32_t last_fp4_rows;             /* matrix-core matcher: 1 if the last launch read the rows from their resident fp4 copy */
+  uint32_t fp4_rows_builds;           /* ... and how often this context has built that copy (once per change of the searched rows) */
 } todhip_counters;
 
 /* ---- lifetime ---------------------------------------------------------------------------------- */

@@ -1,0 +1,98 @@
+"""Child of tests/test_match_fp4_rows_gpu.py (TODHIP_K4X_FP4_ROWS and TODHIP_K4X_QT are read once per process): the matrix-core search
+over the resident fp4 copy of the rows against the vector-ALU engine in the same process, bit for bit, in every block form."""
+import itertools
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tod_amd import capi
+
+FIELDS = ("queryIdx", "trainIdx", "imgIdx", "distance")
+
+
+def flip(rows, rng, n_bits):
+    out = rows.copy()
+    for i in range(len(out)):
+        for b in rng.choice(256, n_bits, replace=False):
+            out[i, b >> 3] ^= np.uint8(1 << (b & 7))
+    return out
+
+
+def make(kind, n_rows, nq, seed):
+    """kind 0: independent bits, a third of the queries near a row; 1 / 2: every row equals one query on its first 128 / 192 bit
+    positions, so the split blocks go on to their second part; 3: rows drawn from 40 distinct ones (ties, broken by the row index)"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    if kind == 3:
+        pool = rng.integers(0, 256, (40, 32), dtype=np.uint8)
+        desc = pool[rng.integers(0, 40, n_rows)]
+        q = flip(pool[rng.integers(0, 40, nq)], rng, 9)
+    else:
+        desc = rng.integers(0, 256, (n_rows, 32), dtype=np.uint8)
+        q = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+        near = rng.choice(nq, nq // 3, replace=False)
+        q[near] = flip(desc[rng.integers(0, n_rows, len(near))], rng, 20)
+        if kind in (1, 2):
+            nb = 16 if kind == 1 else 24
+            desc[:, :nb] = q[np.arange(n_rows) % nq, :nb]
+    pts = rng.random((n_rows, 3), dtype=np.float32)
+    off = np.array([0, n_rows // 3, 2 * n_rows // 3, n_rows], np.uint32)
+    return np.ascontiguousarray(desc), pts, off, np.ascontiguousarray(q)
+
+
+def same(a, b):
+    return np.array_equal(a[0], b[0]) and all(np.array_equal(a[1][f], b[1][f]) for f in FIELDS) and np.array_equal(a[2], b[2])
+
+
+def compare(ctx, q, ks, radii, splits, what):
+    n = 0
+    for k, radius in itertools.product(ks, radii):
+        ctx.set_matcher_engine("valu")
+        want = ctx.match(q, k, radius)
+        ctx.set_matcher_engine("mfma")
+        for split in splits:
+            ctx.set_matcher_block_split(split)
+            got = ctx.match(q, k, radius)
+            cnt = ctx.counters()
+            lowest = 2 if radius + 1 <= 64 else (3 if radius + 1 <= 96 else 4)     # the lowest split the thresholds allow
+            form = 4 if split == 0 else max(split, lowest)
+            assert cnt.last_fp4_rows == 1 and cnt.last_block_split == form, (what, k, radius, split, cnt.last_fp4_rows, cnt.last_block_split)
+            assert same(got, want), (what, k, radius, split)
+            n += 1
+    ctx.set_matcher_block_split(-1)
+    return n
+
+
+def main():
+    assert os.environ.get("TODHIP_K4X_FP4_ROWS") == "1" and os.environ.get("TODHIP_K4X_QT") in ("4", "6")
+    ctx = capi.Context(0)
+    n, builds = 0, 0
+    for kind, n_rows, nq in itertools.product((0, 1, 2, 3), (4096, 4113, 8191), (129, 200)):
+        desc, pts, off, q = make(kind, n_rows, nq, 1000 * kind + n_rows + nq)
+        ctx.db_load(desc, pts, off)
+        n += compare(ctx, q, (1, 2, 5), (35, 64, 96, 255), (0, 2, 3), (kind, n_rows, nq))
+        builds += 1
+        assert ctx.counters().fp4_rows_builds == builds                    # one copy per load, whatever the number of launches
+    # the copy follows the rows: a second load on the same context (above, 23 times), a selection on and off, the bit order on and off
+    desc, pts, off, q = make(1, 4113, 200, 7)
+    ctx.db_load(desc, pts, off)
+    n += compare(ctx, q, (2,), (35, 96), (0, 2, 3), "load")
+    for ids in ([0, 2], [1], None):
+        ctx.select_objects(ids)
+        n += compare(ctx, q, (2,), (35, 96), (0, 2, 3), ("select", ids))
+    assert ctx.counters().fp4_rows_builds == builds + 4
+    for mode in (1, 0):
+        ctx.set_db_bit_order(mode)
+        ctx.db_load(desc, pts, off)
+        n += compare(ctx, q, (2,), (35, 96), (0, 2, 3), ("bit order", mode))
+    ctx.select_objects([2, 1])
+    ctx.set_db_bit_order(1)
+    ctx.db_load(desc, pts, off)                                              # a load selects all objects again
+    n += compare(ctx, q, (1, 5), (64, 255), (0, 3), "load over a selection")
+    ctx.close()
+    print("ok %d" % n)
+
+
+if __name__ == "__main__":
+    main()

@@ -52,7 +52,7 @@ class Counters(C.Structure):
                 ("last_match_kernel_ms", C.c_double), ("sum_match_kernel_ms", C.c_double),
                 ("n_match_kernel_launches", C.c_uint64), ("last_sprint_launches", C.c_uint32), ("last_sprint_rounds", C.c_uint32),
                 ("last_verify_ticks", C.c_uint32), ("last_block_split", C.c_uint32), ("k4x_half_blocks", C.c_uint64),
-                ("k4x_half_blocks_completed", C.c_uint64)]
+                ("k4x_half_blocks_completed", C.c_uint64), ("last_fp4_rows", C.c_uint32), ("fp4_rows_builds", C.c_uint32)]
 
 
 class PipelineParams(C.Structure):

@@ -199,6 +199,7 @@ static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_o
   if (desc_bytes != 32 && desc_bytes != 64 && !(desc_bytes == 512 && shard_count == 1)) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
   tod_view_reset(ctx);                                      // todhip_db_select_objects: a load selects all objects
+  tod_db_rows_written(ctx);                                 // the fp4 copy of the old rows is stale (match_launch.h builds the next)
   ctx->h_obj_off.assign(n_objs + 1, 0u);
   uint64_t total = 0;
   for (uint32_t o = 0; o < n_objs; ++o) {
@@ -234,6 +235,7 @@ static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_o
   ctx->counters.db_objects = n_objs;
 
   TOD_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->db_fp4.release();                                    // nothing reads it any more; a DB that never needs one holds none
   TOD_HIP(ctx->db_desc.reserve((size_t)ctx->shard_rows * desc_bytes + kDbSlackBytes));   // (the matrix-core matcher's last step reads into the slack)
   TOD_HIP(ctx->db_pts.reserve((size_t)total * 3 * sizeof(float) + 16));
   TOD_HIP(ctx->db_obj_off.reserve((size_t)(n_objs + 1) * sizeof(uint32_t)));

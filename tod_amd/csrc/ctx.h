@@ -12,6 +12,7 @@
 
 #include "../../include/todhip.h"
 #include "db_select.h"
+#include "fp4_rows.h"
 #include "match_split.h"
 #include "match_tiles.h"
 
@@ -147,6 +148,12 @@ struct todhip_ctx {
   bool sel_on = false;
   TodViewTables sel;
   DevBuf view_desc, view_tab;
+  // The resident fp4 copy of the active 32-byte rows (tod_db_rows; layout: fp4_rows.h), read by hamming_topk_fp4rows instead of
+  // expanding every row in every launch. Built by the first launch that reads it (match_launch.h) and again whenever the rows it
+  // was built from have changed: rows_gen counts the writes of db_desc / view_desc and the switches between them
+  // (tod_db_rows_written), fp4_gen is the count the copy was built at (0: no copy).
+  DevBuf db_fp4;
+  uint64_t rows_gen = 1, fp4_gen = 0;
 
   std::vector<todhip_round_trace> traces;
 
@@ -160,6 +167,9 @@ struct todhip_ctx {
 inline const void* tod_db_rows(const todhip_ctx* ctx) { return ctx->sel_on ? ctx->view_desc.p : ctx->db_desc.p; }
 inline uint64_t tod_db_n_rows(const todhip_ctx* ctx) { return ctx->sel_on ? ctx->sel.view_rows() : ctx->shard_rows; }
 inline uint64_t tod_db_first_row(const todhip_ctx* ctx) { return ctx->sel_on ? 0ull : ctx->shard_first; }
+// Every writer of what tod_db_rows returns says so (todhip_db_load, todhip_db_select_objects on and off, todhip_set_db_bit_order):
+// what was derived from the rows (the fp4 copy) is stale from here on
+inline void tod_db_rows_written(todhip_ctx* ctx) { ++ctx->rows_gen; }
 
 template <typename T> T* tod_ws(todhip_ctx* ctx) {
   std::unique_ptr<TodWs>& s = ctx->ws[T::kSlot];

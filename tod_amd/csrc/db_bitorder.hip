@@ -87,6 +87,7 @@ int launch_permute(todhip_ctx* ctx, const void* src, void* dst, uint32_t n_rows)
 // measure, decide and rewrite the rows in place (never a byte behind row shard_rows - 1); otherwise back to the identity.
 int tod_bit_order_load(todhip_ctx* ctx) {
   ctx->bit_order_on = false;
+  tod_db_rows_written(ctx);                                            // (the load has said so already; the rewrite below is a write of its own)
   for (int p = 0; p < 256; ++p) ctx->bit_src_of[p] = (uint8_t)p;
   if (ctx->bit_order_mode != TODHIP_BIT_ORDER_INFORMATIVE_FIRST || ctx->desc_bytes != 32 || ctx->shard_rows == 0) return TODHIP_OK;
   if (ctx->shard_rows > 0xFFFFFFFFull) return TODHIP_EINVAL;
@@ -122,6 +123,7 @@ int tod_bit_order_queries(todhip_ctx* ctx, const void* d_q, uint32_t nq, const v
 extern "C" int todhip_set_db_bit_order(todhip_ctx* ctx, int mode) {
   if (!ctx || (mode != TODHIP_BIT_ORDER_NONE && mode != TODHIP_BIT_ORDER_INFORMATIVE_FIRST)) return TODHIP_EINVAL;
   ctx->bit_order_mode = mode;
+  tod_db_rows_written(ctx);                                            // the next load stores the rows in another order
   return TODHIP_OK;
 }
 

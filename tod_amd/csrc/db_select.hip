@@ -117,6 +117,7 @@ extern "C" int todhip_db_select_objects(todhip_ctx* ctx, const uint32_t* ids, ui
   if (ids && !tod_view_build(ids, n_ids, ctx->h_obj_off.data(), ctx->n_objs, ctx->shard_first, ctx->shard_rows, &t)) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
   TOD_HIP(hipStreamSynchronize(ctx->stream));
+  tod_db_rows_written(ctx);                                  // on or off: the searches read other rows from here on
   // every object listed is the state after a load: today's pointers, no second copy of the rows
   const bool all = !ids || t.objs.size() == ctx->n_objs;
   if (all) {

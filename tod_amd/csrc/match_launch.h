@@ -16,16 +16,44 @@ struct MatchEnv {
   int k4x_qt;           // TODHIP_K4X_QT=2|4|6|8           K4x: query blocks per wave, also for <= 32 queries (0: by launch shape)
   int k4x_half;         // TODHIP_K4X_HALF=0|2|3           the process's default for todhip_set_matcher_block_split (-1: adaptive; 1 = 2)
   bool k4x_half_debug;  // TODHIP_K4X_HALF_DEBUG           print every report of the split controller to stderr
+  int k4x_fp4_rows;     // TODHIP_K4X_FP4_ROWS=0|1         K4x: launches of 4 or 6 query blocks per wave read the rows from their resident fp4 copy (1)
+  int k4x_fp4_rows_mb;  // TODHIP_K4X_FP4_ROWS_MB=n        K4x: the largest fp4 copy a context builds, in MiB (512); beyond it the packed rows are read
 };
 inline const MatchEnv& match_env() {
   static const MatchEnv env = [] {
     auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
     const char* eng = getenv("TODHIP_K4_ENGINE");
     return MatchEnv{eng ? eng[0] : '\0', num("TODHIP_K4_MODE", -1), num("TODHIP_K4_WAVES_PER_CU", 0), num("TODHIP_K4X_WAVES_PER_CU", 0),
-                    num("TODHIP_K4X_SHARE", 16), num("TODHIP_K4X_QT", 0), num("TODHIP_K4X_HALF", -1), getenv("TODHIP_K4X_HALF_DEBUG") != nullptr};
+                    num("TODHIP_K4X_SHARE", 16), num("TODHIP_K4X_QT", 0), num("TODHIP_K4X_HALF", -1), getenv("TODHIP_K4X_HALF_DEBUG") != nullptr,
+                    num("TODHIP_K4X_FP4_ROWS", 1), num("TODHIP_K4X_FP4_ROWS_MB", 512)};
   }();
   return env;
 }
+
+// The fp4 copy of the active rows (ctx.h: db_fp4; layout fp4_rows.h) for a launch that reads it: built here the first time, and again
+// when the rows have changed since (tod_db_rows_written). *out stays nullptr where no copy is kept -- switched off, or larger than the
+// cap -- and the launch reads the packed rows. The packed rows are readable up to the end of their last 32-row step (kDbSlackBytes).
+inline int fp4_rows_ready(todhip_ctx* ctx, uint32_t n_rows, const uint4** out) {
+  const MatchEnv& env = match_env();
+  const size_t bytes = fp4_rows_bytes(n_rows);
+  if (env.k4x_fp4_rows == 0 || bytes > ((size_t)std::max(0, env.k4x_fp4_rows_mb) << 20) || bytes >= (1ull << 32)) return TODHIP_OK;   // (32-bit offsets)
+  if (ctx->fp4_gen != ctx->rows_gen) {
+    TOD_HIP(ctx->db_fp4.reserve(bytes));
+    hipLaunchKernelGGL(expand_rows_fp4_kernel, dim3(fp4_rows_steps(n_rows)), dim3(kBlock), 0, ctx->stream,
+                       reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), fp4_rows_steps(n_rows), ctx->db_fp4.as<uint4>());
+    TOD_HIP(hipGetLastError());
+    ctx->fp4_gen = ctx->rows_gen;
+    ++ctx->counters.fp4_rows_builds;
+  }
+  *out = ctx->db_fp4.as<uint4>();
+  return TODHIP_OK;
+}
+// Which launches read the copy: every one of 4 or 6 query blocks per wave, in every block form. The copy takes the expansion (a third of
+// a split step's vector instructions) out of a loop bound by vector issue and puts four times the bytes through the vector L1 instead;
+// measured alone (tools/time_fp4_rows.sh, profiles/match_fp4_rows.json) that pays in each form at 32 000 x 1M (split 2: 1.57 -> 1.43 ms,
+// split 3: 1.88 -> 1.82, whole blocks: 2.32 -> 2.28) and from one frame per launch on (1000 x 1M, 8 query waves per tile: 0.102 -> 0.098;
+// 4000 queries tie at 0.26), so there is no floor on the launch size. Eight blocks per wave keep the packed rows (no room for two
+// steps' fragments), two blocks and the <= 32-query form are bound by HBM, where four times the bytes would cost four times the time.
 
 template <int K, int QT>
 int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
@@ -74,10 +102,26 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
               : (cut <= 128u ? hamming_topk_mfma<K, QT, 1, PF2> : hamming_topk_mfma<K, QT, 0, PF2>);
   ctx->counters.last_block_split = split;
   uint32_t* const d_stats = split < 4 ? ctx->k4x_stats_dev.as<uint32_t>() : nullptr;
-  hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream,
-                     reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw, n_qw64,
-                     t.blocks_per_xcd, t.tiles_per_xcd, cut, (uint32_t)std::max(2, env.k4x_share), ctx->m_part.as<uint32_t>(),
-                     ctx->m_bound.as<uint32_t>(), d_stored, d_stats ? d_stats + 2u * (split - 2u) : nullptr);
+  const uint4* rows_fp4 = nullptr;                                     // the fp4 copy, where this launch reads it
+  if ((QT == 4 || QT == 6) && t.rows_per_tile % 32u == 0u)          // (a tile starts on a step of the copy: mfma_tile_rows gives whole steps)
+    if (int rc = fp4_rows_ready(ctx, n_rows, &rows_fp4)) return rc;
+  ctx->counters.last_fp4_rows = rows_fp4 ? 1u : 0u;
+  if constexpr (QT == 4 || QT == 6) {                                  // (eight blocks per wave leave no room for two steps' fragments)
+    if (rows_fp4) {
+      auto kern4 = split == 2 ? hamming_topk_fp4rows<K, QT, 2>
+                   : split == 3 ? hamming_topk_fp4rows<K, QT, 3>
+                   : (cut <= 128u ? hamming_topk_fp4rows<K, QT, 1> : hamming_topk_fp4rows<K, QT, 0>);
+      hipLaunchKernelGGL(kern4, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream, rows_fp4, d_q, n_rows, nq, nq_pad,
+                         t.rows_per_tile, t.n_tiles, n_qw, n_qw64, t.blocks_per_xcd, t.tiles_per_xcd, cut,
+                         (uint32_t)std::max(2, env.k4x_share), ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored,
+                         d_stats ? d_stats + 2u * (split - 2u) : nullptr);
+    }
+  }
+  if (!rows_fp4)
+    hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream,
+                       reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw, n_qw64,
+                       t.blocks_per_xcd, t.tiles_per_xcd, cut, (uint32_t)std::max(2, env.k4x_share), ctx->m_part.as<uint32_t>(),
+                       ctx->m_bound.as<uint32_t>(), d_stored, d_stats ? d_stats + 2u * (split - 2u) : nullptr);
   if (int rc = timer.end()) return rc;
   if (d_stats) ++ctx->k4x.seq_sent;
   if (nq <= 64u && !d_stats && t.n_tiles >= 256u) return launch_merge_wave<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, d_lists, n_lists);
@@ -96,6 +140,7 @@ int launch_topk_mfma_q32(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint
   KernelTimer timer{ctx};
   if (int rc = timer.begin()) return rc;
   auto kern = cut <= 128u ? hamming_topk_mfma_q32<K, true> : hamming_topk_mfma_q32<K, false>;
+  ctx->counters.last_fp4_rows = 0;                                    // one query block per wave: the packed rows, bound by HBM
   hipLaunchKernelGGL(kern, dim3((t.n_tiles + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, ctx->stream,
                      reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw64, cut,
                      (uint32_t)std::max(4, match_env().k4x_share), ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored);
