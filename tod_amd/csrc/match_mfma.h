@@ -427,16 +427,31 @@ struct Fp4StepLoader {
   }
 };
 
+// mfma_block_test_part for this pass: the same test and the same completion, written for the path that all but one block in 2200 take
+// on independent bits. The block that goes on is the unlikely side, so hipcc lays the completion (the other MFMAs, the second test, the
+// walk) out behind the loop and the hot loop falls through from block to block instead of jumping over 1.2 KB per block; and the count
+// of such blocks (half_stats) is bumped here, where it happens, as one wave-uniform counter -- a 0/1 flag per block, summed per trip,
+// cost the fast path a join block and an s_add each (tools/mfma_valu_overlap.hip prices both; profiles/match_fastpath.json).
+template <int K, int SPLIT>
+__device__ __forceinline__ void fp4rows_block_test_part(mfma_f32x16& acc, const Fp4Row& rows, const Fp4Row& q, float& thr, float& thrp,
+                                                        uint32_t r_lane, uint32_t n_lim, uint32_t (&best)[K], uint32_t& n_pass) {
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(block_reaches<true, false>(acc, thrp)) == 0ull, 1)) return;
+  ++n_pass;
+#pragma unroll
+  for (int s = SPLIT; s < 4; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(rows.s[s], q.s[s], acc, 4, 4, 0, 0, 0, 0);
+  mfma_block_test<K, false, true>(acc, thr, r_lane, n_lim, best);
+  thrp = thr - 64.f * (float)(4 - SPLIT);
+}
+
 // mfma_step on the copy: the fragments of step next_step go straight into a_next, which holds the rows of the step BEFORE this one
 // until then. Those are dead but for the block carried in from that step, which completes at t == 0 with its s[SPLIT .. 3]: the
 // fragments below SPLIT are loaded at once (all four with whole blocks), the others behind that test. Nothing else differs.
 template <int K, int QT, bool MASK, bool IMAX, int SPLIT = 0>
-__device__ __forceinline__ uint32_t fp4rows_step(const Fp4Row& a, Fp4Row& a_next, const Fp4StepLoader& rows, uint32_t next_step,
-                                                 const Fp4Row (&qb)[QT], float (&thr)[QT], float (&thrp)[QT], uint32_t (&best)[QT][K],
-                                                 mfma_f32x16& acc_even, mfma_f32x16& acc_odd, uint32_t r_lane, uint32_t n_lim) {
+__device__ __forceinline__ void fp4rows_step(const Fp4Row& a, Fp4Row& a_next, const Fp4StepLoader& rows, uint32_t next_step,
+                                             const Fp4Row (&qb)[QT], float (&thr)[QT], float (&thrp)[QT], uint32_t (&best)[QT][K],
+                                             mfma_f32x16& acc_even, mfma_f32x16& acc_odd, uint32_t r_lane, uint32_t n_lim, uint32_t& n_pass) {
   constexpr bool HALF = SPLIT != 0;
   constexpr int kEarly = HALF ? SPLIT : 4;
-  uint32_t n_pass = 0;                                     // SPLIT: blocks that went on to their second part (wave-uniform)
   static_assert(!(HALF && MASK) && !(HALF && !IMAX) && QT >= 4, "split blocks: unmasked steps, integer maximum; >= 4 query blocks");
   static_assert(SPLIT == 0 || SPLIT == 2 || SPLIT == 3, "2 or 3 of the 4 MFMAs first");
 #pragma unroll
@@ -452,14 +467,13 @@ __device__ __forceinline__ uint32_t fp4rows_step(const Fp4Row& a, Fp4Row& a_next
       for (int m = kEarly; m < 4; ++m) a_next.s[m] = rows.template load<!HALF>(next_step, m);
     }
     if (HALF) {
-      if (t == 0) n_pass += mfma_block_test_part<K, HALF ? SPLIT : 2>(acc_odd, a_next, qb[QT - 1], thr[QT - 1], thrp[QT - 1], r_lane - 32u, n_lim, best[QT - 1]) ? 1u : 0u;   // previous step's last block, its rows
-      else n_pass += mfma_block_test_part<K, HALF ? SPLIT : 2>((t & 1) ? acc_even : acc_odd, a, qb[t - 1], thr[t - 1], thrp[t - 1], r_lane, n_lim, best[t - 1]) ? 1u : 0u;
+      if (t == 0) fp4rows_block_test_part<K, HALF ? SPLIT : 2>(acc_odd, a_next, qb[QT - 1], thr[QT - 1], thrp[QT - 1], r_lane - 32u, n_lim, best[QT - 1], n_pass);   // previous step's last block, its rows
+      else fp4rows_block_test_part<K, HALF ? SPLIT : 2>((t & 1) ? acc_even : acc_odd, a, qb[t - 1], thr[t - 1], thrp[t - 1], r_lane, n_lim, best[t - 1], n_pass);
     } else {
       if (t == 0) mfma_block_test<K, MASK, IMAX>(acc_odd, thr[QT - 1], r_lane - 32u, n_lim, best[QT - 1]);   // previous step's last block
       else mfma_block_test<K, MASK, IMAX>((t & 1) ? acc_even : acc_odd, thr[t - 1], r_lane, n_lim, best[t - 1]);
     }
   }
-  return n_pass;
 }
 
 // hamming_topk_mfma with the rows read from their fp4 copy (rows_fp4: fp4_rows.h's layout of the rows the packed pass would read;
@@ -520,9 +534,16 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
 #pragma unroll
   for (int t = 0; t < QT; ++t) seen[t] = 0xFFFFFFFFu;                // "nothing published"
   uint32_t next_share = 2u, step = 0, n_pass = 0;
+  // Static priority for half of the workgroups, set once in front of the loop: the two waves of a SIMD run the same program, and at
+  // equal priority the older one wins every arbitration. Workgroups are dealt out over the 8 XCDs and then over an XCD's 32 CUs, so
+  // bit 5 of the slot tells a CU's first workgroup from its second in the first round and splits the later ones evenly. Measured at
+  // 32 000 x 1M, split 2, alternating: 1.378 -> 1.353 ms (profiles/match_fastpath.json); it changes no result. Only in the form it
+  // was measured to pay in, split 2 with six query blocks: raised everywhere it also outranked ORB's and the verifier's kernels in
+  // the chained pipeline, whose DB runs whole blocks or split 3 (one run: 10 428 -> 9 522 frames/s), and whole blocks gained 0.7 %.
+  if (MODE == 2 && QT == 6 && ((slot >> 5) & 1u)) __builtin_amdgcn_s_setprio(1);
   for (; step + 2u <= n_full; step += 2u) {                           // two steps per trip: the fragments ping-pong between a0 and a1
-    n_pass += fp4rows_step<K, QT, false, IMAX, HALF>(a0, a1, rows, step + 1u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local);
-    n_pass += fp4rows_step<K, QT, false, IMAX, HALF>(a1, a0, rows, step + 2u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local);
+    fp4rows_step<K, QT, false, IMAX, HALF>(a0, a1, rows, step + 1u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local, n_pass);
+    fp4rows_step<K, QT, false, IMAX, HALF>(a1, a0, rows, step + 2u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, n_pass);
     if (step + 2u >= next_share) {                                    // wave-uniform
       next_share += share_period;
       exchange_bounds<K, QT, HALF>(bound, q0, c, nq, best, seen, thr, thrp);
@@ -530,13 +551,13 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
   }
   // the last unmasked step's last block is still a part: it completes here, with that step's rows (a1)
   if (HALF && step > 0u) {
-    n_pass += mfma_block_test_part<K, HALF ? HALF : 2>(acc_odd, a1, qb[QT - 1], thr[QT - 1], thrp[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 1]) ? 1u : 0u;
+    fp4rows_block_test_part<K, HALF ? HALF : 2>(acc_odd, a1, qb[QT - 1], thr[QT - 1], thrp[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 1], n_pass);
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
     if (lane == 0 && half_stats) { atomicAdd(half_stats, n_pass); atomicAdd(half_stats + 1, step * (uint32_t)QT); }
   }
   for (; step < n_steps; ++step) {                                    // at most one full and one partial step: masked, whole blocks
-    fp4rows_step<K, QT, true, IMAX>(a0, a1, rows, step + 1u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local);
+    fp4rows_step<K, QT, true, IMAX>(a0, a1, rows, step + 1u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local, n_pass);
     a0 = a1;
   }
   mfma_block_test<K, true, IMAX>(acc_odd, thr[QT - 1], lane_row_base(n_steps - 1u, h), n_local, best[QT - 1]);   // drain

@@ -175,11 +175,182 @@ double run(const char* what, int n_cu, float* d_out, unsigned* d_sink) {
   return ns;
 }
 
+// ---- The fast path of hamming_topk_fp4rows<2, 6, 2> (tod_amd/csrc/match_mfma.h), one ingredient at a time on the "2 MFMAs + tree
+// test" loop above. kp<0,0,0,0> is that loop in the product's shape: six query blocks per 32-row step, two steps per trip, the step's
+// last test carried into the next step's block 0, a tiny slow path that counts itself. The ingredients:
+//   LOADS  the rows come from a 128 MB fp4 copy, four 1 KB buffer loads per step addressed as Fp4StepLoader does (lane offset in the
+//          vector operand, step offset scalar, clamped to the tile's last step), two in front of block 0's test and two behind it; the
+//          first two feed the next step's MFMAs, the other two only the slow path, as in the product
+//   FLAG   every block's 0/1 "went on" flag, summed per trip (the product's n_pass); without it the slow path bumps a counter itself
+//   BIG    the slow path inline behind each test at the product's size: two more MFMAs, a second tree test, the 16-row walk into a
+//          2-entry list, the threshold update -- never executed (thr = 1e30), so the fast path is the taken side of a far branch
+//   TAIL   the per-trip remainder: the lane's row base and the share-period test with its (never taken) exchange of bounds
+//   COLD   the slow path marked unlikely: hipcc lays it out behind the loop and the fast path falls through (what the product does now)
+// The clock climbs over the first launches of a process and differs between these loops (1.9 - 2.3 GHz seen): a warm-up runs first, and
+// tools/match_fastpath.sh clock gives every line in cycles as well. Compare variants in cycles.
+// 16 tiles of 2048 steps; the 128 waves of 32 workgroups with equal blockIdx.x % 8 read one tile together (the product: 167 query waves).
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kQT = 6, kTileSteps = 2048, kTiles = 16;
+struct Row { i32x8 s[4]; };
+
+__device__ __forceinline__ i32x8 frag(__amdgpu_buffer_rsrc_t rs, unsigned lane_off, unsigned step_off, int m) {
+  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(lane_off + m * 1024u), (int)step_off, 0);
+  return i32x8{(int)v.x, (int)v.y, (int)v.z, (int)v.w, 0, 0, 0, 0};
+}
+
+template <bool FLAG, bool BIG, bool COLD>
+__device__ __forceinline__ bool part_test(f32x16& acc, const Row& rows, const Row& q, float& thr, float& thrp, unsigned r_lane,
+                                          unsigned (&best)[2], unsigned& hits, unsigned* sink) {
+  const bool none = __builtin_amdgcn_ballot_w64(test<2>(acc, thrp)) == 0ull;
+  if (COLD ? __builtin_expect(none, 1) : none) return false;
+  if (!FLAG) ++hits;
+  if (!BIG) {
+    thrp += 1.f;
+    asm volatile("global_store_dword %0, %1, off" :: "v"(sink + (threadIdx.x & 63u)), "v"(thrp) : "memory");
+    return true;
+  }
+#pragma unroll
+  for (int s = 2; s < 4; ++s) acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(rows.s[s], q.s[s], acc, 4, 4, 0, 0, 0, 0);
+  if (__builtin_amdgcn_ballot_w64(test<2>(acc, thr)) != 0ull) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const bool hit = acc[i] > thr;
+      if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {
+        const unsigned key = hit ? ((unsigned)((256.f - acc[i]) * 2097152.f) | r_lane | (unsigned)((i & 3) + 8 * (i >> 2))) : 0xFFFFFFFFu;
+        const unsigned lo = min(best[0], key), hi = max(best[0], key);
+        best[0] = lo; best[1] = min(best[1], hi);
+      }
+    }
+    thr = fmaxf(thr, 256.f - 2.f * (float)(best[1] >> 22));
+  }
+  thrp = thr - 128.f;
+  return true;
+}
+
+template <bool LOADS, bool FLAG, bool BIG, bool COLD>
+__device__ __forceinline__ unsigned pstep(const Row& a, Row& a_next, __amdgpu_buffer_rsrc_t rs, unsigned lane_off, unsigned step_off,
+                                          const Row (&qb)[kQT], float (&thr)[kQT], float (&thrp)[kQT], unsigned (&best)[kQT][2],
+                                          f32x16& acc_e, f32x16& acc_o, unsigned r_lane, unsigned& hits, unsigned* sink) {
+  unsigned n_pass = 0;
+#pragma unroll
+  for (int t = 0; t < kQT; ++t) {
+    if (t & 1) acc_o = block<2>(a.s, qb[t].s); else acc_e = block<2>(a.s, qb[t].s);
+    if (LOADS && t == 0) { a_next.s[0] = frag(rs, lane_off, step_off, 0); a_next.s[1] = frag(rs, lane_off, step_off, 1); }
+    if (LOADS && t == 1) { a_next.s[2] = frag(rs, lane_off, step_off, 2); a_next.s[3] = frag(rs, lane_off, step_off, 3); }
+    bool went_on;
+    if (t == 0) went_on = part_test<FLAG, BIG, COLD>(acc_o, a_next, qb[kQT - 1], thr[kQT - 1], thrp[kQT - 1], r_lane - 32u, best[kQT - 1], hits, sink);
+    else went_on = part_test<FLAG, BIG, COLD>((t & 1) ? acc_e : acc_o, a, qb[t - 1], thr[t - 1], thrp[t - 1], r_lane, best[t - 1], hits, sink);
+    if (FLAG) n_pass += went_on ? 1u : 0u;
+  }
+  return n_pass;
+}
+
+__global__ void fill_fp4(unsigned* p, size_t n_words) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_words; i += (size_t)gridDim.x * blockDim.x)
+    p[i] = (mix((unsigned)i * 2654435761u + (unsigned)(i >> 32)) & 0x88888888u) | 0x22222222u;
+}
+
+template <bool LOADS, bool FLAG, bool BIG, bool TAIL, bool COLD = false>
+__global__ __launch_bounds__(256, 2) void kp(const u32x4* rows_fp4, unsigned copy_bytes, unsigned n_steps, unsigned share_period,
+                                             float* out, int seed, float thr0, unsigned* sink) {
+  const unsigned lane = threadIdx.x & 63u, h = lane >> 5;
+  const unsigned tile = __builtin_amdgcn_readfirstlane(((blockIdx.x & 7u) * 2u + ((blockIdx.x >> 3) & 1u)) % kTiles);
+  const unsigned step0 = tile * kTileSteps;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<u32x4*>(rows_fp4), 0, (int)copy_bytes, 0x00020000);
+  const unsigned lane_off = lane * 16u;
+  Row qb[kQT];
+  unsigned best[kQT][2];
+  float thr[kQT], thrp[kQT];
+#pragma unroll
+  for (int t = 0; t < kQT; ++t) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) qb[t].s[s][i] = i < 4 ? (int)((mix(threadIdx.x * 977u + t * 61u + s * 29u + i * 7u + blockIdx.x) & 0x88888888u) | 0x22222222u) : 0;
+    best[t][0] = best[t][1] = 0xFFFFFFFFu;
+    thr[t] = thr0; thrp[t] = thr0 - 128.f;
+  }
+  Row a0, a1;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    if (LOADS) a0.s[s] = frag(rs, lane_off, step0 * 4096u, s);
+    else
+#pragma unroll
+      for (int i = 0; i < 8; ++i) a0.s[s][i] = i < 4 ? (int)((mix(threadIdx.x * 131u + s * 17u + i + seed) & 0x88888888u) | 0x22222222u) : 0;
+  }
+  a1 = a0;
+  f32x16 acc_e, acc_o;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc_e[i] = -4096.f; acc_o[i] = -4096.f; }
+  unsigned hits = 0, n_pass = 0, next_share = 2u, seen = 0xFFFFFFFFu;
+  auto off = [&](unsigned step) { return (step0 + min(step, n_steps - 1u)) * 4096u; };   // wave-uniform
+  for (unsigned step = 0; step + 2u <= n_steps; step += 2u) {
+    n_pass += pstep<LOADS, FLAG, BIG, COLD>(a0, a1, rs, lane_off, off(step + 1u), qb, thr, thrp, best, acc_e, acc_o, 32u * step + 4u * h, hits, sink);
+    n_pass += pstep<LOADS, FLAG, BIG, COLD>(a1, a0, rs, lane_off, off(step + 2u), qb, thr, thrp, best, acc_e, acc_o, 32u * step + 4u * h + 32u, hits, sink);
+    if (TAIL && step + 2u >= next_share) {
+      next_share += share_period;
+#pragma unroll
+      for (int t = 0; t < kQT; ++t)
+        if (seen != 0xFFFFFFFFu) { thr[t] = fmaxf(thr[t], 256.f - 2.f * (float)(seen + 1u)); thrp[t] = thr[t] - 128.f; }
+      seen = __hip_atomic_load(sink + 2 + (lane & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  float r = 0.f;
+  for (int i = 0; i < 16; ++i) r += acc_e[i] + acc_o[i];
+  for (int t = 0; t < kQT; ++t) r += thr[t] + thrp[t] + (float)(best[t][0] ^ best[t][1]);
+  out[blockIdx.x * 256 + threadIdx.x] = r + (float)a0.s[0][0] + (float)a1.s[2][1] + (float)seen;
+  if (lane == 0 && n_pass) atomicAdd(sink, n_pass);
+  if (lane == 0 && hits) atomicAdd(sink + 1, hits);
+}
+
+template <bool LOADS, bool FLAG, bool BIG, bool TAIL, bool COLD = false>
+double runp(const char* what, int n_cu, const u32x4* d_rows, float* d_out, unsigned* d_sink) {
+  const int grid = n_cu * 2;
+  const unsigned bytes = (unsigned)kTiles * kTileSteps * 4096u;
+  hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+  hipLaunchKernelGGL((kp<LOADS, FLAG, BIG, TAIL, COLD>), dim3(grid), dim3(256), 0, 0, d_rows, bytes, (unsigned)kTileSteps, 16u, d_out, 1, 1e30f, d_sink);
+  hipDeviceSynchronize();
+  float best = 1e30f;
+  for (int r = 0; r < 6; ++r) {
+    hipEventRecord(e0, 0);
+    hipLaunchKernelGGL((kp<LOADS, FLAG, BIG, TAIL, COLD>), dim3(grid), dim3(256), 0, 0, d_rows, bytes, (unsigned)kTileSteps, 16u, d_out, r + 2, 1e30f, d_sink);
+    hipEventRecord(e1, 0); hipEventSynchronize(e1);
+    float ms; hipEventElapsedTime(&ms, e0, e1); if (ms < best) best = ms;
+  }
+  const double blocks_per_simd = 2.0 * kTileSteps * kQT;   // two waves per SIMD
+  const double ns = best * 1e6 / blocks_per_simd;
+  printf("%-58s %.3f ms  %6.1f ns per block per SIMD (%5.1f cycles @2.1 GHz)\n", what, best, ns, ns * 2.1);
+  return ns;
+}
+
 int main() {
   hipDeviceProp_t p; hipGetDeviceProperties(&p, 0);
   const int n_cu = p.multiProcessorCount;
   float* d_out; hipMalloc(&d_out, (size_t)n_cu * 2 * 256 * sizeof(float));
   unsigned* d_sink; (void)hipMalloc(&d_sink, 1024); (void)hipMemset(d_sink, 0, 1024);
+  {
+    const size_t bytes = (size_t)kTiles * kTileSteps * 4096u;
+    u32x4* d_rows; if (hipMalloc(&d_rows, bytes) != hipSuccess) { printf("no memory for the fp4 copy\n"); return 1; }
+    hipLaunchKernelGGL(fill_fp4, dim3(n_cu * 8), dim3(256), 0, 0, reinterpret_cast<unsigned*>(d_rows), bytes / 4);
+    if (hipDeviceSynchronize() != hipSuccess) { printf("fill failed\n"); return 1; }
+    for (int r = 0; r < 300; ++r)                              // warm-up: about 0.3 s of the full loop
+      hipLaunchKernelGGL((kp<true, true, true, true>), dim3(n_cu * 2), dim3(256), 0, 0, d_rows, (unsigned)bytes, (unsigned)kTileSteps, 16u, d_out, 1, 1e30f, d_sink);
+    if (hipDeviceSynchronize() != hipSuccess) { printf("warm-up failed\n"); return 1; }
+    printf("the product's fast path (hamming_topk_fp4rows<2,6,2>), one ingredient at a time:\n");
+    const double base = runp<false, false, false, false>("six blocks x two steps per trip, 2 MFMAs + tree test", n_cu, d_rows, d_out, d_sink);
+    const double va = runp<true, false, false, false>("(a) + four fragment loads per step", n_cu, d_rows, d_out, d_sink);
+    const double vb = runp<false, true, false, false>("(b) + per-block pass flag, summed per trip", n_cu, d_rows, d_out, d_sink);
+    const double vc = runp<false, false, true, false>("(c) + large inline slow path (never executed)", n_cu, d_rows, d_out, d_sink);
+    const double vt = runp<false, false, false, true>("    + row base and share-period test per trip", n_cu, d_rows, d_out, d_sink);
+    const double vac = runp<true, false, true, true>("(d) without the pass flag: loads + slow path + tail", n_cu, d_rows, d_out, d_sink);
+    const double vab = runp<true, true, false, true>("(d) with a small slow path: loads + flag + tail", n_cu, d_rows, d_out, d_sink);
+    const double vd = runp<true, true, true, true>("(d) everything: loads + flag + slow path + tail", n_cu, d_rows, d_out, d_sink);
+    const double ve = runp<true, false, true, true, true>("(e) = (d), flag counted in the slow path, slow path unlikely", n_cu, d_rows, d_out, d_sink);
+    printf("prices in ns per block and SIMD: (a) %+.2f  (b) %+.2f  (c) %+.2f  tail %+.2f  (d) %+.2f; flag inside (d) %+.2f, slow path inside (d) %+.2f; (e) against (d) %+.2f\n",
+           va - base, vb - base, vc - base, vt - base, vd - base, vd - vac, vd - vab, ve - vd);
+    (void)hipFree(d_rows);
+    printf("the earlier variants:\n");
+  }
   run<2, 0, 0>("2 MFMAs per block, nothing else", n_cu, d_out, d_sink);
   run<0, 1, 0>("chain test only", n_cu, d_out, d_sink);
   run<0, 1, 4>("chain test + expansion only", n_cu, d_out, d_sink);
