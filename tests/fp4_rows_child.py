@@ -1,15 +1,11 @@
 """Child of tests/test_match_fp4_rows_gpu.py (TODHIP_K4X_FP4_ROWS and TODHIP_K4X_QT are read once per process): the matrix-core search
-over the resident fp4 copy of the rows against the vector-ALU engine in the same process, bit for bit, in every block form."""
+over the resident fp4 copy of the rows against the vector-ALU engine in the same process, bit for bit, in every block form. The
+comparison itself: tests/k4x_children.py."""
 import itertools
-import os
-import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tod_amd import capi
-
-FIELDS = ("queryIdx", "trainIdx", "imgIdx", "distance")
+import k4x_children as C
 
 
 def flip(rows, rng, n_bits):
@@ -41,32 +37,17 @@ def make(kind, n_rows, nq, seed):
     return np.ascontiguousarray(desc), pts, off, np.ascontiguousarray(q)
 
 
-def same(a, b):
-    return np.array_equal(a[0], b[0]) and all(np.array_equal(a[1][f], b[1][f]) for f in FIELDS) and np.array_equal(a[2], b[2])
-
-
 def compare(ctx, q, ks, radii, splits, what):
     n = 0
     for k, radius in itertools.product(ks, radii):
-        ctx.set_matcher_engine("valu")
-        want = ctx.match(q, k, radius)
-        ctx.set_matcher_engine("mfma")
-        for split in splits:
-            ctx.set_matcher_block_split(split)
-            got = ctx.match(q, k, radius)
-            cnt = ctx.counters()
-            lowest = 2 if radius + 1 <= 64 else (3 if radius + 1 <= 96 else 4)     # the lowest split the thresholds allow
-            form = 4 if split == 0 else max(split, lowest)
-            assert cnt.last_fp4_rows == 1 and cnt.last_block_split == form, (what, k, radius, split, cnt.last_fp4_rows, cnt.last_block_split)
-            assert same(got, want), (what, k, radius, split)
-            n += 1
+        n += C.compare_forms(ctx, q, k, radius, C.valu_answer(ctx, q, k, radius), splits, what)
     ctx.set_matcher_block_split(-1)
     return n
 
 
 def main():
-    assert os.environ.get("TODHIP_K4X_FP4_ROWS") == "1" and os.environ.get("TODHIP_K4X_QT") in ("4", "6")
-    ctx = capi.Context(0)
+    C.qt_from_env()
+    ctx = C.capi.Context(0)
     n, builds = 0, 0
     for kind, n_rows, nq in itertools.product((0, 1, 2, 3), (4096, 4113, 8191), (129, 200)):
         desc, pts, off, q = make(kind, n_rows, nq, 1000 * kind + n_rows + nq)

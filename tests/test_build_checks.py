@@ -53,7 +53,22 @@ def test_k4x_waves_leave_room_in_the_register_file(match_asm):
     assert seen == 8, "expected the four block forms of hamming_topk_mfma<1 / 2, 6, ...>"
 
 
-R1_REGISTERS = {2: 112, 4: 185, 6: 228}                                # per QT, as measured when the check was written
+def test_fp4rows_waves_leave_room_in_the_register_file(match_asm):
+    """hamming_topk_fp4rows (tod_amd/csrc/match_fp4rows.h), the DB pass that reads the fp4 copy of the rows, under the same budget: the
+    default launch (six query blocks per wave, k <= 2) stays at <= 224 registers per wave and has no scratch, in all four block
+    forms: two waves then leave >= 64 of a SIMD's 512 registers free and ORB's and the verifier's kernels start beside the matcher's
+    waves, exactly as hamming_topk_mfma's do."""
+    seen = 0
+    for m in re.finditer(r"\.name:\s+(\S*hamming_topk_fp4rowsILi([12])ELi6ELi([0-3])E\S*)", match_asm):
+        blk = match_asm[m.start():m.start() + 1500]
+        vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1))
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1))
+        assert vgpr <= 224 and scratch == 0, "hamming_topk_fp4rows<%s, 6, %s>: %d registers, %d bytes of scratch" % (m.group(2), m.group(3), vgpr, scratch)
+        seen += 1
+    assert seen == 8, "expected the four block forms of hamming_topk_fp4rows<1 / 2, 6, ...>"
+
+
+R1_REGISTERS = {2: 112, 4: 185, 6: 228}                               # per QT, as measured when the check was written
 
 
 def test_r1_waves_stay_two_per_simd_without_scratch():

@@ -1,4 +1,4 @@
-"""The split-block fast path of hamming_topk_fp4rows (tod_amd/csrc/match_mfma.h): the block that goes on to its second part is the
+"""The split-block fast path of hamming_topk_fp4rows (tod_amd/csrc/match_fp4rows.h): the block that goes on to its second part is the
 unlikely side of its test, laid out behind the loop, and counts itself there. tests/fastpath_cases.py constructs DBs whose planted rows
 make a block go on in every block position of a step -- the last position, whose test is carried into the next step, in the first step
 of a tile, across the boundary of a two-step trip, in the last step of the loop, in rows held by either half of the lanes -- over tiles

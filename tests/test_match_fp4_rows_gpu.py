@@ -1,4 +1,4 @@
-"""hamming_topk_fp4rows (tod_amd/csrc/match_mfma.h): the matrix-core search reading the rows from their resident fp4 copy, against the
+"""hamming_topk_fp4rows (tod_amd/csrc/match_fp4rows.h): the matrix-core search reading the rows from their resident fp4 copy, against the
 vector-ALU engine in the same process, bit for bit (tests/fp4_rows_child.py). The knobs are read once per process, hence children:
 TODHIP_K4X_FP4_ROWS=1 sends every launch of >= 4 query blocks per wave through the copy, TODHIP_K4X_QT picks 4 or 6 blocks.
 Shapes: 4096, 4113 and 8191 rows in 3 objects (whole steps, a 17-row last step, a 31-row one; several tiles), 129 and 200 queries (a

@@ -1,4 +1,4 @@
-"""The split-2 form of hamming_topk_fp4rows (tod_amd/csrc/match_mfma.h) keeps only the fragments in front of the split in its loop; a
+"""The split-2 form of hamming_topk_fp4rows (tod_amd/csrc/match_fp4rows.h) keeps only the fragments in front of the split in its loop; a
 block that goes on loads the tails of ITS step from the fp4 copy and the tail words of ITS query, where it goes on (split 3 and whole
 blocks keep all four fragments resident and are held to the same answers here). The fast-path tests
 (tests/test_match_fastpath_gpu.py) cover "goes on and fails" and "distance 0"; what they do not pin down is whose tail is read.

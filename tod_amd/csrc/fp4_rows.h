@@ -1,4 +1,4 @@
-// The resident fp4 copy of the 32-byte DB rows (hamming_topk_fp4rows, match_mfma.h): where a fragment lives and what it holds, as
+// The resident fp4 copy of the 32-byte DB rows (hamming_topk_fp4rows, match_fp4rows.h): where a fragment lives and what it holds, as
 // plain C++ for host and device. The copy is what expand_word (match_fp4.h) makes of the packed rows, stored once, in the order the
 // DB pass reads it: fragment-major, so each of a wave's four loads per 32-row step is 1 KB contiguous at a wave-uniform base plus
 // constants. No reference lines: the reference has no such search. Included by ctx.h and by tests/fp4_rows_host_test.cpp.

@@ -18,12 +18,13 @@
 //                          group, the second half of those rows is never touched. Exact for any data; how
 //                          often it fires depends on the data (always, but for ~1e-4 of the groups, on
 //                          descriptors with independent bits and radius 35).
-// K4x hamming_topk_mfma    the same search on the matrix cores (fp4 x fp4 MFMAs, exact): match_fp4.h, match_mfma.h.
+// K4x hamming_topk_mfma    the same search on the matrix cores (fp4 x fp4 MFMAs, exact): match_fp4.h, match_mfma.h; and
+//     hamming_topk_fp4rows the same pass over the resident fp4 copy of the rows, the default from 4 query blocks per wave on: match_fp4rows.h.
 // K4m merge_tiles_kernel   per query: merge the per-tile lists into k global keys.
 // K4f finalize_kernel      per query: merge shard lists, radius cut, object lookup, 3D gather.
 // This file is the matcher's one translation unit: the engine choice, the timing ring and the tod_match_* entry points. The rest
-// is included below: match_keys.h (constants, sorted lists, the pick over lists), match_valu.h (K4), match_fp4.h + match_mfma.h (K4x: block
-// primitives, kernels), match_merge.h (K4m, K4s, K4f), match_plan.h (tiling, workspaces, merge launch: shared with match_wide.hip),
+// is included below: match_keys.h (constants, sorted lists, the pick over lists), match_valu.h (K4), match_fp4.h + match_mfma.h + match_fp4rows.h
+// (K4x: block primitives and list helpers, the pass over the packed rows, the pass over their fp4 copy), match_merge.h (K4m, K4s, K4f), match_plan.h (tiling, workspaces, merge launch: shared with match_wide.hip),
 // match_launch.h (knobs, launchers); with ctx.h: match_tiles.h, match_split.h, KernelTimer, dispatch_k.
 #include <algorithm>
 #include <cstdio>
@@ -39,6 +40,7 @@ namespace {
 #include "match_valu.h"
 #include "match_fp4.h"
 #include "match_mfma.h"
+#include "match_fp4rows.h"
 #include "match_merge.h"
 #include "match_plan.h"
 #include "match_launch.h"

@@ -1,6 +1,7 @@
 // The matrix-core block primitives of the exact Hamming searches, and no kernel: what hamming_topk_mfma, hamming_topk_mfma_q32
-// (match_mfma.h), radius_collect_mfma (match_radius.hip) and hamming_topk_wide (match_wide.hip) share; at the end, the row widths
-// (RowBits: 256 and 512 bits) and the step loop of the last two (block_step_loop).
+// (match_mfma.h), hamming_topk_fp4rows (match_fp4rows.h), radius_collect_mfma (match_radius.hip) and hamming_topk_wide
+// (match_wide.hip) share; the top-k passes' list helpers (exchange_bounds, store_tile_lists); at the end, the row widths (RowBits:
+// 256 and 512 bits) and the step loop of R1 and W1 (block_step_loop).
 // Included by match.hip, match_radius.hip and match_wide.hip inside their anonymous namespaces, after match_keys.h.
 // With every descriptor bit b written as the MX-fp4 (E2M1) value 1 - 2b, the dot product of two descriptors is 256 - 2 * hamming:
 // products are +-1, the f32 accumulator holds integers <= 256, so the result is EXACT. v_mfma_f32_32x32x64_f8f6f4 (fp4 x fp4, unit
@@ -106,6 +107,62 @@ struct StepLoaderT {
   }
 };
 using StepLoader = StepLoaderT<kWords>;
+
+// ---- What the top-k DB passes do to their lists around the step loop: hamming_topk_fp4rows (match_fp4rows.h) and hamming_topk_wide
+// (match_wide.hip) call these two. hamming_topk_mfma and hamming_topk_mfma_q32 (match_mfma.h) keep inline copies, the only ones left:
+// with the functions hipcc allocates hamming_topk_mfma's registers anew -- measured when they were written (the QT = 6 forms) and again
+// when W1 joined: QT = 6 gains 2 VGPRs and 3 SGPRs (<2, 6, 2>: 221 -> 223 of the 224 tests/test_build_checks.py allows), QT = 2 gains
+// 15 instructions, QT = 4 and 8 do not move -- and that kernel is tuned to the code it has. The callers' code is the same either way.
+// The exchange of distance bounds between tiles, once per share period: take the bounds loaded one period ago (a published bound stays
+// valid: bounds only fall), publish a full list's bound if it improves on what was seen, start the loads of the next period.
+// q0 + c: this lane's query of block 0; thr_of_limit: the row width's (dot > thr <=> d < limit); tightened(t): behind a threshold that
+// took a foreign bound (the split blocks' part thresholds follow it there). Both come as lambdas, as block_step_loop's hooks do: handed
+// thr_of_limit by its name, a pointer, hamming_topk_fp4rows' split forms came out with other registers (the call is resolved after
+// the inlining, not with it)
+template <int K, int QT, typename ThrOfLimit, typename Tightened>
+__device__ __forceinline__ void exchange_bounds(uint32_t* bound, uint32_t q0, uint32_t c, uint32_t nq, const uint32_t (&best)[QT][K],
+                                                uint32_t (&seen)[QT], float (&thr)[QT], ThrOfLimit thr_of_limit, Tightened tightened) {
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    const uint32_t qi = q0 + 32u * t + c;
+    uint32_t* my_bound = bound + (qi < nq ? qi : nq - 1u);
+    const uint32_t worst_d = best[t][K - 1] >> kLocalBits;
+    if (worst_d < kNoLimit && worst_d < seen[t]) atomicMin(my_bound, worst_d);
+    // a foreign bound is applied with <=: a smaller row index elsewhere may still win a tie
+    if (seen[t] != 0xFFFFFFFFu) { thr[t] = fmaxf(thr[t], thr_of_limit(seen[t] + 1u)); tightened(t); }
+    seen[t] = __hip_atomic_load(my_bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// The epilogue: lanes l and l + 32 hold the two halves of a query's rows: merge the partner's list, then K4's output format
+// (partial keys + one flag byte per (tile, 64 queries); two query blocks share a flag, so both are stored when either kept something)
+template <int K, int QT>
+__device__ __forceinline__ void store_tile_lists(uint32_t (&best)[QT][K], uint32_t tile, uint32_t q0, uint32_t nq, uint32_t nq_pad,
+                                                 uint32_t n_qw64, uint32_t lane, uint32_t c, uint32_t h, uint32_t* __restrict__ part,
+                                                 uint8_t* __restrict__ stored) {
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    uint32_t other[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) other[j] = __shfl_xor(best[t][j], 32);
+#pragma unroll
+    for (int j = 0; j < K; ++j) topk_insert<K>(best[t], other[j]);
+  }
+#pragma unroll
+  for (int u = 0; u < QT / 2; ++u) {
+    const uint32_t qa = q0 + 64u * u + c, qb2 = qa + 32u;
+    const bool any_a = qa < nq && best[2 * u][0] != 0xFFFFFFFFu, any_b = qb2 < nq && best[2 * u + 1][0] != 0xFFFFFFFFu;
+    if (__builtin_amdgcn_ballot_w64(any_a || any_b) != 0ull) {  // some query below nq: the flag's index is below n_qw64
+      if (h == 0u) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          if (qa < nq) part[((size_t)tile * K + j) * nq_pad + qa] = best[2 * u][j];
+          if (qb2 < nq) part[((size_t)tile * K + j) * nq_pad + qb2] = best[2 * u + 1][j];
+        }
+      }
+      if (lane == 0) stored[(size_t)tile * n_qw64 + (q0 >> 6) + u] = 0;
+    }
+  }
+}
 
 // ---- Rows of BITS = 256 or 512 bits (ORB; BRISK, FREAK and the other 64-byte descriptors) for the passes that take the width as
 // a parameter. A wider row is 256-bit parts in the layout above: lane l holds the 16 bytes at word 8 part + 4 (l >> 5). A 32 x 32

@@ -7,6 +7,7 @@ constexpr int kWords = 8;          // 256-bit descriptors (ORB / rBRIEF), 32 byt
 constexpr int kGroupRows = 4;      // DB rows per SGPR group (two s_load_dwordx16)
 constexpr int kLocalBits = 22;     // tile-local row index bits in a partial key (tile <= 4M rows)
 constexpr uint32_t kLocalMask = (1u << kLocalBits) - 1u;
+constexpr uint32_t kNoLimit = 0xFFFFFFFFu >> kLocalBits;   // 1023: the distance field of the empty key, above every distance
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / 64;
 constexpr int kWavesPerCU = 24;    // waves a CU holds at once: 6 blocks of 4 waves (<= 112 SGPRs); the grid is ~3x that
@@ -23,6 +24,12 @@ __device__ __forceinline__ void topk_insert(uint32_t (&best)[K], uint32_t key) {
     best[j] = lo;
   }
 }
+
+// The work-item decode (xcd, slot) -> (tile, query wave) stands inline, three times the same, at the head of hamming_topk_tiles,
+// hamming_topk_mfma and hamming_topk_fp4rows (the commented copy is hamming_topk_tiles'). As a __forceinline__ function returning
+// "this wave has an item" it changed the generated code of every form of all three (the early return becomes a flag that hipcc
+// branches on: another block layout in front of the loops, other register numbers behind it; K4's forms differ by two swapped scalar
+// moves only) -- in four spellings of the function, with and without branch hints -- and these kernels are tuned to the code they have.
 
 // The smallest key of query qi over n_lists ascending lists (layout [list][nq][k]) that is greater than the last one taken (any,
 // while !have_last); ~0 when nothing is left. Keys are unique (the row is part of the key), so each list's candidate is its first

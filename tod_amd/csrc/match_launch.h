@@ -1,8 +1,8 @@
 // Host planning of the 32-byte matcher's launches: the environment knobs and the launchers of both engines. Each engine keeps its
 // own, measured policy for how many tiles to ask for; what follows that policy is shared (match_plan.h: tiling, workspaces, merge
 // launch). The k of the reference's knnMatch is DescriptorMatcher.cpp:211, its radius cut :212-220.
-// Included by match.hip inside its anonymous namespace, after match_keys.h, match_valu.h, match_fp4.h, match_mfma.h, match_merge.h
-// and match_plan.h.
+// Included by match.hip inside its anonymous namespace, after match_keys.h, match_valu.h, match_fp4.h, match_mfma.h, match_fp4rows.h
+// (expand_rows_fp4_kernel, hamming_topk_fp4rows), match_merge.h and match_plan.h.
 
 int k4_engine(const todhip_ctx* ctx, uint32_t nq);   // match.hip, behind this header
 
@@ -59,7 +59,7 @@ template <int K, int QT>
 int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
   constexpr bool PF2 = QT < 8;                                        // register budget: see hamming_topk_mfma
   const MatchEnv& env = match_env();
-  const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu >> kLocalBits : radius + 1u;   // distances are <= 256: no cut beyond that
+  const uint32_t cut = radius >= 256u ? kNoLimit : radius + 1u;       // distances are <= 256: no cut beyond that
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx);
   const uint32_t n_qw = (nq + 32u * QT - 1u) / (32u * QT), n_qw64 = (nq + 63u) / 64u;
   const uint32_t nq_pad = n_qw64 * 64u;
@@ -97,31 +97,31 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
     ctx->k4x.take_report(ctx->k4x_stats_host.as<uint32_t>(), ctx->counters, min_split, env.k4x_half, env.k4x_half_debug);
   }
   const uint32_t split = ctx->k4x.next(min_split, env.k4x_half);       // 4 = whole blocks
-  auto kern = split == 2 ? hamming_topk_mfma<K, QT, 2, PF2>
-              : split == 3 ? hamming_topk_mfma<K, QT, 3, PF2>
-              : (cut <= 128u ? hamming_topk_mfma<K, QT, 1, PF2> : hamming_topk_mfma<K, QT, 0, PF2>);
+  const int mode = split == 2 ? 2 : split == 3 ? 3 : cut <= 128u ? 1 : 0;   // the kernels' MODE
   ctx->counters.last_block_split = split;
   uint32_t* const d_stats = split < 4 ? ctx->k4x_stats_dev.as<uint32_t>() : nullptr;
   const uint4* rows_fp4 = nullptr;                                     // the fp4 copy, where this launch reads it
   if ((QT == 4 || QT == 6) && t.rows_per_tile % 32u == 0u)          // (a tile starts on a step of the copy: mfma_tile_rows gives whole steps)
     if (int rc = fp4_rows_ready(ctx, n_rows, &rows_fp4)) return rc;
   ctx->counters.last_fp4_rows = rows_fp4 ? 1u : 0u;
-  if constexpr (QT == 4 || QT == 6) {                                  // (eight blocks per wave leave no room for two steps' fragments)
-    if (rows_fp4) {
-      auto kern4 = split == 2 ? hamming_topk_fp4rows<K, QT, 2>
-                   : split == 3 ? hamming_topk_fp4rows<K, QT, 3>
-                   : (cut <= 128u ? hamming_topk_fp4rows<K, QT, 1> : hamming_topk_fp4rows<K, QT, 0>);
-      hipLaunchKernelGGL(kern4, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream, rows_fp4, d_q, n_rows, nq, nq_pad,
-                         t.rows_per_tile, t.n_tiles, n_qw, n_qw64, t.blocks_per_xcd, t.tiles_per_xcd, cut,
-                         (uint32_t)std::max(2, env.k4x_share), ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored,
-                         d_stats ? d_stats + 2u * (split - 2u) : nullptr);
-    }
+  // the two passes differ in the rows they read and in nothing behind them
+  auto launch = [&](auto kern, auto rows) {
+    hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream, rows, d_q, n_rows, nq, nq_pad, t.rows_per_tile,
+                       t.n_tiles, n_qw, n_qw64, t.blocks_per_xcd, t.tiles_per_xcd, cut, (uint32_t)std::max(2, env.k4x_share),
+                       ctx->m_part.as<uint32_t>(), ctx->m_bound.as<uint32_t>(), d_stored, d_stats ? d_stats + 2u * (split - 2u) : nullptr);
+  };
+  auto launch_mode = [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    if constexpr (QT == 4 || QT == 6)                                  // (eight blocks per wave leave no room for two steps' fragments)
+      if (rows_fp4) return launch(hamming_topk_fp4rows<K, QT, MODE>, rows_fp4);
+    launch(hamming_topk_mfma<K, QT, MODE, PF2>, reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)));
+  };
+  switch (mode) {
+    case 0: launch_mode(std::integral_constant<int, 0>{}); break;
+    case 1: launch_mode(std::integral_constant<int, 1>{}); break;
+    case 2: launch_mode(std::integral_constant<int, 2>{}); break;
+    default: launch_mode(std::integral_constant<int, 3>{}); break;
   }
-  if (!rows_fp4)
-    hipLaunchKernelGGL(kern, dim3(t.blocks_per_xcd * 8u), dim3(kBlock), 0, ctx->stream,
-                       reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)), d_q, n_rows, nq, nq_pad, t.rows_per_tile, t.n_tiles, n_qw, n_qw64,
-                       t.blocks_per_xcd, t.tiles_per_xcd, cut, (uint32_t)std::max(2, env.k4x_share), ctx->m_part.as<uint32_t>(),
-                       ctx->m_bound.as<uint32_t>(), d_stored, d_stats ? d_stats + 2u * (split - 2u) : nullptr);
   if (int rc = timer.end()) return rc;
   if (d_stats) ++ctx->k4x.seq_sent;
   if (nq <= 64u && !d_stats && t.n_tiles >= 256u) return launch_merge_wave<K>(ctx, nq, nq_pad, t, d_stored, n_qw64, d_lists, n_lists);
@@ -130,7 +130,7 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
 
 template <int K>
 int launch_topk_mfma_q32(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint32_t radius, uint64_t* d_lists, uint32_t* n_lists) {
-  const uint32_t cut = radius >= 256u ? 0xFFFFFFFFu >> kLocalBits : radius + 1u;
+  const uint32_t cut = radius >= 256u ? kNoLimit : radius + 1u;
   const uint32_t n_rows = (uint32_t)tod_db_n_rows(ctx), n_qw64 = 1u, nq_pad = 64u;
   // one wave per tile; about 32 waves per CU in all (each holds four 1 KB loads in flight), tiles of >= 2048 rows
   Tiling t;

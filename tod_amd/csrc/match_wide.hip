@@ -24,7 +24,6 @@ namespace {
 #include "match_plan.h"
 
 using W = RowBits<512>;
-constexpr uint32_t kNoLimit = 0xFFFFFFFFu >> kLocalBits;     // 1023: the distance field of the empty key, above every distance
 
 // The test of one accumulator block, as mfma_block_test: nothing unless some lane's best dot product beats its threshold, then the
 // walk. The walk masks the rows behind the tile's end (the DB's last, partial step reads the slack). IMAX: thresholds are >= 0.
@@ -45,7 +44,8 @@ __device__ __forceinline__ void wide_block_test(const mfma_f32x16& acc, float& t
 }
 
 // W1. Work item = (tile, query wave), consecutive items share a tile. The loop over the tile's steps is match_fp4.h's
-// block_step_loop; the test of a block is wide_block_test, and behind a step the bounds are exchanged as in hamming_topk_mfma.
+// block_step_loop; the test of a block is wide_block_test; behind a step the bounds are exchanged, and at the end the lists stored, by
+// the functions hamming_topk_fp4rows uses (exchange_bounds, store_tile_lists).
 // cut = radius + 1 (kNoLimit: none); IMAX: cut <= 256, every threshold >= 0. Output: K4's partial lists and flag bytes (match_merge.h
 // reads them).
 template <int K, int QT, bool IMAX>
@@ -81,45 +81,9 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_wide(const uint32_t* _
       [&](uint32_t step) {
         if (step + 1u < next_share) return;                 // wave-uniform
         next_share += share_period;
-        // take the bounds loaded one period ago (a published bound stays valid: bounds only fall), publish a full list's bound if it
-        // improves on what was seen, start the loads of the next period
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-          const uint32_t qi = q0 + 32u * t + c;
-          uint32_t* my_bound = bound + (qi < nq ? qi : nq - 1u);
-          const uint32_t worst_d = best[t][K - 1] >> kLocalBits;
-          if (worst_d < kNoLimit && worst_d < seen[t]) atomicMin(my_bound, worst_d);
-          // a foreign bound is applied with <=: a smaller row index elsewhere may still win a tie
-          if (seen[t] != 0xFFFFFFFFu) thr[t] = fmaxf(thr[t], W::thr_of_limit(seen[t] + 1u));
-          seen[t] = __hip_atomic_load(my_bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        exchange_bounds<K, QT>(bound, q0, c, nq, best, seen, thr, [](uint32_t limit) { return W::thr_of_limit(limit); }, [](int) {});
       });
-
-  // lanes l and l + 32 hold the two halves of a query's rows: merge the partner's list, then K4's output format (partial keys + one
-  // flag byte per (tile, 64 queries); two query blocks share a flag, so both are stored when either kept something)
-#pragma unroll
-  for (int t = 0; t < QT; ++t) {
-    uint32_t other[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) other[j] = __shfl_xor(best[t][j], 32);
-#pragma unroll
-    for (int j = 0; j < K; ++j) topk_insert<K>(best[t], other[j]);
-  }
-#pragma unroll
-  for (int u = 0; u < QT / 2; ++u) {
-    const uint32_t qa = q0 + 64u * u + c, qb2 = qa + 32u;
-    const bool any_a = qa < nq && best[2 * u][0] != 0xFFFFFFFFu, any_b = qb2 < nq && best[2 * u + 1][0] != 0xFFFFFFFFu;
-    if (__builtin_amdgcn_ballot_w64(any_a || any_b) != 0ull) {  // some query below nq: the flag's index is below n_qw64
-      if (h == 0u) {
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-          if (qa < nq) part[((size_t)tile * K + j) * nq_pad + qa] = best[2 * u][j];
-          if (qb2 < nq) part[((size_t)tile * K + j) * nq_pad + qb2] = best[2 * u + 1][j];
-        }
-      }
-      if (lane == 0) stored[(size_t)tile * n_qw64 + (q0 >> 6) + u] = 0;
-    }
-  }
+  store_tile_lists<K, QT>(best, tile, q0, nq, nq_pad, n_qw64, lane, c, h, part, stored);
 }
 
 // One launch on the shared plan (match_plan.h): tiling, workspaces, the DB pass, the tile merge. The grid is linear: the kernel's

@@ -175,7 +175,7 @@ double run(const char* what, int n_cu, float* d_out, unsigned* d_sink) {
   return ns;
 }
 
-// ---- The fast path of hamming_topk_fp4rows<2, 6, 2> (tod_amd/csrc/match_mfma.h), one ingredient at a time on the "2 MFMAs + tree
+// ---- The fast path of hamming_topk_fp4rows<2, 6, 2> (tod_amd/csrc/match_fp4rows.h), one ingredient at a time on the "2 MFMAs + tree
 // test" loop above. kp<0,0,0,0> is that loop in the product's shape: six query blocks per 32-row step, two steps per trip, the step's
 // last test carried into the next step's block 0, a tiny slow path that counts itself. The ingredients:
 //   LOADS  the rows come from a 128 MB fp4 copy, four 1 KB buffer loads per step addressed as Fp4StepLoader does (lane offset in the
