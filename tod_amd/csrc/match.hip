@@ -40,6 +40,7 @@ namespace {
 #include "match_valu.h"
 #include "match_fp4.h"
 #include "match_mfma.h"
+#include "match_pair_pack.h"
 #include "match_fp4rows.h"
 #include "match_merge.h"
 #include "match_plan.h"

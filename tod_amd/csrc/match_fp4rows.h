@@ -1,7 +1,7 @@
 // K4x over the resident fp4 copy of the rows (layout: fp4_rows.h): expand_rows_fp4_kernel, which builds the copy, the loader of its
 // fragments, the split-block tests and steps of this pass and hamming_topk_fp4rows -- the default DB pass of every launch of 4 or 6
 // query blocks per wave (match_launch.h). Included by match.hip inside its anonymous namespace, after match_fp4.h (arithmetic, layout,
-// block primitives, exchange_bounds, store_tile_lists) and match_mfma.h (mfma_block_test).
+// block primitives, exchange_bounds, store_tile_lists), match_mfma.h (mfma_block_test) and match_pair_pack.h (PairPack).
 // hamming_topk_mfma expands every packed row to fp4 again in every launch and in every query wave of its tile: 28 of the 82 vector
 // instructions of a 32-row step of six split blocks, in a loop that is bound by vector issue. The DB is loaded once and searched for
 // many frames, so the expansion is done once instead (expand_rows_fp4_kernel) and this pass loads the fragments as they stand: four
@@ -157,6 +157,109 @@ __device__ __forceinline__ void fp4rows_split_step(const Fp4Frags<SPLIT>& a, Fp4
   }
 }
 
+// ---- Two split blocks per accumulator (match_pair_pack.h has the packing; profiles/match_pairs.json the measurements). The block
+// test above is at its operation count for 16 registers per block -- 8 v_max3 + a compare, in a loop bound by vector issue -- so the
+// paired step tests 16 registers per TWO blocks: query blocks t and t + 1 of a row step share an accumulator, block t + 1's MFMAs
+// scaled by 2^11, and 7 v_or3 + v_bitop3 + a compare answer for both. The bias is one per launch, so the fast path tests against
+// the launch's radius, not against each query's tightened threshold: exact, since a threshold only rises (a block skipped at the
+// radius is skipped at any tighter threshold), and the block that goes on applies its query's own thr as before.
+struct PairConsts {
+  mfma_f32x16 magic;          // srcC of a pair's first MFMA; also "no pending pair" (both flags clear)
+  int scale_one, scale_field; // the E8M0 scales, in vector registers: from scalar ones hipcc copies both in front of every pair
+  int bias;                   // field = dot + bias (wave-uniform)
+};
+__device__ __forceinline__ PairConsts pair_consts(uint32_t cut) {
+  PairConsts pk;
+  const float m = PairPack::magic(cut);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) pk.magic[i] = m;
+  asm volatile("v_mov_b32 %0, %1" : "=v"(pk.scale_one) : "n"(PairPack::kScaleOne));
+  asm volatile("v_mov_b32 %0, %1" : "=v"(pk.scale_field) : "n"(PairPack::kScaleField));
+  pk.bias = PairPack::bias(cut);
+  return pk;
+}
+// The first block in the unscaled form of the instruction, the second with 2^11 on the rows: tools/mfma_valu_overlap.hip measured all
+// four scaled at 79.7 cycles per block and this at 76.5 (today's block: 87.3). The empty asm keeps the MFMAs where they stand: hipcc
+// otherwise sinks them behind the NEXT test, straight in front of their own, with s_nop 11 and one accumulator.
+__device__ __forceinline__ void dot_pair(mfma_f32x16& acc, const Fp4Frags<2>& a, const Fp4Frags<2>& qa, const Fp4Frags<2>& qb, const PairConsts& pk) {
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[0], qa.s[0], pk.magic, 4, 4, 0, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[1], qa.s[1], acc, 4, 4, 0, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[0], qb.s[0], acc, 4, 4, 0, pk.scale_field, 0, pk.scale_one);
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a.s[1], qb.s[1], acc, 4, 4, 0, pk.scale_field, 0, pk.scale_one);
+  asm volatile("" : "+v"(acc));
+}
+// The OR of a packed accumulator's 16 registers, as a tree like block_reaches' maximum (hipcc reassociates plain ORs into one chain)
+__device__ __forceinline__ uint32_t pair_or(const mfma_f32x16& acc) {
+  uint32_t g[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    g[j] = (uint32_t)__float_as_int(acc[3 * j]) | (uint32_t)__float_as_int(acc[3 * j + 1]) | (uint32_t)__float_as_int(acc[3 * j + 2]);
+    asm("" : "+v"(g[j]));
+  }
+  return (g[0] | g[1] | g[2]) | (g[3] | g[4] | (uint32_t)__float_as_int(acc[15]));
+}
+// Block FIELD of a pair goes on: its part is unpacked from its field (exact: the dot products of its first two MFMAs) and completes as
+// fp4rows_block_test_part's block does -- the tails of its own step from the copy, its query's tail words, the test against the
+// query's own thr, the walk. Unpacking keeps nothing for this path in registers across the fast path.
+template <int K, int FIELD>
+__device__ __forceinline__ void fp4rows_pair_complete(const mfma_f32x16& packed, int bias, const Fp4StepLoader& rows, uint32_t own_step,
+                                                      const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, const Fp4Consts& kc,
+                                                      float& thr, uint32_t r_lane, uint32_t n_lim, uint32_t (&best)[K], uint32_t& n_pass) {
+  ++n_pass;
+  asm volatile("" : "+v"(qi));
+  mfma_f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = (float)PairPack::unpack((uint32_t)__float_as_int(packed[i]), FIELD, bias);
+  mfma_i32x8 tail[2];
+#pragma unroll
+  for (int s = 2; s < 4; ++s) tail[s - 2] = rows.template load<true>(own_step, s);
+  const uint4 p = load_query_packed(q, qi, nq, h);
+#pragma unroll
+  for (int s = 2; s < 4; ++s)
+    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(tail[s - 2], expand_word(packed_word(p, s), kc), acc, 4, 4, 0, 0, 0, 0);
+  mfma_block_test<K, false, true>(acc, thr, r_lane, n_lim, best);
+  asm("" : "+v"(thr));        // (a register of its own: see fp4rows_block_test_part)
+}
+// The test of a pair (blocks ta and ta + 1 of own_step; qi: this lane's query of block ta). n_pass counts each block that goes on, by
+// its own flag: a block whose partner alone went on is not counted.
+template <int K>
+__device__ __forceinline__ void fp4rows_pair_test(const mfma_f32x16& acc, const PairConsts& pk, const Fp4StepLoader& rows, uint32_t own_step,
+                                                  const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, const Fp4Consts& kc,
+                                                  float& thr_a, float& thr_b, uint32_t r_lane, uint32_t n_lim, uint32_t (&best_a)[K],
+                                                  uint32_t (&best_b)[K], uint32_t& n_pass) {
+  const uint32_t o = pair_or(acc);
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64((o & PairPack::kFlagMask) != 0u) == 0ull, 1)) return;
+  if (__builtin_amdgcn_ballot_w64((o & PairPack::kFlagA) != 0u) != 0ull)
+    fp4rows_pair_complete<K, 0>(acc, pk.bias, rows, own_step, q, qi, nq, h, kc, thr_a, r_lane, n_lim, best_a, n_pass);
+  if (__builtin_amdgcn_ballot_w64((o & PairPack::kFlagB) != 0u) != 0ull)
+    fp4rows_pair_complete<K, 1>(acc, pk.bias, rows, own_step, q, qi + 32u, nq, h, kc, thr_b, r_lane, n_lim, best_b, n_pass);
+}
+// fp4rows_split_step in pairs: QT / 2 pairs per step into two alternating accumulators, the test of a pair behind the MFMAs of the
+// next (three accumulators, the test trailing further, measured no better), the step's last pair carried into the next step. With
+// three pairs per step the pending pair's accumulator alternates per step: PH is the step's place in the loop's trip of two. Either
+// way a trip starts and ends with its pending pair in acc_odd.
+template <int K, int QT, int PH>
+__device__ __forceinline__ void fp4rows_pair_step(const Fp4Frags<2>& a, Fp4Frags<2>& a_next, const Fp4StepLoader& rows, uint32_t step,
+                                                  const Fp4Frags<2> (&qh)[QT], const uint32_t* __restrict__ q, uint32_t q0c, uint32_t nq,
+                                                  uint32_t h, const Fp4Consts& kc, const PairConsts& pk, float (&thr)[QT],
+                                                  uint32_t (&best)[QT][K], mfma_f32x16& acc_even, mfma_f32x16& acc_odd, uint32_t r_lane,
+                                                  uint32_t n_lim, uint32_t& n_pass) {
+  static_assert(QT >= 4 && QT % 2 == 0, "whole pairs; the pending pair alternates between two accumulators");
+  constexpr int NP = QT / 2;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    const bool odd = ((NP * PH + j) & 1) != 0;
+    dot_pair(odd ? acc_odd : acc_even, a, qh[2 * j], qh[2 * j + 1], pk);
+    if (j == 0) {
+#pragma unroll
+      for (int m = 0; m < 2; ++m) a_next.s[m] = rows.template load<false>(step + 1u, m);
+    }
+    constexpr int kLast = NP - 1;
+    if (j == 0) fp4rows_pair_test<K>(odd ? acc_even : acc_odd, pk, rows, step - 1u, q, q0c + 64u * kLast, nq, h, kc, thr[2 * kLast], thr[2 * kLast + 1], r_lane - 32u, n_lim, best[2 * kLast], best[2 * kLast + 1], n_pass);   // previous step's last pair, its rows
+    else fp4rows_pair_test<K>(odd ? acc_even : acc_odd, pk, rows, step, q, q0c + 64u * (j - 1), nq, h, kc, thr[2 * j - 2], thr[2 * j - 1], r_lane, n_lim, best[2 * j - 2], best[2 * j - 1], n_pass);
+  }
+}
+
 // A masked whole-block step (and the one before it when the loop leaves an odd step) in a split form: at most two per tile. The rows
 // come complete (a); of the queries only the packed tail words are kept for these steps (qtail, loaded once per wave), and one block's
 // tail is expanded at a time.
@@ -179,7 +282,12 @@ __device__ __forceinline__ void fp4rows_split_masked_step(const Fp4Row& a, const
 }
 
 // hamming_topk_mfma with the rows read from their fp4 copy (rows_fp4: fp4_rows.h's layout of the rows the packed pass would read;
-// rows_per_tile is a multiple of 32, so a tile starts on a step of the copy). MODE, the work items, the lists and the output as there.
+// rows_per_tile is a multiple of 32, so a tile starts on a step of the copy). MODE, the work items, the lists and the output as there,
+// and one more: MODE 4 is split 2 in single blocks (fp4rows_split_step), the step MODE 2 had before it paired its blocks
+// (fp4rows_pair_step) -- kept for A/B and diagnostics (TODHIP_K4X_PAIRS=0).
+#ifndef TOD_K4X_STATIC_PRIO
+#define TOD_K4X_STATIC_PRIO 1
+#endif
 template <int K, int QT, int MODE>
 __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* __restrict__ rows_fp4,
                                                                   const uint32_t* __restrict__ q, uint32_t n_rows,
@@ -191,7 +299,7 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
                                                                   uint8_t* __restrict__ stored, uint32_t* half_stats) {
   static_assert(QT == 4 || QT == 6, "four or six query blocks per wave: with eight the fragments of two steps do not fit beside them");
   constexpr bool IMAX = MODE >= 1;
-  constexpr int HALF = MODE >= 2 ? MODE : 0;                          // the split (0: whole blocks)
+  constexpr int HALF = MODE == 4 ? 2 : (MODE >= 2 ? MODE : 0);        // the split (0: whole blocks)
   constexpr float kPartOff = HALF ? 64.f * (float)(4 - HALF) : 0.f;   // what the positions behind the split can still add to a dot product
   const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
   uint32_t tile, qw;
@@ -213,12 +321,13 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
   // Split 2 alone: on data where split 2 pays, one block in 2200 goes on. Split 3 is what the adaptive launch probes on data where
   // every second block goes on (match_split.h); there each such block would wait for its loads, and at 32 000 x 1M split 3 gained
   // nothing from it (profiles/match_tails.json). Split 3 and whole blocks keep all four fragments resident, as before.
-  constexpr bool TAILS = MODE == 2;
+  constexpr bool TAILS = HALF == 2;
+  constexpr bool PAIRS = MODE == 2;                                   // two blocks per accumulator, tested at the launch's radius
   constexpr int NF = TAILS ? HALF : 4;                                // the fragments the loop keeps
   using Frags = typename std::conditional<TAILS, Fp4Frags<NF>, Fp4Row>::type;
   Frags qb[QT];
   uint32_t best[QT][K];
-  float thr[QT], thrp[QT];
+  float thr[QT], thrp[QT];                                            // (thrp: not in the paired form)
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
     if constexpr (TAILS) {
@@ -231,7 +340,7 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
 #pragma unroll
     for (int j = 0; j < K; ++j) best[t][j] = 0xFFFFFFFFu;
     thr[t] = thr_of_limit(cut);
-    thrp[t] = thr[t] - kPartOff;
+    if constexpr (!PAIRS) thrp[t] = thr[t] - kPartOff;
   }
 
   const uint32_t row0 = tile * rows_per_tile;
@@ -243,8 +352,12 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
   for (int m = 0; m < NF; ++m) a0.s[m] = rows.template load<false>(0, m);
   a1 = a0;                                                            // "the step before the first": its pending block is none
   mfma_f32x16 acc_even, acc_odd;
+  PairConsts pk;
+  if constexpr (PAIRS) { pk = pair_consts(cut); acc_odd = pk.magic; }   // "no pending pair"
+  else {
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
+    for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
+  }
   uint32_t seen[QT];
 #pragma unroll
   for (int t = 0; t < QT; ++t) seen[t] = 0xFFFFFFFFu;                // "nothing published"
@@ -255,9 +368,13 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
   // 32 000 x 1M, split 2, alternating: 1.378 -> 1.353 ms (profiles/match_fastpath.json); it changes no result. Only in the form it
   // was measured to pay in, split 2 with six query blocks: raised everywhere it also outranked ORB's and the verifier's kernels in
   // the chained pipeline, whose DB runs whole blocks or split 3 (one run: 10 428 -> 9 522 frames/s), and whole blocks gained 0.7 %.
-  if (MODE == 2 && QT == 6 && ((slot >> 5) & 1u)) __builtin_amdgcn_s_setprio(1);
+  // TOD_K4X_STATIC_PRIO=0: a build without it, for the A/B (tools/match_pairs.sh prio).
+  if (TOD_K4X_STATIC_PRIO && HALF == 2 && QT == 6 && ((slot >> 5) & 1u)) __builtin_amdgcn_s_setprio(1);
   for (; step + 2u <= n_full; step += 2u) {                           // two steps per trip: the fragments ping-pong between a0 and a1
-    if constexpr (TAILS) {
+    if constexpr (PAIRS) {
+      fp4rows_pair_step<K, QT, 0>(a0, a1, rows, step, qb, q, q0 + c, nq, h, kc, pk, thr, best, acc_even, acc_odd, lane_row_base(step, h), n_local, n_pass);
+      fp4rows_pair_step<K, QT, 1>(a1, a0, rows, step + 1u, qb, q, q0 + c, nq, h, kc, pk, thr, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, n_pass);
+    } else if constexpr (TAILS) {
       fp4rows_split_step<K, QT, NF>(a0, a1, rows, step, qb, q, q0 + c, nq, h, kc, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local, n_pass);
       fp4rows_split_step<K, QT, NF>(a1, a0, rows, step + 1u, qb, q, q0 + c, nq, h, kc, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, n_pass);
     } else {
@@ -267,13 +384,16 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
     if (step + 2u >= next_share) {                                    // wave-uniform
       next_share += share_period;
       exchange_bounds<K, QT>(bound, q0, c, nq, best, seen, thr, [](uint32_t limit) { return thr_of_limit(limit); },
-                             [&](int t) { thrp[t] = thr[t] - kPartOff; });
+                             [&](int t) { if constexpr (!PAIRS) thrp[t] = thr[t] - kPartOff; });
     }
   }
   if constexpr (TAILS) {
     // the last unmasked step's last block is still a part: it completes here, in the same form, with the tails of step - 1
     if (step > 0u) {
-      fp4rows_block_test_part<K, NF>(acc_odd, rows, step - 1u, q, q0 + c + 32u * (QT - 1), nq, h, kc, thr[QT - 1], thrp[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 1], n_pass);
+      if constexpr (PAIRS)                                            // (the last pair, likewise)
+        fp4rows_pair_test<K>(acc_odd, pk, rows, step - 1u, q, q0 + c + 32u * (QT - 2), nq, h, kc, thr[QT - 2], thr[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 2], best[QT - 1], n_pass);
+      else
+        fp4rows_block_test_part<K, NF>(acc_odd, rows, step - 1u, q, q0 + c + 32u * (QT - 1), nq, h, kc, thr[QT - 1], thrp[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 1], n_pass);
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
       if (lane == 0 && half_stats) { atomicAdd(half_stats, n_pass); atomicAdd(half_stats + 1, step * (uint32_t)QT); }

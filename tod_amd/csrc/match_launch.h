@@ -18,6 +18,7 @@ struct MatchEnv {
   bool k4x_half_debug;  // TODHIP_K4X_HALF_DEBUG           print every report of the split controller to stderr
   int k4x_fp4_rows;     // TODHIP_K4X_FP4_ROWS=0|1         K4x: launches of 4 or 6 query blocks per wave read the rows from their resident fp4 copy (1)
   int k4x_fp4_rows_mb;  // TODHIP_K4X_FP4_ROWS_MB=n        K4x: the largest fp4 copy a context builds, in MiB (512); beyond it the packed rows are read
+  int k4x_pairs;        // TODHIP_K4X_PAIRS=0|1            K4x over the fp4 copy, split 2: two blocks per accumulator, tested at the launch's radius, where measured to win (1); 0: single blocks
 };
 inline const MatchEnv& match_env() {
   static const MatchEnv env = [] {
@@ -25,7 +26,7 @@ inline const MatchEnv& match_env() {
     const char* eng = getenv("TODHIP_K4_ENGINE");
     return MatchEnv{eng ? eng[0] : '\0', num("TODHIP_K4_MODE", -1), num("TODHIP_K4_WAVES_PER_CU", 0), num("TODHIP_K4X_WAVES_PER_CU", 0),
                     num("TODHIP_K4X_SHARE", 16), num("TODHIP_K4X_QT", 0), num("TODHIP_K4X_HALF", -1), getenv("TODHIP_K4X_HALF_DEBUG") != nullptr,
-                    num("TODHIP_K4X_FP4_ROWS", 1), num("TODHIP_K4X_FP4_ROWS_MB", 512)};
+                    num("TODHIP_K4X_FP4_ROWS", 1), num("TODHIP_K4X_FP4_ROWS_MB", 512), num("TODHIP_K4X_PAIRS", 1)};
   }();
   return env;
 }
@@ -97,7 +98,13 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
     ctx->k4x.take_report(ctx->k4x_stats_host.as<uint32_t>(), ctx->counters, min_split, env.k4x_half, env.k4x_half_debug);
   }
   const uint32_t split = ctx->k4x.next(min_split, env.k4x_half);       // 4 = whole blocks
-  const int mode = split == 2 ? 2 : split == 3 ? 3 : cut <= 128u ? 1 : 0;   // the kernels' MODE
+  // the kernels' MODE; 4 is hamming_topk_fp4rows' split 2 in single blocks (hamming_topk_mfma knows one split-2 form, MODE 2)
+  // The paired step where it was measured to win (profiles/match_pairs.json, the pass alone, adaptive form, parent and child
+  // alternating): six blocks per wave at every size (4 .. 32 frames: -6 .. -9 %), four blocks per wave for one frame's launch
+  // (0.106 -> 0.094 ms); at two frames (2000 queries, four blocks, tiles twice as long) it lost 4 % (0.131 -> 0.137), so launches of
+  // four blocks beyond 1024 queries keep the single-block step.
+  const bool pairs = env.k4x_pairs != 0 && (QT == 6 || nq <= 1024u);
+  const int mode = split == 2 ? (pairs ? 2 : 4) : split == 3 ? 3 : cut <= 128u ? 1 : 0;
   ctx->counters.last_block_split = split;
   uint32_t* const d_stats = split < 4 ? ctx->k4x_stats_dev.as<uint32_t>() : nullptr;
   const uint4* rows_fp4 = nullptr;                                     // the fp4 copy, where this launch reads it
@@ -114,12 +121,13 @@ int launch_topk_mfma_qt(todhip_ctx* ctx, const uint32_t* d_q, uint32_t nq, uint3
     constexpr int MODE = decltype(M)::value;
     if constexpr (QT == 4 || QT == 6)                                  // (eight blocks per wave leave no room for two steps' fragments)
       if (rows_fp4) return launch(hamming_topk_fp4rows<K, QT, MODE>, rows_fp4);
-    launch(hamming_topk_mfma<K, QT, MODE, PF2>, reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)));
+    launch(hamming_topk_mfma<K, QT, MODE == 4 ? 2 : MODE, PF2>, reinterpret_cast<const uint32_t*>(tod_db_rows(ctx)));
   };
   switch (mode) {
     case 0: launch_mode(std::integral_constant<int, 0>{}); break;
     case 1: launch_mode(std::integral_constant<int, 1>{}); break;
     case 2: launch_mode(std::integral_constant<int, 2>{}); break;
+    case 4: launch_mode(std::integral_constant<int, 4>{}); break;
     default: launch_mode(std::integral_constant<int, 3>{}); break;
   }
   if (int rc = timer.end()) return rc;

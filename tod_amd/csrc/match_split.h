@@ -13,6 +13,9 @@
 // level up (2 -> 3 -> whole blocks) when more than a quarter of the blocks went on, and probes one level down every hold_len
 // launches (32, doubling to 256 while the probes keep failing). `force` (todhip_set_matcher_block_split), else the process's
 // default (TODHIP_K4X_HALF): < 0 adaptive, 0 never, 2 / 3 always that split (1 = 2).
+// "Went on" at split 2 over the fp4 copy is judged at the LAUNCH's radius, not at each query's tightened threshold: the paired step
+// (fp4rows_pair_step, match_fp4rows.h) tests two blocks at once against one bias per launch. The count can only be higher than the
+// single-block step's, and it is what that step pays for: every such block runs the slow path.
 struct K4xSplit {
   int force = -1;
   uint32_t seq_sent = 0, seq_seen = 0;   // split launches sent; the last report looked at
