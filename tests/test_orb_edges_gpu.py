@@ -326,6 +326,33 @@ def test_one_context_alternating_masks_and_patterns():
     ctx.close()
 
 
+def test_one_context_through_the_graph_cache():
+    """The captured launch sequence's transitions in one fresh context, every call against the restatement: first capture, a geometry
+    without an admissible level (nothing is launched and the captured sequence goes), capture again, replay, a batch (the frame count
+    is part of the key), one frame again. TODHIP_ORB_NO_GRAPH is read once per process, so it stays as the suite was started: unset,
+    this walks the cache; set, the same calls launch directly."""
+    ctx = capi.Context(0)
+    img, (nl, sf), nf = image("small_lattice"), (16, 1.5), 50         # two levels yield keypoints, the upper ones have no pixels
+    want = ref("small_lattice", nf, nl, sf)
+    assert len(want[0]) == I.SMALL_LATTICE_CASES[(nl, sf)] == 17
+    nothing = I.tiny(62, 62)
+    assert I.TINY_SHAPES[(62, 62)] == 0
+    _equal(ctx.orb(img, nf, nl, sf), want)                             # A: captures
+    got = ctx.orb(nothing, 10, 1, 1.2)                                 # B: drops
+    assert len(got[0]) == len(got[1]) == len(got[2]) == 0
+    _equal(got, O.orb(nothing, 10, 1, 1.2))
+    _equal(ctx.orb(img, nf, nl, sf), want)                             # A: captures again
+    _equal(ctx.orb(img, nf, nl, sf), want)                             # A: replays
+    n, out = orb_batch(ctx, [img, img], nf, nl, sf, nf)                # A twice in one call
+    assert n == [17, 17]
+    for f in (0, 1):
+        b_got, untouched = out.frame(f, n[f])
+        _equal(b_got, want)
+        assert untouched
+    _equal(ctx.orb(img, nf, nl, sf), want)                             # A: one frame again
+    ctx.close()
+
+
 # ------------------------------------------------------------------------------------------ f. the learner through a stride
 def test_learner_view_through_a_stride(ctx):
     gray, mask = P.learn_views()[1]

@@ -25,9 +25,8 @@
     }                                                  \
   } while (0)
 
-// Growable device buffer: the hot path never calls hipMalloc once sizes have been seen.
-// The short, latency-bound kernels (ORB, verifier, merges) raise their wave priority: beside the matcher's
-// VALU-saturating waves a wave at default priority gets ~1/5 of a SIMD's issue slots.
+// The short, latency-bound kernels (verifier, merges) raise their wave priority: beside the matcher's VALU-saturating waves a wave
+// at default priority gets ~1/5 of a SIMD's issue slots. ORB's kernels do not (orb.hip says why).
 #ifndef TOD_LATENCY_PRIO_LEVEL
 #define TOD_LATENCY_PRIO_LEVEL 3
 #endif
@@ -38,6 +37,7 @@ constexpr size_t kDbSlackBytes = 2048;
 // (and hamming_topk_wide, match_wide.hip: the last 32-row step of 64-byte rows reaches 31 rows behind the end -- it fits, only just)
 static_assert(31 * 64 <= kDbSlackBytes, "a 32-row step of the widest binary row must end inside the slack");
 
+// Growable device buffer: the hot path never calls hipMalloc once sizes have been seen.
 // A buffer frees itself with its owner and is never copied (release() is for freeing early on purpose). Nothing that holds one may
 // have static storage duration: its destructor would call hipFree after the runtime has shut down.
 struct DevBuf {

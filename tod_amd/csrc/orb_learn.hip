@@ -12,7 +12,6 @@
 #include <numeric>
 #include <vector>
 
-#define TOD_LATENCY_PRIO_LEVEL 0
 #include "ctx.h"
 #include "orb_stages.h"
 
@@ -153,10 +152,10 @@ __global__ __launch_bounds__(64) void resolve_block_kernel(Walk A, uint32_t blk,
   if (l == 0) A.state[0] = nacc;
 }
 
-// what a learner's calls need besides its own data: the upload of a host view and the selection's scratch
+// what a learner's calls need besides its own data: the selection's scratch
 struct LearnWs : TodWs {
   static constexpr int kSlot = kWsLearn;
-  DevBuf in_img, ones, order, state, taken, both;
+  DevBuf ones, order, state, taken, both;
 };
 
 bool in_disc(int x, int y) { return x * x + y * y <= kPatternRadius2; }
@@ -247,19 +246,9 @@ int todhip_pattern_learn_add_view(todhip_ctx* ctx, todhip_pattern_learner* L, co
   if (n_added) *n_added = 0;
   if (!ctx || !L || !gray || stride < W || H == 0 || W == 0) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
-  LearnWs* ws = tod_ws<LearnWs>(ctx);
-  const size_t img_bytes = (size_t)H * W;                                // of the caller's rows only the W pixels are read
-  TOD_HIP(ws->in_img.reserve(mask ? 2 * img_bytes : img_bytes));         // the mask rides behind the image, both at row pitch W
-  if (stride == W)
-    TOD_HIP(hipMemcpyAsync(ws->in_img.p, gray, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-  else
-    TOD_HIP(hipMemcpy2DAsync(ws->in_img.p, W, gray, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-  uint8_t* dm = nullptr;
-  if (mask) {
-    dm = ws->in_img.as<uint8_t>() + img_bytes;
-    TOD_HIP(hipMemcpy2DAsync(dm, W, mask, stride, W, H, hipMemcpyHostToDevice, ctx->stream));
-  }
-  return todhip_pattern_learn_add_view_device(ctx, L, ws->in_img.p, dm, H, W, W, n_features, n_levels, scale_factor, n_added);
+  const uint8_t *d_gray = nullptr, *d_mask = nullptr;                    // in the ORB workspace, both at row pitch W
+  if (const int rc = tod_orb_stage_host_view(ctx, gray, mask, H, W, stride, &d_gray, &d_mask)) return rc;
+  return todhip_pattern_learn_add_view_device(ctx, L, d_gray, d_mask, H, W, W, n_features, n_levels, scale_factor, n_added);
 }
 
 int todhip_pattern_learn_responses(todhip_ctx* ctx, todhip_pattern_learner* L, uint32_t first, uint32_t count, uint32_t* words) {

@@ -1,31 +1,27 @@
-// What stage A's translation units share (orb.hip: detection and description; orb_learn.hip: the rBRIEF pattern learner): the level
-// table, the selection's record, the moment and steering arithmetic of describe_kernel, and the door through which the learner runs
-// the detection stages of todhip_orb_masked and reads where they left their results. Device functions here are the ONLY statement
-// of that arithmetic: a bit of the learner's response matrix and a bit of a descriptor come from the same expressions.
+// What stage A's translation units share (orb.hip: detection and description; orb_learn.hip: the rBRIEF pattern learner): the launch
+// plan with the level table and the selection's record (orb_plan.h), the wave-aggregated append, the moment and steering arithmetic of
+// describe_kernel, and the doors through which the learner stages a host view and runs the detection stages of todhip_orb_masked and
+// reads where they left their results. Device functions here are the ONLY statement of that arithmetic: a bit of the learner's
+// response matrix and a bit of a descriptor come from the same expressions.
 #pragma once
 
 #include "ctx.h"
+#include "orb_plan.h"
 
 namespace tod_orb {
 
-constexpr int kEdge = 31;
-constexpr int kHalfPatch = 15;
-constexpr int kMaxLevels = 16;
-constexpr int kPatternRadius2 = 13 * 13;   // every pattern point: x^2 + y^2 <= 169, so a rotated, rounded point stays inside the patch
-
-struct Cand { int x, y, score; float harris; };
-
-// control words of one level and one frame (device): what the selection kernels hand to each other without a
-// host round trip; [8 + l] = keypoints of level l
-constexpr uint32_t kCtlWords = 512;
-
-// geometry of the pyramid levels; want[l] == 0: the level yields nothing (too small, or no features asked of it)
-struct LevelTab {
-  uint32_t n_levels, F;
-  const uint8_t* img[kMaxLevels];                          // level l of frame 0 (frame stride: the level-0 pixel count)
-  uint32_t h[kMaxLevels], w[kMaxLevels], want[kMaxLevels];
-  float scale[kMaxLevels];
-};
+// Append to a list whose order is free: one atomic per wave on *counter (LDS or global memory), every flagged lane gets its slot.
+// Called by all lanes of the wave together.
+__device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool flag) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long bal = __builtin_amdgcn_ballot_w64(flag);
+  if (bal == 0ull) return 0u;
+  const uint32_t first = (uint32_t)__ffsll((long long)bal) - 1u;
+  uint32_t base = 0;
+  if (lane == first) base = atomicAdd(counter, (uint32_t)__popcll(bal));
+  base = (uint32_t)__builtin_amdgcn_readlane((int)base, (int)first);
+  return base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+}
 
 // integer moments over the radius-15 disc around (x, y): lane l < 31 owns row l - 15, every lane of the wave gets the sums
 __device__ __forceinline__ void patch_moments(const uint8_t* __restrict__ img, int W, int x, int y, const int (&umax)[kHalfPatch + 2],
@@ -72,6 +68,11 @@ struct Stages {
 
 }  // namespace tod_orb
 
+// orb.hip: a host image and its mask (may be null), both with row stride `stride`, into the context's ORB workspace at row pitch W
+// (of wider rows only the W pixels are read: the buffers may end with the last row's pixels); *d_mask is null without a mask. The
+// copies are on the context's stream.
+int tod_orb_stage_host_view(todhip_ctx* ctx, const uint8_t* gray, const uint8_t* mask, uint32_t H, uint32_t W, uint32_t stride,
+                            const uint8_t** d_gray, const uint8_t** d_mask);
 // orb.hip: the stages of todhip_orb_masked (capacity n_features, built-in pattern) on a device-resident frame; d_mask (may be null)
 // has row pitch W. Synchronizes the stream.
 int tod_orb_stages(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask, uint32_t H, uint32_t W, uint32_t stride,
