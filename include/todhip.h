@@ -378,6 +378,27 @@ int todhip_verify_batch_device_depth(todhip_ctx*, uint32_t n_frames, const void*
                                      uint32_t n_objs, const todhip_verify_params*, todhip_rng* rng, todhip_pose* poses,
                                      uint32_t* n_poses, uint32_t* pose_ptr, uint32_t* inlier_kp, uint32_t* n_inlier_kp);
 
+/* The depth image at the sensor's own size, dH x dW, in front of todhip_verify[_batch]_device_depth (RescaledRegisteredDepth in front
+ * of DepthTo3d, detector.py:26,66-67; the arithmetic of Trainer.cpp:62-81). Definition: the result -- poses, their order, R and t bit
+ * for bit, inlier lists, the generator's final state -- is that of todhip_rescale_depth_device(d_depth, depth_is_u16, dH, dW -> H, W,
+ * nearest) on each frame followed by todhip_verify[_batch]_device_depth on the float result with depth_is_u16 = 0. No H x W image is
+ * made: the rescaled pixel is computed from its taps at each keypoint's pixel, inside the kernel that looks the keypoints' 3D points
+ * up. H, W and K9 are the IMAGE's (keypoints are image pixels). A keypoint in the NaN band below the resized rows, or on a NaN / 0 tap,
+ * has no 3D point, exactly as after a rescale. The batch form reads frame f's depth at f * dH * dW values. A geometry that
+ * todhip_rescale_depth refuses (the resized rows would not fit into H): TODHIP_EINVAL before any device work. dH == H and dW == W:
+ * todhip_verify[_batch]_device_depth. */
+int todhip_verify_device_depth_rescaled(todhip_ctx*, const void* d_kp_xy, uint32_t nq, const void* d_depth, int depth_is_u16,
+                                        uint32_t dH, uint32_t dW, int nearest, uint32_t H, uint32_t W, const float* K9,
+                                        const void* d_counts, const void* d_matches, const void* d_matches_xyz, uint32_t k,
+                                        const float* spans, uint32_t n_objs, const todhip_verify_params*, todhip_rng* rng,
+                                        todhip_pose* poses, uint32_t* n_poses, uint32_t* inlier_kp, uint32_t* n_inlier_kp);
+int todhip_verify_batch_device_depth_rescaled(todhip_ctx*, uint32_t n_frames, const void* d_kp_xy, uint32_t nq, const void* d_depth,
+                                              int depth_is_u16, uint32_t dH, uint32_t dW, int nearest, uint32_t H, uint32_t W,
+                                              const float* K9, const void* d_counts, const void* d_matches, const void* d_matches_xyz,
+                                              uint32_t k, const float* spans, uint32_t n_objs, const todhip_verify_params*,
+                                              todhip_rng* rng, todhip_pose* poses, uint32_t* n_poses, uint32_t* pose_ptr,
+                                              uint32_t* inlier_kp, uint32_t* n_inlier_kp);
+
 /* ---- stage A: ORB features (ecto_opencv FeatureDescriptor -> cv::ORB; detector.py:10,27) --------- */
 /* gray: H x W u8, row stride `stride` >= W: (H - 1) * stride + W bytes, nothing behind the last row's pixels is read (a region of
  * a larger image). A pyramid level that rounds to fewer than 63 pixels either way yields nothing; an image without any other level
@@ -406,6 +427,13 @@ int todhip_orb_device(todhip_ctx*, const void* d_gray, uint32_t H, uint32_t W, u
 int todhip_orb_batch_device(todhip_ctx*, const void* d_gray, uint32_t n_frames, uint64_t frame_stride, uint32_t H, uint32_t W,
                             uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
                             void* d_kp_xy, void* d_kp_aux, void* d_desc, uint32_t cap, uint32_t* n_out);
+
+/* The batch with a mask per frame (todhip_orb_masked's `mask`, in HBM): d_mask is n_frames x H x W u8, packed (frame f's mask at
+ * d_mask + f * H * W, row pitch W, whatever stride and frame_stride are). Frame f's result equals todhip_orb_masked's on frame f with
+ * mask f. d_mask == NULL: todhip_orb_batch_device. */
+int todhip_orb_batch_device_masked(todhip_ctx*, const void* d_gray, const void* d_mask, uint32_t n_frames, uint64_t frame_stride,
+                                   uint32_t H, uint32_t W, uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor,
+                                   const int8_t* pattern, void* d_kp_xy, void* d_kp_aux, void* d_desc, uint32_t cap, uint32_t* n_out);
 
 /* ---- stage C without depth (SURVEY 8(f) row N4 b) -------------------------------------------------------- */
 /* The branch GuessGenerator::process leaves empty when `points3d` is empty (GuessGenerator.cpp:147-152 "Only use 2d to 3d
@@ -461,6 +489,11 @@ int todhip_verify_2d_batch_device(todhip_ctx*, uint32_t n_frames, const void* d_
  * todhip_orb_device (capacity n_features) -> todhip_match_device on its n_kp descriptors -> todhip_verify_device_depth with a
  * generator seeded rng_seed: keypoints, poses and their order, R and t bit for bit, inlier lists. A frame with fewer than n_features
  * keypoints is padded with match counts 0 on the device.
+ * The detector's two further inputs (detector.py:26,41,66-67) extend that chain and leave it as it is when unused: with masks
+ * (todhip_pipeline_submit_masked[_device]) its first link is masked ORB -- todhip_orb_masked's result on frame f with mask f, in the
+ * device form -- and with a depth size of its own (todhip_pipeline_set_depth_size) todhip_rescale_depth_device stands between the
+ * matcher and todhip_verify_device_depth: masked ORB -> todhip_match_device -> todhip_rescale_depth_device -> todhip_verify_device_depth.
+ * Inside, the steps run todhip_orb_batch_device_masked and todhip_verify_batch_device_depth_rescaled.
  * Threading: submit, wait and get_stats may be called from any threads, also concurrently; each ticket is waited for once.
  * The pipeline uses 1 + orb_workers + verify_workers streams plus the verifier's two process-wide side streams; see INTEGRATION.md
  * for the number of hardware queues a host should allow before HIP initialises. */
@@ -469,7 +502,7 @@ enum { TODHIP_FRAME_GRAY8 = 0, TODHIP_FRAME_BGR8 = 1, TODHIP_FRAME_BGRA8 = 2 };
 typedef struct {
   uint32_t struct_size;                /* sizeof(todhip_pipeline_params), as todhip_pipeline_default_params sets it */
   uint32_t frames_per_step;            /* B: 1..64 frames per submit */
-  uint32_t H, W;                       /* every frame; the depth image has the same size */
+  uint32_t H, W;                       /* every frame; the depth image has the same size unless todhip_pipeline_set_depth_size says otherwise */
   int      frame_format;               /* TODHIP_FRAME_* */
   int      depth_is_u16;               /* uint16 mm (0 = none) or float m (NaN = none) */
   float    K9[9];                      /* camera matrix, row-major */
@@ -507,7 +540,7 @@ todhip_ctx* todhip_pipeline_matcher(todhip_pipeline*);
 int  todhip_pipeline_db_load(todhip_pipeline*, const todhip_object*, uint32_t n_objs, uint32_t desc_bytes);
 int  todhip_pipeline_db_load_device(todhip_pipeline*, const todhip_object*, uint32_t n_objs, uint32_t desc_bytes);
 /* n_frames in 1..frames_per_step, frames and depth images densely packed back to back without row padding: a frame is H*W bytes
- * (GRAY8), H*W*3 (BGR8) or H*W*4 (BGRA8), a depth image H*W uint16 or float values. Tickets count up from 1. Never blocks on the
+ * (GRAY8), H*W*3 (BGR8) or H*W*4 (BGRA8), a depth image H*W uint16 or float values (dH*dW after todhip_pipeline_set_depth_size). Tickets count up from 1. Never blocks on the
  * GPU: with ring_depth tickets submitted and not yet waited for it returns TODHIP_EBUSY (wait for one, then submit again).
  * Host form: copies into pinned staging owned by the ring slot and returns; the caller may reuse its buffers at once.
  * Device form: no copy -- the stages READ THE CALLER'S DEVICE BUFFERS UNTIL THAT TICKET'S todhip_pipeline_wait HAS RETURNED the
@@ -530,6 +563,19 @@ int  todhip_pipeline_get_stats(todhip_pipeline*, todhip_pipeline_stats* out);
  * pattern learned by todhip_pattern_learn_* reaches the batched path. The DB must hold descriptors of the same pattern.
  * TODHIP_EBUSY while a ticket is outstanding. */
 int  todhip_pipeline_set_pattern(todhip_pipeline*, const int8_t* pattern /* 256 x 4; NULL = built-in */);
+/* The size of a depth image, from the next submit on: dH x dW values (uint16 or float as depth_is_u16 says), rescaled to the image
+ * as todhip_rescale_depth does (nearest != 0: its nearest mode) -- see the definition above and todhip_verify_device_depth_rescaled.
+ * (0, 0): the image's size again. The host form's staging and upload buffers follow. TODHIP_EINVAL where todhip_rescale_depth refuses
+ * the geometry (nothing changes), TODHIP_EBUSY while a ticket is outstanding. */
+int  todhip_pipeline_set_depth_size(todhip_pipeline*, uint32_t dH, uint32_t dW, int nearest);
+/* todhip_pipeline_submit[_device] with a mask per frame: masks is n_frames x H x W u8, packed, one channel whatever frame_format is;
+ * only pixels with mask != 0 can become keypoints (todhip_orb_masked). masks == NULL: todhip_pipeline_submit[_device]. Host form: the
+ * masks are copied into pinned staging of the slot and go up on the ORB worker's stream, as the frames do. Device form: d_masks is
+ * read under the frames' lifetime rule. A step's masks apply to that step only. */
+int  todhip_pipeline_submit_masked(todhip_pipeline*, const uint8_t* frames, const uint8_t* masks, const void* depth, uint32_t n_frames,
+                                   uint64_t* ticket);
+int  todhip_pipeline_submit_masked_device(todhip_pipeline*, const void* d_frames, const void* d_masks, const void* d_depth,
+                                          uint32_t n_frames, uint64_t* ticket);
 /* todhip_db_select_objects on the pipeline's matcher context, from the next submit on; the verifier workers keep the spans of every
  * object (poses name objects of the full DB). TODHIP_EBUSY while a ticket is outstanding. */
 int  todhip_pipeline_select_objects(todhip_pipeline*, const uint32_t* ids, uint32_t n_ids);
@@ -663,6 +709,12 @@ int todhip_test_adjacency(todhip_ctx*, const float* train_xyz, const float* quer
  * (test/test_maximum_clique.cpp:7-53). out3 = {clique size, internal error flag, search steps}. */
 int todhip_test_clique(todhip_ctx*, uint32_t m, const uint32_t* edges, uint32_t n_edges, uint32_t minimal_size,
                        uint32_t* out3);
+/* The depth lookup of the verifier's cluster kernel alone: z_out[i] = the depth in metres at pixel (int(kp_xy[2i]), int(kp_xy[2i+1]))
+ * of rescale_depth's H x W result of the device-resident dH x dW image, computed as todhip_verify_device_depth_rescaled computes it
+ * (equal sizes: the plain load of todhip_verify_device_depth). kp_xy (n x 2) and z_out (n) are host arrays. A position outside the
+ * H x W image is what the verifier refuses: TODHIP_ERANGE, that z_out entry untouched, the others filled. */
+int todhip_test_depth_lookup(todhip_ctx*, const void* d_depth, int depth_is_u16, uint32_t dH, uint32_t dW, int nearest, uint32_t H,
+                             uint32_t W, const float* kp_xy, uint32_t n, float* z_out);
 /* The same graph through the form of the search the verifier's gate runs: sac_model_registration_graph.h:260-262 only asks whether
  * the clique FindClique(minimal_size) returns is larger than minimal_size, which is decided once Q holds minimal_size vertices
  * with a common neighbour (or at the first leaf of at least that size) -- the search stops there. out3[0] = that clique's size

@@ -96,6 +96,8 @@ EXPORTS = [
     "todhip_match_radius", "todhip_match_radius_device",
     "todhip_match_radius_shard_device", "todhip_merge_radius_shards_device", "todhip_merge_radius_shards_device_on",
     "todhip_db_desc_bytes",
+    "todhip_orb_batch_device_masked", "todhip_verify_device_depth_rescaled", "todhip_verify_batch_device_depth_rescaled",
+    "todhip_test_depth_lookup", "todhip_pipeline_set_depth_size", "todhip_pipeline_submit_masked", "todhip_pipeline_submit_masked_device",
 ]
 
 MAX_PER_QUERY_LIMIT = 1024
@@ -167,6 +169,19 @@ def lib():
             L.todhip_merge_radius_shards_device_on.restype = C.c_int
         if hasattr(L, "todhip_db_desc_bytes"):                        # (as above)
             L.todhip_db_desc_bytes.argtypes, L.todhip_db_desc_bytes.restype = [C.c_void_p, C.c_void_p], C.c_int
+        if hasattr(L, "todhip_verify_device_depth_rescaled"):        # (as above)
+            u32, vp, ci = C.c_uint32, C.c_void_p, C.c_int
+            L.todhip_orb_batch_device_masked.argtypes = [vp, vp, vp, u32, C.c_uint64, u32, u32, u32, u32, u32, C.c_float, vp, vp, vp, vp, u32, vp]
+            L.todhip_orb_batch_device_masked.restype = ci
+            tail = [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp]        # counts, matches, xyz, k, spans, n_objs, params, rng, poses, n_poses
+            L.todhip_verify_device_depth_rescaled.argtypes = [vp, vp, u32, vp, ci, u32, u32, ci, u32, u32, vp] + tail + [vp, vp]
+            L.todhip_verify_device_depth_rescaled.restype = ci
+            L.todhip_verify_batch_device_depth_rescaled.argtypes = [vp, u32, vp, u32, vp, ci, u32, u32, ci, u32, u32, vp] + tail + [vp, vp, vp]
+            L.todhip_verify_batch_device_depth_rescaled.restype = ci
+            L.todhip_test_depth_lookup.argtypes, L.todhip_test_depth_lookup.restype = [vp, vp, ci, u32, u32, ci, u32, u32, vp, u32, vp], ci
+            L.todhip_pipeline_set_depth_size.argtypes, L.todhip_pipeline_set_depth_size.restype = [vp, u32, u32, ci], ci
+            L.todhip_pipeline_submit_masked.argtypes, L.todhip_pipeline_submit_masked.restype = [vp, vp, vp, vp, u32, vp], ci
+            L.todhip_pipeline_submit_masked_device.argtypes, L.todhip_pipeline_submit_masked_device.restype = [vp, vp, vp, vp, u32, vp], ci
         _lib = L
     return _lib
 
@@ -557,6 +572,43 @@ class Context:
         _check(rc, "todhip_verify_batch_device")
         return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
 
+    def verify_device_depth_rescaled(self, d_kp_xy, nq, d_depth, depth_is_u16, dH, dW, nearest, H, W, K, d_counts, d_matches, d_xyz, k,
+                                     spans, min_inliers, n_iter, err, rng, max_poses=64):
+        """verify_device_depth on a dH x dW depth image: the result of rescale_depth_device followed by verify_device_depth, without
+        the H x W intermediate (H, W, K: the image's)."""
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
+        K9 = _k9(K)
+        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq)
+        rc = lib().todhip_verify_device_depth_rescaled(self._h, d_kp_xy, nq, d_depth, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0,
+                                                       H, W, _np_ptr(K9), d_counts, d_matches, d_xyz, k, _np_ptr(sp), len(sp),
+                                                       C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
+        _check(rc, "todhip_verify_device_depth_rescaled")
+        return _pose_list(poses, 0, n_poses.value, inl)
+
+    def verify_batch_device_depth_rescaled(self, n_frames, d_kp_xy, nq, d_depth, depth_is_u16, dH, dW, nearest, H, W, K, d_counts,
+                                           d_matches, d_xyz, k, spans, min_inliers, n_iter, err, rngs, max_poses=16):
+        """The batch form (d_depth: n_frames x dH x dW, rngs: ctypes array Rng * n_frames); a list per frame of lists of pose dicts."""
+        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
+        K9 = _k9(K)
+        poses, n_poses, inl, n_inl, pose_ptr = _pose_out(max_poses, nq, n_frames, cache=self)
+        rc = lib().todhip_verify_batch_device_depth_rescaled(self._h, n_frames, d_kp_xy, nq, d_depth, 1 if depth_is_u16 else 0, dH, dW,
+                                                             1 if nearest else 0, H, W, _np_ptr(K9), d_counts, d_matches, d_xyz, k,
+                                                             _np_ptr(sp), len(sp), C.byref(prm), rngs, poses, C.byref(n_poses), pose_ptr,
+                                                             _np_ptr(inl), C.byref(n_inl))
+        _check(rc, "todhip_verify_batch_device_depth_rescaled")
+        return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
+
+    def test_depth_lookup(self, d_depth, depth_is_u16, dH, dW, nearest, H, W, kp_xy, fill=0.0):
+        """z (f32 [n]) of the verifier's depth lookup at the pixel positions kp_xy [n, 2]. Returns (status, z): OK, or ERANGE when a
+        position lies outside the H x W image (its z keeps `fill`)."""
+        kp = np.ascontiguousarray(kp_xy, np.float32).reshape(-1, 2)
+        z = np.full(len(kp), fill, np.float32)
+        rc = lib().todhip_test_depth_lookup(self._h, d_depth, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0, H, W, _np_ptr(kp),
+                                            len(kp), _np_ptr(z))
+        if rc not in (OK, ERANGE):
+            raise TodError(rc, "todhip_test_depth_lookup")
+        return rc, z
+
     def verify_trace(self, cap=4096):
         arr = (RoundTrace * cap)()
         n = C.c_uint32(cap)
@@ -645,6 +697,17 @@ class Context:
                                            C.c_void_p(d_kp_aux),
                                            C.c_void_p(d_desc), C.c_uint32(cap), n)
         _check(rc, "todhip_orb_batch_device")
+        return list(n)
+
+    def orb_batch_device_masked(self, d_gray, d_mask, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy,
+                                d_kp_aux, d_desc, cap, pattern=None):
+        """orb_batch_device with a packed mask per frame (d_mask: n_frames x H x W u8 in HBM; None / 0: no masks)."""
+        n = (C.c_uint32 * n_frames)()
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
+        rc = lib().todhip_orb_batch_device_masked(self._h, d_gray, d_mask or None, n_frames, frame_stride, H, W, stride, n_features,
+                                                  n_levels, scale_factor, None if pat is None else _np_ptr(pat), d_kp_xy, d_kp_aux,
+                                                  d_desc, cap, n)
+        _check(rc, "todhip_orb_batch_device_masked")
         return list(n)
 
     def rescale_depth(self, depth, H, W, nearest=False):
@@ -881,6 +944,31 @@ class Pipeline:
         rc = lib().todhip_pipeline_submit(self._h, _np_ptr(fr), _np_ptr(dp), C.c_uint32(n), C.byref(t))
         if rc == OK:
             self._n[t.value] = n
+        return rc, t.value
+
+    def set_depth_size(self, dH, dW, nearest=False):
+        """A depth image is dH x dW from the next submit on ((0, 0): the image's size); returns the status (EINVAL: a geometry
+        rescale_depth refuses, EBUSY while a ticket is outstanding)."""
+        return lib().todhip_pipeline_set_depth_size(self._h, dH, dW, 1 if nearest else 0)
+
+    def submit_masked(self, frames, masks, depth, n_frames=None):
+        """submit with masks u8 [n, H, W] (None: submit). Returns (status, ticket)."""
+        fr = np.ascontiguousarray(frames, np.uint8)
+        mk = None if masks is None else np.ascontiguousarray(masks, np.uint8)
+        dp = np.ascontiguousarray(depth, np.uint16 if self.params.depth_is_u16 else np.float32)
+        n = len(fr) if n_frames is None else n_frames
+        t = C.c_uint64(0)
+        rc = lib().todhip_pipeline_submit_masked(self._h, _np_ptr(fr), None if mk is None else _np_ptr(mk), _np_ptr(dp), n, C.byref(t))
+        if rc == OK:
+            self._n[t.value] = n
+        return rc, t.value
+
+    def submit_masked_device(self, d_frames, d_masks, d_depth, n_frames):
+        """submit_device with d_masks (n x H x W u8 in HBM, None / 0: no masks), read as long as the frames are."""
+        t = C.c_uint64(0)
+        rc = lib().todhip_pipeline_submit_masked_device(self._h, d_frames, d_masks or None, d_depth, n_frames, C.byref(t))
+        if rc == OK:
+            self._n[t.value] = n_frames
         return rc, t.value
 
     def submit_device(self, d_frames, d_depth, n_frames):

@@ -231,16 +231,26 @@ int tod_orb_stages(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask
 
 extern "C" {
 
-int todhip_orb_batch_device(todhip_ctx* ctx, const void* d_gray, uint32_t n_frames, uint64_t frame_stride, uint32_t H, uint32_t W,
-                            uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
-                            void* d_kp_xy, void* d_kp_aux, void* d_desc, uint32_t cap, uint32_t* n_out) {
+// d_mask: frame f's mask at d_mask + f * H * W (packed, whatever the frames' strides are), or NULL. orb_device copies the masks
+// into the workspace (one launch for all frames) and fast_nms_kernel offsets that copy per frame; the graph cache's key holds the
+// copy's address or NULL, so a masked and an unmasked call of one shape never replay each other's sequence.
+int todhip_orb_batch_device_masked(todhip_ctx* ctx, const void* d_gray, const void* d_mask, uint32_t n_frames, uint64_t frame_stride,
+                                   uint32_t H, uint32_t W, uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor,
+                                   const int8_t* pattern, void* d_kp_xy, void* d_kp_aux, void* d_desc, uint32_t cap, uint32_t* n_out) {
   if (!ctx || !d_gray || !d_kp_xy || !d_kp_aux || !d_desc || !n_out || stride < W || n_frames == 0) return TODHIP_EINVAL;
   if (n_frames > 1 && frame_stride < (uint64_t)H * stride) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
   for (uint32_t f = 0; f < n_frames; ++f) n_out[f] = 0;
-  return orb_device(ctx, {reinterpret_cast<const uint8_t*>(d_gray), (size_t)frame_stride, nullptr, n_frames, H, W, stride},
+  return orb_device(ctx, {reinterpret_cast<const uint8_t*>(d_gray), (size_t)frame_stride, reinterpret_cast<const uint8_t*>(d_mask), n_frames, H, W, stride},
                     {n_features, n_levels, scale_factor, pattern},
                     {reinterpret_cast<float*>(d_kp_xy), reinterpret_cast<float*>(d_kp_aux), reinterpret_cast<uint8_t*>(d_desc), cap, n_out});
+}
+
+int todhip_orb_batch_device(todhip_ctx* ctx, const void* d_gray, uint32_t n_frames, uint64_t frame_stride, uint32_t H, uint32_t W,
+                            uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
+                            void* d_kp_xy, void* d_kp_aux, void* d_desc, uint32_t cap, uint32_t* n_out) {
+  return todhip_orb_batch_device_masked(ctx, d_gray, nullptr, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor,
+                                        pattern, d_kp_xy, d_kp_aux, d_desc, cap, n_out);
 }
 
 // one frame: the batch of one, the capacity arrives in *n_out

@@ -1,7 +1,8 @@
 // todhip_pipeline (include/todhip.h): ORB -> matcher -> verifier on batches of frames behind submit / wait, with the stage overlap
 // of tod_amd/pipeline.py's StagePipeline as bench.py drives it -- in C++, on plain HIP streams and events and std::thread. It calls
-// the stages only through their public entry points (todhip_orb_batch_device, todhip_match_device, todhip_verify_batch_device_depth)
-// and adds two kernels of its own: the colour conversion in front of ORB and the padding rule behind the matcher.
+// the stages only through their public entry points (todhip_orb_batch_device[_masked], todhip_match_device,
+// todhip_verify_batch_device_depth[_rescaled]) and adds two kernels of its own: the colour conversion in front of ORB and the
+// padding rule behind the matcher.
 //
 // A ticket owns one ring slot from submit to wait; the slot holds every buffer of its step. Step i (ticket i + 1) goes through ORB
 // worker i % orb_workers, the one matcher thread (in ticket order) and verifier worker i % verify_workers; each worker thread is the
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "depth_rescale.h"
 
 namespace {
 
@@ -107,6 +109,9 @@ struct Slot {
   bool host_form = false;
   const void* d_frames = nullptr;        // what the stages read: the caller's buffers (device form) or this slot's uploads
   const void* d_depth = nullptr;
+  const void* d_masks = nullptr;         // this step's masks, or nullptr: set by every submit, so a slot's earlier masks never reach a later step
+  bool host_masks = false;               // the masks are in st_masks and go up with the frames
+  DevBuf up_masks; HostBuf st_masks;     // the host form's masks (allocated by the slot's first masked submit)
   DevBuf up_frames, up_depth, gray, kp, aux, desc, counts, matches, xyz;
   HostBuf st_frames, st_depth, h_kp;     // pinned: staging of the host form, the keypoints on their way out
   hipEvent_t matched = nullptr;          // recorded behind the matcher's work of the step
@@ -124,6 +129,9 @@ struct todhip_pipeline {
   int device = 0;
   uint32_t B = 0, NO = 0, NV = 0, D = 0, nq = 0;
   size_t frame_bytes = 0, depth_bytes = 0, px = 0;
+  // todhip_pipeline_set_depth_size: written only while every slot is free. depth_rescaled: a depth image is dH x dW and the verifier
+  // looks rescale_depth's result up at the keypoints; otherwise it has the image's size
+  uint32_t dH = 0, dW = 0; int depth_nearest = 0; bool depth_rescaled = false;
   uint32_t inl_cap = 0, pose_cap = 0;
 
   todhip_ctx* mctx = nullptr;
@@ -170,8 +178,9 @@ struct todhip_pipeline {
   void orb_worker(uint32_t w);
   void match_worker();
   void verify_worker(uint32_t w);
-  int reserve_host_form(Slot* s);
-  int submit(const void* frames, const void* depth, uint32_t n_frames, uint64_t* ticket, bool host_form);
+  int reserve_host_form(Slot* s, bool masks);
+  int submit(const void* frames, const void* masks, const void* depth, uint32_t n_frames, uint64_t* ticket, bool host_form);
+  int set_depth_size(uint32_t dH_in, uint32_t dW_in, int nearest);
   int db_load(const todhip_object* objs, uint32_t n_objs_in, uint32_t desc_bytes, bool device_src);
 };
 
@@ -184,6 +193,10 @@ int todhip_pipeline::orb_step(Slot* s, uint32_t w) {
     PIPE_HIP(hipMemcpyAsync(s->up_frames.p, s->st_frames.p, n * frame_bytes, hipMemcpyHostToDevice, st));
     PIPE_HIP(hipMemcpyAsync(s->up_depth.p, s->st_depth.p, n * depth_bytes, hipMemcpyHostToDevice, st));   // complete when ORB returns
     s->d_frames = s->up_frames.p; s->d_depth = s->up_depth.p;
+    if (s->host_masks) {
+      PIPE_HIP(hipMemcpyAsync(s->up_masks.p, s->st_masks.p, n * px, hipMemcpyHostToDevice, st));
+      s->d_masks = s->up_masks.p;
+    }
   }
   const void* gray = s->d_frames;
   if (prm.frame_format != TODHIP_FRAME_GRAY8) {
@@ -192,8 +205,8 @@ int todhip_pipeline::orb_step(Slot* s, uint32_t w) {
     if (rc != TODHIP_OK) return rc;
     gray = s->gray.p;
   }
-  return todhip_orb_batch_device(octx[w], gray, n, px, prm.H, prm.W, prm.W, prm.n_features, prm.n_levels, prm.scale_factor,
-                                 has_pattern ? pattern : nullptr, s->kp.p, s->aux.p, s->desc.p, nq, s->n_kp);
+  return todhip_orb_batch_device_masked(octx[w], gray, s->d_masks, n, px, prm.H, prm.W, prm.W, prm.n_features, prm.n_levels,
+                                        prm.scale_factor, has_pattern ? pattern : nullptr, s->kp.p, s->aux.p, s->desc.p, nq, s->n_kp);
 }
 
 int todhip_pipeline::match_step(Slot* s) {
@@ -220,9 +233,14 @@ int todhip_pipeline::verify_step(Slot* s, uint32_t w) {
   todhip_rng rngs[kMaxFrames];
   for (uint32_t f = 0; f < n; ++f) rngs[f] = rng0;
   s->n_poses = pose_cap; s->n_inl = inl_cap;
-  const int rc = todhip_verify_batch_device_depth(vctx[w], n, s->kp.p, nq, s->d_depth, prm.depth_is_u16, prm.H, prm.W, prm.K9,
-                                                  s->counts.p, s->matches.p, s->xyz.p, prm.k, spans.data(), n_objs, &prm.verify, rngs,
-                                                  s->poses.data(), &s->n_poses, s->pose_ptr.data(), s->inl.get(), &s->n_inl);
+  const int rc = depth_rescaled
+      ? todhip_verify_batch_device_depth_rescaled(vctx[w], n, s->kp.p, nq, s->d_depth, prm.depth_is_u16, dH, dW, depth_nearest, prm.H,
+                                                  prm.W, prm.K9, s->counts.p, s->matches.p, s->xyz.p, prm.k, spans.data(), n_objs,
+                                                  &prm.verify, rngs, s->poses.data(), &s->n_poses, s->pose_ptr.data(), s->inl.get(),
+                                                  &s->n_inl)
+      : todhip_verify_batch_device_depth(vctx[w], n, s->kp.p, nq, s->d_depth, prm.depth_is_u16, prm.H, prm.W, prm.K9,
+                                         s->counts.p, s->matches.p, s->xyz.p, prm.k, spans.data(), n_objs, &prm.verify, rngs,
+                                         s->poses.data(), &s->n_poses, s->pose_ptr.data(), s->inl.get(), &s->n_inl);
   if (rc != TODHIP_OK) return rc;
   PIPE_HIP(hipStreamSynchronize(st));                              // the keypoint copy (the verifier returns early on an empty step)
   return TODHIP_OK;
@@ -276,14 +294,16 @@ void todhip_pipeline::verify_worker(uint32_t w) {
   }
 }
 
-int todhip_pipeline::reserve_host_form(Slot* s) {
-  if (s->st_frames.p) return TODHIP_OK;
+// (every reserve returns at once when the buffer is large enough; the depth pair follows todhip_pipeline_set_depth_size, the mask
+// pair exists from the slot's first masked step on)
+int todhip_pipeline::reserve_host_form(Slot* s, bool masks) {
   PIPE_HIP(s->st_frames.reserve(B * frame_bytes)); PIPE_HIP(s->st_depth.reserve(B * depth_bytes));
   PIPE_HIP(s->up_frames.reserve(B * frame_bytes)); PIPE_HIP(s->up_depth.reserve(B * depth_bytes));
+  if (masks) { PIPE_HIP(s->st_masks.reserve(B * px)); PIPE_HIP(s->up_masks.reserve(B * px)); }
   return TODHIP_OK;
 }
 
-int todhip_pipeline::submit(const void* frames, const void* depth, uint32_t n_frames, uint64_t* ticket, bool host_form) {
+int todhip_pipeline::submit(const void* frames, const void* masks, const void* depth, uint32_t n_frames, uint64_t* ticket, bool host_form) {
   if (!frames || !depth || !ticket || n_frames == 0 || n_frames > B) return TODHIP_EINVAL;
   Slot* s = nullptr;
   {
@@ -295,14 +315,16 @@ int todhip_pipeline::submit(const void* frames, const void* depth, uint32_t n_fr
     s->state = kFilling; s->ticket = next_ticket++;
     s->n_frames = n_frames; s->status = TODHIP_OK; s->host_form = host_form;
     s->d_frames = frames; s->d_depth = depth;
+    s->d_masks = host_form ? nullptr : masks; s->host_masks = host_form && masks;
     s->n_poses = s->n_inl = 0;
   }
   int rc = TODHIP_OK;
   if (host_form) {                                                 // outside the lock: tens of megabytes per step
-    rc = hipSetDevice(device) == hipSuccess ? reserve_host_form(s) : TODHIP_EHIP;
+    rc = hipSetDevice(device) == hipSuccess ? reserve_host_form(s, masks != nullptr) : TODHIP_EHIP;
     if (rc == TODHIP_OK) {
       std::memcpy(s->st_frames.p, frames, n_frames * frame_bytes);
       std::memcpy(s->st_depth.p, depth, n_frames * depth_bytes);
+      if (masks) std::memcpy(s->st_masks.p, masks, n_frames * px);
     }
   }
   std::lock_guard<std::mutex> lk(mu);
@@ -310,6 +332,22 @@ int todhip_pipeline::submit(const void* frames, const void* depth, uint32_t n_fr
   *ticket = s->ticket;
   s->state = kSubmitted;
   cv.notify_all();
+  return TODHIP_OK;
+}
+
+int todhip_pipeline::set_depth_size(uint32_t dH_in, uint32_t dW_in, int nearest) {
+  tod::RescaleGeom g = {};
+  const bool own = dH_in == 0 && dW_in == 0;               // the image's size again
+  if (!own && (dH_in == 0 || dW_in == 0 || dH_in > 16384 || dW_in > 16384 || !tod::rescale_geometry(dH_in, dW_in, prm.H, prm.W, nearest, &g)))
+    return TODHIP_EINVAL;
+  std::lock_guard<std::mutex> lk(mu);
+  if (dead) return TODHIP_EHIP;
+  for (const Slot& s : slots)
+    if (s.state != kFree) return TODHIP_EBUSY;
+  dH = own ? prm.H : dH_in; dW = own ? prm.W : dW_in;
+  depth_nearest = nearest ? 1 : 0;
+  depth_rescaled = !own && g.mode != tod::RescaleGeom::kEqual;
+  depth_bytes = (size_t)dH * dW * (prm.depth_is_u16 ? 2u : 4u);
   return TODHIP_OK;
 }
 
@@ -384,6 +422,7 @@ int todhip_pipeline_create(int device, const todhip_pipeline_params* in, todhip_
   p->px = (size_t)q.H * q.W;
   p->frame_bytes = p->px * (q.frame_format == TODHIP_FRAME_GRAY8 ? 1u : q.frame_format == TODHIP_FRAME_BGR8 ? 3u : 4u);
   p->depth_bytes = p->px * (q.depth_is_u16 ? 2u : 4u);
+  p->dH = q.H; p->dW = q.W;
   p->pose_cap = p->B * q.max_poses_per_frame;
   const uint64_t inl = (uint64_t)p->pose_cap * p->nq;
   p->inl_cap = (uint32_t)std::min<uint64_t>(inl, 0x40000000ull);
@@ -477,10 +516,21 @@ int todhip_pipeline_select_objects(todhip_pipeline* p, const uint32_t* ids, uint
 }
 
 int todhip_pipeline_submit(todhip_pipeline* p, const uint8_t* frames, const void* depth, uint32_t n_frames, uint64_t* ticket) {
-  return p ? p->submit(frames, depth, n_frames, ticket, true) : TODHIP_EINVAL;
+  return p ? p->submit(frames, nullptr, depth, n_frames, ticket, true) : TODHIP_EINVAL;
 }
 int todhip_pipeline_submit_device(todhip_pipeline* p, const void* d_frames, const void* d_depth, uint32_t n_frames, uint64_t* ticket) {
-  return p ? p->submit(d_frames, d_depth, n_frames, ticket, false) : TODHIP_EINVAL;
+  return p ? p->submit(d_frames, nullptr, d_depth, n_frames, ticket, false) : TODHIP_EINVAL;
+}
+int todhip_pipeline_submit_masked(todhip_pipeline* p, const uint8_t* frames, const uint8_t* masks, const void* depth, uint32_t n_frames,
+                                  uint64_t* ticket) {
+  return p ? p->submit(frames, masks, depth, n_frames, ticket, true) : TODHIP_EINVAL;
+}
+int todhip_pipeline_submit_masked_device(todhip_pipeline* p, const void* d_frames, const void* d_masks, const void* d_depth,
+                                         uint32_t n_frames, uint64_t* ticket) {
+  return p ? p->submit(d_frames, d_masks, d_depth, n_frames, ticket, false) : TODHIP_EINVAL;
+}
+int todhip_pipeline_set_depth_size(todhip_pipeline* p, uint32_t dH, uint32_t dW, int nearest) {
+  return p ? p->set_depth_size(dH, dW, nearest) : TODHIP_EINVAL;
 }
 
 int todhip_pipeline_wait(todhip_pipeline* p, uint64_t ticket, uint32_t timeout_ms, uint32_t* n_kp, float* kp_xy, todhip_pose* poses,

@@ -16,7 +16,8 @@
 //                            maximum-clique gate (maximum_clique.cpp:286-369) on an LDS-resident induced graph
 //   K9  growth_kernel        (verify_growth.h) Ransac's refinement loop (adjacency_ransac.cpp:255-308) incl. Kabsch/SVD (:304-347)
 //   K11 invalidate_kernel    (verify_prep.h) InvalidateQueryIndices / InvalidateIndices (:63-123)
-//   K_c cluster_frame_kernel (verify_prep.h) ClusterPerObject (:176-205)
+//   K_c cluster_frame_kernel (verify_prep.h) ClusterPerObject (:176-205); cluster_frame_rescaled_kernel: the same body with the depth
+//                            image at a size of its own, the rescaled pixel computed at each keypoint (depth_rescale.h)
 //       sprint_kernel        (verify_sprint.h) all of the above for a frame's small objects, by one workgroup
 // What kernels and host exchange through the slot's control block and mailbox is laid out in verify_kernels.h (SlotCtl, SlotMail).
 // The RANSAC bookkeeping (ransac.h:95-135: strictly-better test, adaptive k with pow/log) is replayed on the
@@ -37,6 +38,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "depth_rescale.h"
 #include "verify_kernels.h"
 
 using namespace tod;
@@ -240,7 +242,9 @@ struct ObjSpan {
   uint64_t adj_off = 0; uint32_t bits_off = 0, deg_off = 0, nvalid = 0, degsum = 0, triangle = 1;
   bool resume = false, counted = false;                    // sprint_kernel left it unfinished (its first-round statistics are stale) / in the counters
 };
-struct DepthInput { const void* d_depth; int is_u16; float fx, fy, cx, cy; };
+// geom (rescale == true): the depth image is geom.dH x geom.dW and the verifier sees rescale_depth's H x W result of it, computed at
+// the keypoint pixels only (todhip_verify*_depth_rescaled); otherwise the depth image has the image's size
+struct DepthInput { const void* d_depth; int is_u16; float fx, fy, cx, cy; bool rescale; RescaleGeom geom; };
 
 #include "verify_engine.h"
 
@@ -430,6 +434,7 @@ static int verify_batch_impl(todhip_ctx* ctx, uint32_t F, const void* d_kp_xy, u
   std::vector<Slot> slots(F);
   std::vector<Slot*> live;
   const size_t px = (size_t)H * Wimg;
+  const size_t depth_px = dep && dep->rescale ? (size_t)dep->geom.dH * dep->geom.dW : px;   // of one frame's depth image
   for (uint32_t f = 0; f < F; ++f) {
     Slot& s = slots[f];
     s.ws = ws_of(ctx, f);
@@ -441,7 +446,7 @@ static int verify_batch_impl(todhip_ctx* ctx, uint32_t F, const void* d_kp_xy, u
     if (dep) {
       s.use_depth = true;
       s.dep = *dep;
-      s.dep.d_depth = reinterpret_cast<const unsigned char*>(dep->d_depth) + (size_t)f * px * (dep->is_u16 ? 2 : 4);
+      s.dep.d_depth = reinterpret_cast<const unsigned char*>(dep->d_depth) + (size_t)f * depth_px * (dep->is_u16 ? 2 : 4);
     } else {
       s.d_cloud = reinterpret_cast<const float*>(d_cloud) + (size_t)f * px * 3;
     }
@@ -471,7 +476,7 @@ int todhip_verify_device_depth(todhip_ctx* ctx, const void* d_kp_xy, uint32_t nq
                                const todhip_verify_params* prm, todhip_rng* rng, todhip_pose* poses, uint32_t* n_poses,
                                uint32_t* inlier_kp, uint32_t* n_inlier_kp) {
   if (!d_depth || !K9) return TODHIP_EINVAL;
-  DepthInput dep = {d_depth, depth_is_u16, K9[0], K9[4], K9[2], K9[5]};
+  DepthInput dep = {d_depth, depth_is_u16, K9[0], K9[4], K9[2], K9[5], false, {}};
   return verify_batch_impl(ctx, 1, d_kp_xy, nq, nullptr, &dep, H, Wimg, d_counts, d_matches, d_mxyz, k, spans, n_objs, prm, rng,
                            poses, n_poses, nullptr, inlier_kp, n_inlier_kp);
 }
@@ -492,7 +497,41 @@ int todhip_verify_batch_device_depth(todhip_ctx* ctx, uint32_t n_frames, const v
                                      const todhip_verify_params* prm, todhip_rng* rng, todhip_pose* poses, uint32_t* n_poses,
                                      uint32_t* pose_ptr, uint32_t* inlier_kp, uint32_t* n_inlier_kp) {
   if (!d_depth || !K9 || !pose_ptr) return TODHIP_EINVAL;
-  DepthInput dep = {d_depth, depth_is_u16, K9[0], K9[4], K9[2], K9[5]};
+  DepthInput dep = {d_depth, depth_is_u16, K9[0], K9[4], K9[2], K9[5], false, {}};
+  return verify_batch_impl(ctx, n_frames, d_kp_xy, nq, nullptr, &dep, H, Wimg, d_counts, d_matches, d_mxyz, k, spans, n_objs, prm,
+                           rng, poses, n_poses, pose_ptr, inlier_kp, n_inlier_kp);
+}
+
+// The depth image at the sensor's own size: what todhip_rescale_depth_device would write into an H x W image is computed at the
+// keypoint pixels inside the cluster kernel (cluster_frame_rescaled_kernel); everything behind the lookup is the code of the calls above.
+static bool depth_rescaled_input(const void* d_depth, int depth_is_u16, uint32_t dH, uint32_t dW, int nearest, uint32_t H, uint32_t Wimg,
+                                 const float* K9, DepthInput* dep) {
+  if (!d_depth || !K9 || !dH || !dW || !H || !Wimg) return false;
+  *dep = {d_depth, depth_is_u16 ? 1 : 0, K9[0], K9[4], K9[2], K9[5], false, {}};
+  if (!rescale_geometry(dH, dW, H, Wimg, nearest, &dep->geom)) return false;
+  dep->rescale = dep->geom.mode != RescaleGeom::kEqual;    // equal sizes: the existing call
+  return true;
+}
+
+int todhip_verify_device_depth_rescaled(todhip_ctx* ctx, const void* d_kp_xy, uint32_t nq, const void* d_depth, int depth_is_u16,
+                                        uint32_t dH, uint32_t dW, int nearest, uint32_t H, uint32_t Wimg, const float* K9,
+                                        const void* d_counts, const void* d_matches, const void* d_mxyz, uint32_t k, const float* spans,
+                                        uint32_t n_objs, const todhip_verify_params* prm, todhip_rng* rng, todhip_pose* poses,
+                                        uint32_t* n_poses, uint32_t* inlier_kp, uint32_t* n_inlier_kp) {
+  DepthInput dep;
+  if (!depth_rescaled_input(d_depth, depth_is_u16, dH, dW, nearest, H, Wimg, K9, &dep)) return TODHIP_EINVAL;
+  return verify_batch_impl(ctx, 1, d_kp_xy, nq, nullptr, &dep, H, Wimg, d_counts, d_matches, d_mxyz, k, spans, n_objs, prm, rng,
+                           poses, n_poses, nullptr, inlier_kp, n_inlier_kp);
+}
+
+int todhip_verify_batch_device_depth_rescaled(todhip_ctx* ctx, uint32_t n_frames, const void* d_kp_xy, uint32_t nq, const void* d_depth,
+                                              int depth_is_u16, uint32_t dH, uint32_t dW, int nearest, uint32_t H, uint32_t Wimg,
+                                              const float* K9, const void* d_counts, const void* d_matches, const void* d_mxyz,
+                                              uint32_t k, const float* spans, uint32_t n_objs, const todhip_verify_params* prm,
+                                              todhip_rng* rng, todhip_pose* poses, uint32_t* n_poses, uint32_t* pose_ptr,
+                                              uint32_t* inlier_kp, uint32_t* n_inlier_kp) {
+  DepthInput dep;
+  if (!pose_ptr || !depth_rescaled_input(d_depth, depth_is_u16, dH, dW, nearest, H, Wimg, K9, &dep)) return TODHIP_EINVAL;
   return verify_batch_impl(ctx, n_frames, d_kp_xy, nq, nullptr, &dep, H, Wimg, d_counts, d_matches, d_mxyz, k, spans, n_objs, prm,
                            rng, poses, n_poses, pose_ptr, inlier_kp, n_inlier_kp);
 }

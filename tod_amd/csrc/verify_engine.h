@@ -73,7 +73,7 @@ struct Launches {
   std::vector<std::pair<StreamCache*, uint64_t>> draw_src, draw_small_src; std::vector<EvalArgs> eval_small, eval_big, eval_direct;
   std::vector<GrowthArgs> growth;
   std::vector<SprintArgs> sprint; std::vector<StreamCache*> sprint_src;
-  std::vector<ClusterArgs> cluster; std::vector<PrepSmallArgs> prep_small;
+  std::vector<ClusterArgs> cluster; std::vector<ClusterRescaledArgs> cluster_rescaled; std::vector<PrepSmallArgs> prep_small;
 };
 
 struct Engine {
@@ -201,7 +201,8 @@ struct Engine {
       cluster_scratch(ca, ws);
       ca.hist = ws->c_hist.as<uint32_t>(); ca.goff = ws->c_goff.as<uint32_t>();
       ca.train = ws->train.as<float>(); ca.qidx = ws->qidx.as<uint32_t>(); ca.m_ctl = &mail(s)->tail.cluster;
-      L.cluster.push_back(ca);
+      if (s.use_depth && s.dep.rescale) L.cluster_rescaled.push_back({ca, s.dep.geom});   // depth at its own size: looked up through the geometry
+      else L.cluster.push_back(ca);
       s.ph = PH_CLUSTER_WAIT;
       return;
     }
@@ -723,6 +724,7 @@ struct Engine {
     for (size_t i = 0; i < L.sprint.size(); ++i) { L.sprint[i].rnd = L.sprint_src[i]->dev.as<uint32_t>(); L.sprint[i].rnd_len = L.sprint_src[i]->dev_valid; }
     launch_list<kWideSlots>(st, sprint_kernel, L.sprint, kSprintThreads, kSprintLds, 0, [](const SprintArgs&) { return dim3(1); });
     launch_list(st, cluster_frame_kernel, L.cluster, 256, 0, 0, [](const ClusterArgs&) { return dim3(1); });
+    launch_list(st, cluster_frame_rescaled_kernel, L.cluster_rescaled, 256, 0, 0, [](const ClusterRescaledArgs&) { return dim3(1); });
     launch_list<kWideSlots>(st, invalidate_kernel, L.inval, 256, 0, 0, [](const InvArgs&) { return dim3(1); });
     launch_either<kManySlots>(st, TOD_BOTH_FORMS(small_prep_kernel, PrepSmallArgs, kManySlots), L.prep_small, L.prep_small.size() > kManySlots, stage,
                               1, [](const PrepSmallArgs&) { return dim3(1); }, 64u, 0u, false);
@@ -822,7 +824,7 @@ struct Engine {
     return n;
   }
   void describe(char* what, size_t cap) const {
-    snprintf(what, cap, "lookup %zu adj %zu prep %zu draw %zu+%zu chain %zu eval %zu+%zu growth %zu inval %zu sprint %zu", L.cluster.size(),
+    snprintf(what, cap, "lookup %zu adj %zu prep %zu draw %zu+%zu chain %zu eval %zu+%zu growth %zu inval %zu sprint %zu", L.cluster.size() + L.cluster_rescaled.size(),
              L.adj.size() + L.prep_small.size(), L.prep.size() + L.prep_small.size(), L.draw.size(), L.draw_small.size(), L.chain.size(), L.eval_small.size() + L.eval_direct.size(),
              L.eval_big.size(), L.growth.size(), L.inval.size(), L.sprint.size());
   }

@@ -2,6 +2,19 @@
 // triples, the clique search on an explicit graph as in the reference's test/test_maximum_clique.cpp).
 // Included last by verify.hip, after its anonymous namespace and C entry points.
 
+// the kernel of todhip_test_depth_lookup
+namespace {
+struct LookupArgs { const float* kp_xy; const void* depth; float* z; uint32_t* err; uint32_t n, H, W; int is_u16, rescale; RescaleGeom geom; };
+__global__ __launch_bounds__(256) void depth_lookup_kernel(LookupArgs a) {
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  if (q >= a.n) return;
+  const int row = (int)a.kp_xy[2 * q + 1], col = (int)a.kp_xy[2 * q];      // float -> int truncation, as cluster_frame
+  if (row < 0 || col < 0 || (uint32_t)row >= a.H || (uint32_t)col >= a.W) { atomicExch(a.err, 1u); return; }
+  a.z[q] = a.rescale ? rescaled_depth_at(a.depth, a.is_u16, a.geom, (uint32_t)col, (uint32_t)row)
+                     : depth_metres(a.depth, a.is_u16, (size_t)row * a.W + col);
+}
+}  // namespace
+
 extern "C" {
 
 int todhip_test_adjacency(todhip_ctx* ctx, const float* train, const float* query, const float* kpxy, uint32_t n,
@@ -102,6 +115,34 @@ int todhip_test_consensus(todhip_ctx* ctx, const float* train, const float* quer
     return TODHIP_ESCRATCH;
   }
   return TODHIP_OK;
+}
+
+// Test hook: the depth lookup of cluster_frame_kernel alone -- z of the keypoint's 3D point for n pixel positions, out of a dH x dW
+// depth image seen as rescale_depth's H x W result (equal sizes: the plain load). A position outside the H x W image is what the
+// cluster kernel refuses (ClusterCtl::error 1, TODHIP_ERANGE from the verify calls): its z_out is left as it was and the call returns
+// TODHIP_ERANGE after filling the others.
+
+int todhip_test_depth_lookup(todhip_ctx* ctx, const void* d_depth, int depth_is_u16, uint32_t dH, uint32_t dW, int nearest, uint32_t H,
+                             uint32_t W, const float* kp_xy, uint32_t n, float* z_out) {
+  if (!ctx || !d_depth || !kp_xy || !z_out || !dH || !dW || !H || !W || n == 0 || n > (1u << 24)) return TODHIP_EINVAL;
+  LookupArgs a = {};
+  if (!rescale_geometry(dH, dW, H, W, nearest, &a.geom)) return TODHIP_EINVAL;
+  TOD_HIP(hipSetDevice(ctx->device));
+  VerifyWs* ws = ws_of(ctx);
+  hipStream_t st = ctx->stream;
+  TOD_HIP(ws->kpxy.reserve((size_t)n * 8)); TOD_HIP(ws->c_qpt.reserve((size_t)n * 4)); TOD_HIP(ws->small.reserve(256 * sizeof(uint32_t)));
+  TOD_HIP(hipMemcpyAsync(ws->kpxy.p, kp_xy, (size_t)n * 8, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->c_qpt.p, z_out, (size_t)n * 4, hipMemcpyHostToDevice, st));     // refused positions keep the caller's value
+  TOD_HIP(hipMemsetAsync(ws->small.p, 0, sizeof(uint32_t), st));
+  a.kp_xy = ws->kpxy.as<float>(); a.depth = d_depth; a.z = ws->c_qpt.as<float>(); a.err = ws->small.as<uint32_t>();
+  a.n = n; a.H = H; a.W = W; a.is_u16 = depth_is_u16 ? 1 : 0; a.rescale = a.geom.mode != RescaleGeom::kEqual;
+  hipLaunchKernelGGL(depth_lookup_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, a);
+  TOD_HIP(hipGetLastError());
+  uint32_t err = 0;
+  TOD_HIP(hipMemcpyAsync(z_out, ws->c_qpt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipMemcpyAsync(&err, ws->small.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));
+  return err ? TODHIP_ERANGE : TODHIP_OK;
 }
 
 // Test hook: the clique search on an explicit graph (edges as pairs), FindClique(minimal_size).

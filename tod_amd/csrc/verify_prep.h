@@ -238,9 +238,13 @@ struct ClusterArgs {
   float *train, *query, *kpxy; uint32_t* qidx;                                    // grouped outputs
   uint32_t* m_hist; ClusterCtl* m_ctl;                                            // mailbox (pinned): histogram; error and n_all
 };
-__global__ __launch_bounds__(256) void cluster_frame_kernel(Slots<ClusterArgs> SL) {
-  TOD_LATENCY_PRIO();
-  const ClusterArgs& a = SL.a[blockIdx.x];
+// The kernel's body. kRescale: the depth image is geom->dH x geom->dW, not of the image size; the pixel rescale_depth would have
+// written at (col, row) is computed from its taps (depth_rescale.h) instead of being read from an H x W intermediate, NaN band
+// included. It is a kernel of its own (cluster_frame_rescaled_kernel), so that cluster_frame_kernel stays the code and the arguments
+// it was before there was a geometry.
+struct ClusterRescaledArgs { ClusterArgs c; RescaleGeom geom; };
+template <bool kRescale>
+__device__ __forceinline__ void cluster_frame(const ClusterArgs& a, const RescaleGeom* geom) {
   __shared__ uint32_t part[256], s_o[256], s_err, s_total;
   const uint32_t tid = threadIdx.x, nq = a.nq, k = a.k, n_objs = a.n_objs;
   if (tid == 0) s_err = 0u;
@@ -258,7 +262,9 @@ __global__ __launch_bounds__(256) void cluster_frame_kernel(Slots<ClusterArgs> S
       const float* p = a.cloud + 3 * ((size_t)row * a.Wimg + col);
       x = p[0]; y = p[1]; z = p[2];
     } else {
-      if (a.depth_is_u16) {
+      if (kRescale) {                                                      // the pixel of the rescaled image, computed here (depth_rescale.h)
+        z = rescaled_depth_at(a.depth, a.depth_is_u16, *geom, (uint32_t)col, (uint32_t)row);
+      } else if (a.depth_is_u16) {
         const uint16_t d = reinterpret_cast<const uint16_t*>(a.depth)[(size_t)row * a.Wimg + col];
         z = d == 0 ? __builtin_nanf("") : (float)d * 0.001f;
       } else {
@@ -352,4 +358,12 @@ __global__ __launch_bounds__(256) void cluster_frame_kernel(Slots<ClusterArgs> S
     __syncthreads();
   }
   if (tid == 0) { a.m_ctl->error = s_err; a.m_ctl->n_kept = n_all; }
+}
+__global__ __launch_bounds__(256) void cluster_frame_kernel(Slots<ClusterArgs> SL) {
+  TOD_LATENCY_PRIO();
+  cluster_frame<false>(SL.a[blockIdx.x], nullptr);
+}
+__global__ __launch_bounds__(256) void cluster_frame_rescaled_kernel(Slots<ClusterRescaledArgs> SL) {
+  TOD_LATENCY_PRIO();
+  cluster_frame<true>(SL.a[blockIdx.x].c, &SL.a[blockIdx.x].geom);
 }
