@@ -6,10 +6,12 @@
     todhip_orb -> todhip_match -> todhip_verify                           <- detector.py: features -> matcher -> guess generator
 
 Synthetic data (a textured plane rendered at a known pose), so that the recovered pose can be checked.
-Run on a machine with an MI355X:  python examples/train_and_detect.py [--learn-pattern] [--compact DIST,HAM]
+Run on a machine with an MI355X:  python examples/train_and_detect.py [--learn-pattern] [--compact DIST,HAM] [--batched]
 --learn-pattern: first learn an rBRIEF test pattern from the training view (todhip_pattern_learn_*), then train and detect with it.
 --compact DIST,HAM: train from two views a few degrees apart and merge the model's near-duplicate rows (todhip_model_compact: rows
 within DIST metres and HAM descriptor bits of a row kept before them go), e.g. --compact 0.003,24.
+--batched: train from the same two views, resident on the device, in one call (todhip_model_add_observations_device; needs torch to
+hold the device buffers). The model is the one that two todhip_model_add_observation calls give.
 """
 import argparse
 import os
@@ -42,6 +44,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--learn-pattern", action="store_true", help="learn the ORB test pattern from the training view first")
     ap.add_argument("--compact", metavar="DIST,HAM", help="train from two views and merge near-duplicate rows, e.g. 0.003,24")
+    ap.add_argument("--batched", action="store_true", help="train from two device-resident views in one call")
     args = ap.parse_args()
     ctx = capi.Context(0)
     texture = synth.make_image(321)
@@ -58,19 +61,32 @@ def main():
         print("pattern: learned from %d keypoints and %d candidate tests, accepted per round %s" %
               (n, res["n_candidates"], res["accepted_in_round"]))
 
-    # --- training: one observation (two with --compact); the object frame is the training camera frame (R = I, T = 0)
+    # --- training: one observation (two with --compact or --batched); the object frame is the training camera frame (R = I, T = 0)
     model = capi.Model(ctx, 4000)
-    model.add_observation(texture, mask, depth, K, np.eye(3, dtype=np.float32), np.zeros(3, np.float32), n_features=1500,
-                          n_levels=3, scale_factor=1.2, pattern=pattern)
-    if args.compact:
+    views = [(texture, np.eye(3, dtype=np.float32), np.zeros(3, np.float32))]
+    if args.compact or args.batched:
         # a second view, 5 degrees on and shifted: p_cam = R2 p_obj + t2, which is what cameraToWorld undoes
-        dist, ham = args.compact.split(",")
         th2, shift2 = np.deg2rad(5.0), (7.0, -5.0)
         c2, s2 = np.cos(th2), np.sin(th2)
         R2 = np.array([[c2, -s2, 0], [s2, c2, 0], [0, 0, 1]], np.float32)
         t2 = np.array([shift2[0] * Z / F, shift2[1] * Z / F, 0.0], np.float32) + (np.eye(3, dtype=np.float32) - R2) @ np.array([0, 0, Z], np.float32)
-        model.add_observation(render(texture, th2, shift2), mask, depth, K, R2, t2.astype(np.float32), n_features=1500, n_levels=3,
-                              scale_factor=1.2, pattern=pattern)
+        views.append((render(texture, th2, shift2), R2, t2.astype(np.float32)))
+    if args.batched:
+        import torch
+        n = len(views)
+        d_gray = torch.from_numpy(np.stack([v[0] for v in views])).cuda()
+        d_mask = torch.from_numpy(np.stack([mask] * n)).cuda()
+        d_depth = torch.from_numpy(np.stack([depth] * n)).cuda()
+        torch.cuda.synchronize()                                   # the uploads ran on torch's stream, the call runs on the context's
+        added = model.add_observations_device(d_gray.data_ptr(), d_mask.data_ptr(), d_depth.data_ptr(), n, H, W, K,
+                                              np.stack([v[1] for v in views]), np.stack([v[2] for v in views]), n_features=1500,
+                                              n_levels=3, scale_factor=1.2, pattern=pattern)
+        print("batched: %d views in one call, rows added per view %s" % (n, added.tolist()))
+    else:
+        for img, R, t in views:
+            model.add_observation(img, mask, depth, K, R, t, n_features=1500, n_levels=3, scale_factor=1.2, pattern=pattern)
+    if args.compact:
+        dist, ham = args.compact.split(",")
         before, after = model.compact(float(dist), int(ham))
         print("compact: %d rows before, %d after" % (before, after))
     desc, pts = model.finish(); model.close()

@@ -609,6 +609,33 @@ int  todhip_rescale_depth(todhip_ctx*, const void* depth_in, int depth_is_u16, u
                           uint32_t H, uint32_t W, int nearest);
 int  todhip_rescale_depth_device(todhip_ctx*, const void* d_depth_in, int depth_is_u16, uint32_t dH, uint32_t dW,
                                  void* d_depth_out, uint32_t H, uint32_t W, int nearest);
+/* A batch of device-resident views in one call: what a host that renders or captures an object's views on the device (tens to
+ * hundreds per object, Trainer.cpp:121-187 loops over them) does instead of n_views host-buffer calls. View v's gray image is at
+ * d_gray + v * frame_stride with row pitch stride >= W; its mask at d_mask + v * H * W (packed, != 0 = object); its depth image at
+ * d_depth + v * dH * dW elements (packed; float metres or uint16 millimetres), at the sensor's own size dH x dW, or of the image's
+ * size when dH == dW == 0. K9, R9 and T3 are HOST arrays of n_views x 9, n_views x 9 and n_views x 3 floats.
+ * Definition: the model afterwards is byte for byte the model after this sequence, for v = 0 .. n_views - 1 in order:
+ *   - if the depth size differs from the image's: todhip_rescale_depth(view v's depth, depth_is_u16, dH, dW -> H, W, nearest);
+ *   - then todhip_model_add_observation(view v's packed gray, mask v, that depth, ..., K9 + 9 v, R9 + 9 v, T3 + 3 v, n_features,
+ *     n_levels, scale_factor, pattern, &n_added[v]); the depth is float after a rescale, otherwise it is used as it is.
+ * The bytes are the descriptors, the points, the row count, and n_added[v] per view (n_added may be NULL). That includes the capacity
+ * cut (the view that reaches capacity_rows stores its first rows that still fit, every later view adds 0), views that yield no
+ * keypoint (they add 0), and rows the model already held -- from todhip_model_add_observation, _add_rows, _compact or an earlier batch.
+ * (Points: equal bytes where they are not NaN, NaN in the same places.) Neither an eroded mask nor a rescaled depth image is made:
+ * the arithmetic of both is evaluated at the keypoints (tod_amd/csrc/train_validate.h, depth_rescale.h).
+ * TODHIP_EINVAL, checked before any device work, the model untouched: whatever todhip_model_add_observation refuses (a null pointer,
+ * H or W below 8, n_features == 0, n_levels == 0 or above 16, scale_factor <= 1); d_mask == NULL; n_views == 0 or > 64 (the caller
+ * loops over larger sets); stride < W; n_views > 1 with frame_stride < H * stride; exactly one of dH, dW zero; a depth geometry
+ * todhip_rescale_depth refuses. Synchronizes the context's stream once, at its end, as todhip_model_add_observation does: the
+ * caller's buffers may be reused on return. All views of a batch share the image size and the ORB settings. */
+int  todhip_model_add_observations_device(todhip_ctx*, todhip_model*,
+                                          const void* d_gray, uint64_t frame_stride, uint32_t stride,
+                                          const void* d_mask,
+                                          const void* d_depth, int depth_is_u16, uint32_t dH, uint32_t dW, int nearest,
+                                          uint32_t n_views, uint32_t H, uint32_t W,
+                                          const float* K9, const float* R9, const float* T3,
+                                          uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
+                                          uint32_t* n_added);
 /* *n: capacity in rows in, rows out. desc: rows x 32, pts_xyz: rows x 3 (object/world frame). */
 int  todhip_model_finish(todhip_ctx*, todhip_model*, uint8_t* desc, float* pts_xyz, uint32_t* n);
 /* The model where it is: device pointers of its descriptors (n x 32 u8) and points (n x 3 f32), valid until todhip_model_free.

@@ -98,7 +98,15 @@ EXPORTS = [
     "todhip_db_desc_bytes",
     "todhip_orb_batch_device_masked", "todhip_verify_device_depth_rescaled", "todhip_verify_batch_device_depth_rescaled",
     "todhip_test_depth_lookup", "todhip_pipeline_set_depth_size", "todhip_pipeline_submit_masked", "todhip_pipeline_submit_masked_device",
+    "todhip_model_add_observations_device",
 ]
+
+MAX_TRAIN_BATCH_VIEWS = 64
+
+# todhip_model_add_observations_device's arguments in the header's order (tests/test_train_batch_cpu.py compares them with its text)
+_u32, _vp, _ci = C.c_uint32, C.c_void_p, C.c_int
+ADD_OBSERVATIONS_DEVICE_ARGTYPES = [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _ci, _u32, _u32, _ci, _u32, _u32, _u32, _vp, _vp, _vp,
+                                    _u32, _u32, C.c_float, _vp, _vp]
 
 MAX_PER_QUERY_LIMIT = 1024
 
@@ -182,6 +190,9 @@ def lib():
             L.todhip_pipeline_set_depth_size.argtypes, L.todhip_pipeline_set_depth_size.restype = [vp, u32, u32, ci], ci
             L.todhip_pipeline_submit_masked.argtypes, L.todhip_pipeline_submit_masked.restype = [vp, vp, vp, vp, u32, vp], ci
             L.todhip_pipeline_submit_masked_device.argtypes, L.todhip_pipeline_submit_masked_device.restype = [vp, vp, vp, vp, u32, vp], ci
+        if hasattr(L, "todhip_model_add_observations_device"):       # (as above)
+            L.todhip_model_add_observations_device.argtypes = ADD_OBSERVATIONS_DEVICE_ARGTYPES
+            L.todhip_model_add_observations_device.restype = C.c_int
         _lib = L
     return _lib
 
@@ -754,6 +765,33 @@ class Model:
                                                 C.c_float(scale_factor), None if pat is None else _np_ptr(pat), C.byref(n))
         _check(rc, "todhip_model_add_observation")
         return n.value
+
+    def add_observations_device(self, d_gray, d_mask, d_depth, n_views, H, W, K, R, T, *, stride=None, frame_stride=None,
+                                depth_is_u16=False, depth_size=None, nearest=False, n_features=500, n_levels=8, scale_factor=1.2,
+                                pattern=None):
+        """n_views device-resident views in one call (todhip_model_add_observations_device): the model afterwards is the model after
+        add_observation per view, in order. d_gray, d_mask, d_depth: device pointers -- view v's image at d_gray + v * frame_stride
+        (default H * stride) with row pitch stride (default W), masks n_views x H x W u8 packed, depth n_views x dH x dW packed,
+        float32 metres or (depth_is_u16) uint16 millimetres, depth_size = (dH, dW) or None for the image's size. K: one 3 x 3 matrix
+        for all views or n_views of them; R: n_views x 3 x 3; T: n_views x 3 (host arrays). -> uint32[n_views]: rows added per view."""
+        stride = W if stride is None else stride
+        frame_stride = H * stride if frame_stride is None else frame_stride
+        dH, dW = (0, 0) if depth_size is None else depth_size
+        K9 = np.ascontiguousarray(K, np.float32).reshape(-1)
+        if K9.size == 9:
+            K9 = np.ascontiguousarray(np.tile(K9, max(n_views, 1)))
+        R9 = np.ascontiguousarray(R, np.float32).reshape(-1)
+        T3 = np.ascontiguousarray(T, np.float32).reshape(-1)
+        if n_views and (K9.size != 9 * n_views or R9.size != 9 * n_views or T3.size != 3 * n_views):
+            raise ValueError("K, R, T do not hold n_views cameras")
+        n = np.zeros(max(n_views, 1), np.uint32)
+        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
+        rc = lib().todhip_model_add_observations_device(self._ctx._h, self._h, d_gray or None, frame_stride, stride, d_mask or None,
+                                                        d_depth or None, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0, n_views,
+                                                        H, W, _np_ptr(K9), _np_ptr(R9), _np_ptr(T3), n_features, n_levels, scale_factor,
+                                                        None if pat is None else _np_ptr(pat), _np_ptr(n))
+        _check(rc, "todhip_model_add_observations_device")
+        return n[:n_views].copy()
 
     def add_rows(self, desc, pts):
         """Already-trained rows (desc u8[n, 32], pts f32[n, 3]) behind the model's rows, cut at its capacity -> rows added."""

@@ -251,3 +251,6 @@ int tod_l2_db_prepare(todhip_ctx* ctx);      // l2.hip: bf16 image + norms of a 
 int tod_orb_device(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask, uint32_t H, uint32_t W, uint32_t stride,
                    uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern, float* d_kp_xy,
                    float* d_kp_aux, uint8_t* d_desc, uint32_t cap, uint32_t* n_out);
+int tod_orb_batch_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uint8_t* d_mask, uint32_t F, uint32_t H,
+                         uint32_t W, uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
+                         float* d_kp_xy, float* d_kp_aux, uint8_t* d_desc, uint32_t cap, uint32_t* n_out);

@@ -194,6 +194,15 @@ int tod_orb_device(todhip_ctx* ctx, const uint8_t* d_gray, const uint8_t* d_mask
                     {d_kp_xy, d_kp_aux, d_desc, cap, n_out});
 }
 
+// used by train.hip: F masked views in one call (frame f at d_gray + f * gray_fs, its mask at d_mask + f * H * W, its keypoints at
+// row f * cap of the three arrays, their number in n_out[f])
+int tod_orb_batch_device(todhip_ctx* ctx, const uint8_t* d_gray, size_t gray_fs, const uint8_t* d_mask, uint32_t F, uint32_t H,
+                         uint32_t W, uint32_t stride, uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
+                         float* d_kp_xy, float* d_kp_aux, uint8_t* d_desc, uint32_t cap, uint32_t* n_out) {
+  return orb_device(ctx, {d_gray, gray_fs, d_mask, F, H, W, stride}, {n_features, n_levels, scale_factor, pattern},
+                    {d_kp_xy, d_kp_aux, d_desc, cap, n_out});
+}
+
 // orb_stages.h
 int tod_orb_stage_host_view(todhip_ctx* ctx, const uint8_t* gray, const uint8_t* mask, uint32_t H, uint32_t W, uint32_t stride,
                             const uint8_t** d_gray, const uint8_t** d_mask) {

@@ -10,6 +10,8 @@
 
 #include "depth_rescale.h"
 #include "model.h"
+#include "orb_plan.h"
+#include "train_validate.h"
 
 namespace {
 
@@ -32,9 +34,7 @@ __global__ __launch_bounds__(256) void erode_cols_kernel(const uint8_t* __restri
   dst[i] = all ? 255 : 0;
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-struct Cam { float fx, fy, cx, cy, R[9], T[3]; };
+using Cam = tod::TrainCam;
 
 // rescale_depth (Trainer.cpp:62-81): the arithmetic is depth_rescale.h's, here once per pixel of the H x W result
 __global__ __launch_bounds__(256) void rescale_depth_kernel(const void* __restrict__ src, int is_u16, tod::RescaleGeom geom,
@@ -44,9 +44,8 @@ __global__ __launch_bounds__(256) void rescale_depth_kernel(const void* __restri
   dst[i] = tod::rescaled_depth_at(src, is_u16, geom, i % W, i / W);
 }
 
-// validateKeyPoints (training.cpp:57-145) + depthTo3dSparse + cameraToWorld (:175-195) for one keypoint per thread.
-// roundWithinBounds clamps to [0, width] in the reference (:53-55), which can index one column past the image;
-// here the clamp is to width-1 / height-1.
+// validateKeyPoints (training.cpp:57-145) + depthTo3dSparse + cameraToWorld (:175-195) for one keypoint per thread: the arithmetic
+// is train_validate.h's, the eroded pixels come from the image the two erosion kernels wrote.
 __global__ __launch_bounds__(256) void validate_kernel(const float* __restrict__ kp_xy, const uint32_t* __restrict__ n_ptr,
                                                        const uint8_t* __restrict__ er, const void* __restrict__ depth,
                                                        int depth_is_u16, uint32_t H, uint32_t W, Cam cam, uint32_t* flags,
@@ -54,39 +53,17 @@ __global__ __launch_bounds__(256) void validate_kernel(const float* __restrict__
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= *n_ptr) return;
   const float px = kp_xy[2 * i], py = kp_xy[2 * i + 1];
-  int x = clampi((int)rintf(px), 0, (int)W - 1), y = clampi((int)rintf(py), 0, (int)H - 1);
+  int x, y;
+  tod::rounded_pixel(px, py, (int)H, (int)W, &x, &y);
   bool good = er[(size_t)y * W + x] != 0;
-  if (!good) {
-    float best = FLT_MAX;
-    int bx = x, by = y;
-    for (int ii = clampi(x - 2, 0, (int)W - 1); ii <= clampi(x + 2, 0, (int)W - 1); ++ii)
-      for (int jj = clampi(y - 2, 0, (int)H - 1); jj <= clampi(y + 2, 0, (int)H - 1); ++jj)
-        if (er[(size_t)jj * W + ii]) {
-          const float d = ((float)ii - px) * ((float)ii - px) + ((float)jj - py) * ((float)jj - py);
-          if (d < best) { best = d; bx = ii; by = jj; good = true; }
-        }
-    x = bx; y = by;
-  }
+  if (!good) good = tod::rescue_pixel([&](int ii, int jj) { return er[(size_t)jj * W + ii] != 0; }, px, py, (int)H, (int)W, &x, &y);
   float z = 0.f;
   if (good) {
-    if (depth_is_u16) {                                   // cv::rescaleDepth: millimetres -> metres, 0 -> NaN
-      const uint16_t d = reinterpret_cast<const uint16_t*>(depth)[(size_t)y * W + x];
-      z = d == 0 ? __builtin_nanf("") : (float)d * 0.001f;
-    } else {
-      z = reinterpret_cast<const float*>(depth)[(size_t)y * W + x];
-    }
-    if (!(z == z) || z == FLT_MAX || z == -FLT_MAX || z == FLT_MIN) good = false;      // cv::isValidDepth(float)
+    z = tod::depth_metres(depth, depth_is_u16, (size_t)y * W + x);   // cv::rescaleDepth: millimetres -> metres, 0 -> NaN
+    if (!tod::valid_depth(z)) good = false;
   }
   flags[i] = good ? 1u : 0u;
-  if (good) {
-    const float p[3] = {((float)x - cam.cx) * z / cam.fx, ((float)y - cam.cy) * z / cam.fy, z};
-    const float q[3] = {p[0] - cam.T[0], p[1] - cam.T[1], p[2] - cam.T[2]};
-    for (int c = 0; c < 3; ++c) {                         // (p - T) * R, double accumulation like cv::gemm on CV_32F
-      double s = 0;
-      for (int k = 0; k < 3; ++k) s += (double)q[k] * (double)cam.R[3 * k + c];
-      pts_tmp[3 * i + c] = (float)s;
-    }
-  }
+  if (good) tod::back_project(cam, x, y, z, pts_tmp + 3 * (size_t)i);
 }
 
 // stable compaction of the accepted keypoints behind the rows the model already has (mergePoints, :147-173)
@@ -121,6 +98,103 @@ __global__ __launch_bounds__(1024) void append_kernel(const uint32_t* __restrict
   }
   __syncthreads();
   if (tid == 0) { counters[1] = min(total, cap > base ? cap - base : 0u); counters[0] = min(base + total, cap); }
+}
+
+// ---- a batch of device-resident views (todhip_model_add_observations_device): no eroded image, no rescaled depth image ----------
+// View v's keypoints, flags and points are rows v * n_features .. of their arrays. The keypoints per view are on the host once the
+// ORB call has returned, so they travel as a kernel argument; what the kernels hand to each other is a BatchWords.
+struct BatchCounts { uint32_t n[kTrainBatchMaxViews]; };
+struct BatchWords { uint32_t total[kTrainBatchMaxViews], base[kTrainBatchMaxViews], added[kTrainBatchMaxViews]; };
+
+// validate_kernel over (view, keypoint), a keypoint per thread. The eroded pixels a keypoint asks about come from the 13 x 13
+// neighbourhood of the view's mask (169 byte loads; 13 rows of 13 bytes, so at most 26 lines), the depth at the chosen pixel from
+// the sensor-sized image through the rescale's own arithmetic. A thread per keypoint, not a wave per keypoint with a cooperative
+// read: the loads of one keypoint do not depend on each other or on the other lanes', and nothing has to be reduced across lanes
+// at the end (48 us for 32 views x 1300 keypoints; the cooperative form was not built).
+__global__ __launch_bounds__(256) void validate_batch_kernel(const float* __restrict__ kp_xy, BatchCounts cnt, uint32_t n_features,
+                                                             const uint8_t* __restrict__ mask, const uint8_t* __restrict__ depth,
+                                                             int depth_is_u16, tod::RescaleGeom geom, uint32_t H, uint32_t W,
+                                                             const Cam* __restrict__ cams, uint32_t* flags, float* pts_tmp) {
+  const uint32_t v = blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= cnt.n[v]) return;
+  const size_t row = (size_t)v * n_features + i;
+  const uint8_t* view_mask = mask + (size_t)v * H * W;
+  const void* view_depth = depth + (size_t)v * geom.dH * geom.dW * (depth_is_u16 ? 2u : 4u);
+  const float px = kp_xy[2 * row], py = kp_xy[2 * row + 1];
+  int x, y;
+  tod::rounded_pixel(px, py, (int)H, (int)W, &x, &y);
+  const int x0 = x, y0 = y;
+  const uint32_t win = tod::eroded_window(view_mask, (int)H, (int)W, x0, y0);
+  bool good = tod::eroded_window_at(win, x0, y0, x0, y0);
+  if (!good) good = tod::rescue_pixel([&](int ii, int jj) { return tod::eroded_window_at(win, x0, y0, ii, jj); }, px, py, (int)H, (int)W, &x, &y);
+  float z = 0.f;
+  if (good) {
+    z = tod::train_depth_at(view_depth, depth_is_u16, geom, x, y);
+    if (!tod::valid_depth(z)) good = false;
+  }
+  flags[row] = good ? 1u : 0u;
+  if (good) tod::back_project(cams[v], x, y, z, pts_tmp + 3 * row);
+}
+
+// mergePoints (training.cpp:147-173) across the views, a stable compaction in (view, keypoint) order in three ordinary launches:
+// a block per view counts its accepted keypoints, one wave scans the view totals behind the model's rows and applies the capacity
+// cut, a block per view writes its rows.
+__global__ __launch_bounds__(256) void count_batch_kernel(const uint32_t* __restrict__ flags, BatchCounts cnt, uint32_t n_features,
+                                                          BatchWords* bw) {
+  __shared__ uint32_t part[4];
+  const uint32_t v = blockIdx.x, n = cnt.n[v], tid = threadIdx.x;
+  uint32_t s = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += 256u) {               // (n is the block's: every lane is there for every ballot)
+    const uint32_t i = i0 + tid;
+    s += (uint32_t)__popcll(__ballot(i < n && flags[(size_t)v * n_features + i] != 0u));
+  }
+  if ((tid & 63u) == 0u) part[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0u) bw->total[v] = part[0] + part[1] + part[2] + part[3];
+}
+
+// one wave, lane v = view v: the rows the model holds before view v exactly as the sequence of single calls would find them
+// (counters[0] never passes the capacity), what the view adds, and the counters as append_kernel leaves them
+__global__ __launch_bounds__(64) void scan_batch_kernel(BatchWords* bw, uint32_t n_views, uint32_t cap, uint32_t* counters) {
+  const uint32_t v = threadIdx.x;
+  const unsigned long long rows = counters[0], t = v < n_views ? bw->total[v] : 0u;
+  unsigned long long incl = t;
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const unsigned long long up = __shfl_up(incl, d);
+    if (v >= d) incl += up;
+  }
+  const unsigned long long before = min(rows + incl - t, (unsigned long long)cap), after = min(rows + incl, (unsigned long long)cap);
+  if (v < n_views) { bw->base[v] = (uint32_t)before; bw->added[v] = (uint32_t)(after - before); }
+  if (v == 63u) { counters[1] = (uint32_t)(after - min(rows, (unsigned long long)cap)); counters[0] = (uint32_t)after; }
+}
+
+__global__ __launch_bounds__(256) void append_batch_kernel(const uint32_t* __restrict__ flags, BatchCounts cnt, uint32_t n_features,
+                                                           const uint8_t* __restrict__ kp_desc, const float* __restrict__ pts_tmp,
+                                                           const BatchWords* __restrict__ bw, uint8_t* desc, float* pts) {
+  __shared__ uint32_t wave_n[4];
+  const uint32_t v = blockIdx.x, n = cnt.n[v], tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+  const uint32_t base = bw->base[v], added = bw->added[v];  // rows base .. base + added - 1 are this view's: all below the capacity
+  uint32_t done = 0;                                        // accepted keypoints of the view before this round's 256
+  for (uint32_t i0 = 0; i0 < n && done < added; i0 += 256u) {
+    const uint32_t i = i0 + tid;
+    const size_t src = (size_t)v * n_features + i;
+    const bool f = i < n && flags[src] != 0u;
+    const unsigned long long b = __ballot(f);
+    if (lane == 0u) wave_n[w] = (uint32_t)__popcll(b);
+    __syncthreads();
+    uint32_t r = done, all = 0;
+    for (uint32_t k = 0; k < 4u; ++k) { const uint32_t c = wave_n[k]; r += k < w ? c : 0u; all += c; }
+    r += (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    if (f && r < added) {
+      const size_t o = (size_t)base + r;
+      const uint4* s16 = reinterpret_cast<const uint4*>(kp_desc) + 2 * src;   // a descriptor: two 16-byte copies
+      uint4* d16 = reinterpret_cast<uint4*>(desc) + 2 * o;
+      d16[0] = s16[0]; d16[1] = s16[1];
+      pts[3 * o] = pts_tmp[3 * src]; pts[3 * o + 1] = pts_tmp[3 * src + 1]; pts[3 * o + 2] = pts_tmp[3 * src + 2];
+    }
+    done += all;
+    __syncthreads();                                        // wave_n is written again in the next round
+  }
 }
 
 }  // namespace
@@ -188,6 +262,61 @@ int todhip_model_add_observation(todhip_ctx* ctx, todhip_model* m, const uint8_t
   TOD_HIP(hipMemcpyAsync(h, d_small, sizeof(h), hipMemcpyDeviceToHost, st));
   TOD_HIP(hipStreamSynchronize(st));                     // also keeps gray/mask/depth/n_kp alive until the copies are done
   if (n_added) *n_added = h[1];
+  return TODHIP_OK;
+}
+
+// Trainer::process (Trainer.cpp:121-187) for n_views device-resident views in one call; the definition is include/todhip.h's: the
+// model after the sequence of todhip_rescale_depth + todhip_model_add_observation per view, byte for byte. One batched masked ORB
+// call, one copy of the cameras, four launches, one copy back, one synchronization.
+int todhip_model_add_observations_device(todhip_ctx* ctx, todhip_model* m, const void* d_gray, uint64_t frame_stride, uint32_t stride,
+                                         const void* d_mask, const void* d_depth, int depth_is_u16, uint32_t dH, uint32_t dW,
+                                         int nearest, uint32_t n_views, uint32_t H, uint32_t W, const float* K9, const float* R9,
+                                         const float* T3, uint32_t n_features, uint32_t n_levels, float scale_factor,
+                                         const int8_t* pattern, uint32_t* n_added) {
+  if (!ctx || !m || !d_gray || !d_mask || !d_depth || !K9 || !R9 || !T3 || H < 8 || W < 8 || n_features == 0) return TODHIP_EINVAL;
+  if (n_views == 0 || n_views > kTrainBatchMaxViews || stride < W) return TODHIP_EINVAL;
+  if (n_views > 1 && frame_stride < (uint64_t)H * stride) return TODHIP_EINVAL;
+  if ((dH == 0) != (dW == 0) || (uint64_t)H * W > 0xFFFFFFFFull) return TODHIP_EINVAL;
+  if (dH == 0) { dH = H; dW = W; }
+  tod::RescaleGeom geom;
+  if (!tod::rescale_geometry(dH, dW, H, W, nearest, &geom)) return TODHIP_EINVAL;
+  if (const int bad = tod_orb::check_args(n_views, H, W, n_features, n_levels, scale_factor, n_features)) return bad;
+  TOD_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t rows = (size_t)n_views * n_features;
+  TOD_HIP(m->kp_xy.reserve(rows * 8)); TOD_HIP(m->kp_aux.reserve(rows * 16)); TOD_HIP(m->kp_desc.reserve(rows * 32));
+  TOD_HIP(m->flags.reserve(rows * 4)); TOD_HIP(m->offs.reserve(rows * 12));
+  TOD_HIP(m->cams.reserve(kTrainBatchMaxViews * sizeof(Cam))); TOD_HIP(m->batch.reserve(sizeof(BatchWords)));
+  BatchCounts cnt = {};
+  const int rc = tod_orb_batch_device(ctx, static_cast<const uint8_t*>(d_gray), (size_t)frame_stride, static_cast<const uint8_t*>(d_mask),
+                                      n_views, H, W, stride, n_features, n_levels, scale_factor, pattern, m->kp_xy.as<float>(),
+                                      m->kp_aux.as<float>(), m->kp_desc.as<uint8_t>(), n_features, cnt.n);
+  if (rc != TODHIP_OK) return rc;
+  if (n_added) std::memset(n_added, 0, n_views * sizeof(uint32_t));
+  uint32_t most = 0;
+  for (uint32_t v = 0; v < n_views; ++v) most = std::max(most, cnt.n[v]);
+  if (most == 0) return TODHIP_OK;
+  Cam cams[kTrainBatchMaxViews];
+  for (uint32_t v = 0; v < n_views; ++v) {
+    const float* K = K9 + 9 * (size_t)v;
+    cams[v].fx = K[0]; cams[v].fy = K[4]; cams[v].cx = K[2]; cams[v].cy = K[5];
+    std::memcpy(cams[v].R, R9 + 9 * (size_t)v, sizeof(cams[v].R)); std::memcpy(cams[v].T, T3 + 3 * (size_t)v, sizeof(cams[v].T));
+  }
+  TOD_HIP(hipMemcpyAsync(m->cams.p, cams, n_views * sizeof(Cam), hipMemcpyHostToDevice, st));
+  BatchWords* bw = m->batch.as<BatchWords>();
+  uint32_t* d_small = m->small.as<uint32_t>();
+  hipLaunchKernelGGL(validate_batch_kernel, dim3((most + 255u) / 256u, n_views), dim3(256), 0, st, m->kp_xy.as<float>(), cnt, n_features,
+                     static_cast<const uint8_t*>(d_mask), static_cast<const uint8_t*>(d_depth), depth_is_u16, geom, H, W,
+                     m->cams.as<Cam>(), m->flags.as<uint32_t>(), m->offs.as<float>());
+  hipLaunchKernelGGL(count_batch_kernel, dim3(n_views), dim3(256), 0, st, m->flags.as<uint32_t>(), cnt, n_features, bw);
+  hipLaunchKernelGGL(scan_batch_kernel, dim3(1), dim3(64), 0, st, bw, n_views, m->cap, d_small);
+  hipLaunchKernelGGL(append_batch_kernel, dim3(n_views), dim3(256), 0, st, m->flags.as<uint32_t>(), cnt, n_features,
+                     m->kp_desc.as<uint8_t>(), m->offs.as<float>(), bw, m->desc.as<uint8_t>(), m->pts.as<float>());
+  TOD_HIP(hipGetLastError());
+  uint32_t h_added[kTrainBatchMaxViews];
+  TOD_HIP(hipMemcpyAsync(h_added, bw->added, n_views * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));                     // also keeps cams and h_added alive until the copies are done
+  if (n_added) std::memcpy(n_added, h_added, n_views * sizeof(uint32_t));
   return TODHIP_OK;
 }
 

@@ -56,11 +56,13 @@ def render_views(textures_gpu, obj_ids, thetas_deg, shifts_px, noise_seed, noise
     return torch.clamp(torch.round(img), 0, 255).to(torch.uint8), inside
 
 
-def train_db(ctx, textures, n_features=1300, n_levels=3, views=TRAIN_VIEWS, rows_per_object=None, pattern=None, compact=None):
+def train_db(ctx, textures, n_features=1300, n_levels=3, views=TRAIN_VIEWS, rows_per_object=None, pattern=None, compact=None,
+             batched=False):
     """One model per texture from `views` (todhip_model_*). Returns (desc u8[N, 32], pts f32[N, 3], obj_off u32[n + 1]).
     rows_per_object: keep at most that many rows of each model (the first ones: whole early views). pattern: the ORB test pattern
     (None = built-in; capi.PatternLearner). compact: None, or (merge_dist, max_hamming) -- every model's near-duplicate rows are
-    merged (capi.Model.compact) before it is read back."""
+    merged (capi.Model.compact) before it is read back. batched: the rendered views stay on the device and reach the model in one
+    call per object (capi.Model.add_observations_device, at most capi.MAX_TRAIN_BATCH_VIEWS views per call): the same arrays."""
     import torch
     from . import capi
     n_obj = len(textures)
@@ -69,16 +71,27 @@ def train_db(ctx, textures, n_features=1300, n_levels=3, views=TRAIN_VIEWS, rows
     descs, ptss, off = [], [], [0]
     border = torch.zeros((H, W), dtype=torch.bool, device="cuda")
     border[40:H - 40, 40:W - 40] = True
+    if batched:                                                      # the same constant depth, resident, for every object's views
+        depth_gpu = torch.full((min(len(views), capi.MAX_TRAIN_BATCH_VIEWS), H, W), Z, dtype=torch.float32, device="cuda")
     for o in range(n_obj):
         imgs, inside = render_views(tex, [o] * len(views), [v[0] for v in views], [v[1] for v in views], 700000 + o)
         # the object region of a view: where the plane is seen, minus a border (validateKeyPoints erodes the mask further)
         masks = (inside & border).to(torch.uint8) * 255
-        imgs, masks = imgs.cpu().numpy(), masks.cpu().numpy()
         model = capi.Model(ctx, len(views) * n_features + 16)
-        for vi, (theta, shift) in enumerate(views):
-            R, t = view_pose(theta, shift)
-            model.add_observation(imgs[vi], masks[vi], depth, K, R, t, n_features=n_features, n_levels=n_levels, scale_factor=1.2,
-                                  pattern=pattern)
+        poses = [view_pose(theta, shift) for theta, shift in views]
+        if batched:
+            imgs, masks = imgs.contiguous(), masks.contiguous()
+            torch.cuda.synchronize()                                 # the views were rendered on torch's stream, not the context's
+            for lo in range(0, len(views), capi.MAX_TRAIN_BATCH_VIEWS):
+                n = min(capi.MAX_TRAIN_BATCH_VIEWS, len(views) - lo)
+                model.add_observations_device(imgs[lo:].data_ptr(), masks[lo:].data_ptr(), depth_gpu.data_ptr(), n, H, W, K,
+                                              np.stack([p[0] for p in poses[lo:lo + n]]), np.stack([p[1] for p in poses[lo:lo + n]]),
+                                              n_features=n_features, n_levels=n_levels, scale_factor=1.2, pattern=pattern)
+        else:
+            imgs, masks = imgs.cpu().numpy(), masks.cpu().numpy()
+            for vi, (R, t) in enumerate(poses):
+                model.add_observation(imgs[vi], masks[vi], depth, K, R, t, n_features=n_features, n_levels=n_levels, scale_factor=1.2,
+                                      pattern=pattern)
         if compact is not None:
             model.compact(compact[0], compact[1])
         d, p = model.finish()
