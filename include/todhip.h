@@ -141,6 +141,7 @@ int todhip_db_desc_bytes(const todhip_ctx*, uint32_t* desc_bytes);
  * 4, todhip_set_kernel_timing brackets the DB pass as on a 32-byte DB.
  * What a 64-byte DB refuses or ignores:
  *   todhip_match_radius[_device], todhip_match_l2[_device]   TODHIP_EINVAL.
+ *   todhip_match_l2_radius[_device]                          TODHIP_EINVAL.
  *   todhip_match_radius_shard_device,
  *   todhip_merge_radius_shards_device[_on]                   TODHIP_EINVAL.
  *   the match calls while todhip_set_lsh is enabled          TODHIP_EINVAL before any device work (no index is built at this width).
@@ -241,6 +242,40 @@ int todhip_match_l2(todhip_ctx*, const float* q_desc, uint32_t nq, uint32_t k, f
                     todhip_dmatch* matches, float* matches_xyz);
 int todhip_match_l2_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t k, float radius, void* d_counts,
                            void* d_matches, void* d_matches_xyz);
+
+/* The true L2 radius search over a float DB (desc_bytes == 512): every row within `radius` of a query, not the k <= 8 nearest cut at
+ * the radius -- cv::DescriptorMatcher::radiusMatch for float descriptors, what todhip_match_radius is for 32-byte binary ones, and
+ * for the same reason: a surface point is one row per training view, and k <= 8 hands the verifier a handful of those rows without
+ * saying that the list was cut.
+ * Definition (exact, deterministic):
+ *   d2(q, r)     = sum over i = 0..127 in index order of (q[i] - r[i])^2 in IEEE binary32 without fused multiply-add, and
+ *                  distance = sqrtf(d2): those of todhip_match_l2.
+ *   R(q)         = the DB rows whose distance is NOT > radius (inclusive, the cut of todhip_match_l2). Descriptors are finite, as
+ *                  todhip_match_l2 assumes; a d2 that overflows to +Inf is outside every radius.
+ *   in_radius[q] = |R(q)|, exact, never truncated.
+ *   matches of q = R(q) in the order (d2 ascending, global row ascending), cut after the first max_per_query <= 1024;
+ *                  counts[q] = min(|R(q)|, max_per_query). queryIdx, trainIdx, imgIdx, distance and the gathered model point of a row
+ *                  are exactly what todhip_match_l2 writes for it, so with max_per_query = k <= 8 the two calls agree bit for bit.
+ *   The ratio test and the LSH mode do not apply. Batch form as todhip_match_l2: the nq queries may be those of F frames and share
+ *   ONE pass over the DB.
+ * Host form: CSR with todhip_match_radius's capacity rule. *n_matches: capacity of matches / matches_xyz (in matches) in, row_ptr[nq]
+ * out; when it is too small: TODHIP_ECAPACITY with the needed count in *n_matches, row_ptr and in_radius filled, matches untouched.
+ * in_radius may be NULL.
+ * Device form: fixed stride max_per_query -- d_counts[nq] u32, d_matches[nq * max_per_query], d_matches_xyz[nq * max_per_query * 3],
+ * d_in_radius[nq] u32 (may be NULL); the slots behind counts[q] are not written.
+ * TODHIP_EINVAL: a null context, query or output pointer, nq == 0, max_per_query == 0 or > 1024, a radius that is not > 0 or not
+ * finite, a DB that is not float (or is sharded). TODHIP_ENODB without a DB. todhip_get_counters: last_nq, last_k = max_per_query,
+ * last_matches (host form); todhip_set_kernel_timing brackets the pass over the DB.
+ * How: one pass of the k-NN call's bf16 GEMM with a threshold derived from the radius and the GEMM's proven error bound, the exact
+ * distance of every candidate, a sort. A query whose candidate lists overflow (more than about 2000 candidates) is answered by a
+ * second, ordered pass over the f32 rows for that query (same result). Workspace: the k-NN call's, with
+ * nq * max_per_query * 8 bytes of keys. */
+int todhip_match_l2_radius(todhip_ctx*, const float* q_desc, uint32_t nq, float radius, uint32_t max_per_query,
+                           uint32_t* row_ptr /*[nq+1]*/, todhip_dmatch* matches, float* matches_xyz,
+                           uint32_t* n_matches /* capacity in, count out */, uint32_t* in_radius /*[nq], may be NULL*/);
+int todhip_match_l2_radius_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, float radius, uint32_t max_per_query,
+                                  void* d_counts /*[nq] u32*/, void* d_matches /*[nq*max_per_query]*/,
+                                  void* d_matches_xyz /*[nq*max_per_query*3]*/, void* d_in_radius /*[nq] u32, may be NULL*/);
 
 /* Sharded form, step 1: this shard's top-k per query as keys (distance << 32 | global_row), ascending,
  * UINT64_MAX padded; d_keys[nq*k]. The ranks exchange these with one RCCL all-gather. `radius` is the radius of

@@ -99,6 +99,7 @@ EXPORTS = [
     "todhip_orb_batch_device_masked", "todhip_verify_device_depth_rescaled", "todhip_verify_batch_device_depth_rescaled",
     "todhip_test_depth_lookup", "todhip_pipeline_set_depth_size", "todhip_pipeline_submit_masked", "todhip_pipeline_submit_masked_device",
     "todhip_model_add_observations_device",
+    "todhip_match_l2_radius", "todhip_match_l2_radius_device",
 ]
 
 MAX_TRAIN_BATCH_VIEWS = 64
@@ -193,6 +194,11 @@ def lib():
         if hasattr(L, "todhip_model_add_observations_device"):       # (as above)
             L.todhip_model_add_observations_device.argtypes = ADD_OBSERVATIONS_DEVICE_ARGTYPES
             L.todhip_model_add_observations_device.restype = C.c_int
+        if hasattr(L, "todhip_match_l2_radius"):                      # (as above)
+            L.todhip_match_l2_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 5
+            L.todhip_match_l2_radius.restype = C.c_int
+            L.todhip_match_l2_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 4
+            L.todhip_match_l2_radius_device.restype = C.c_int
         _lib = L
     return _lib
 
@@ -451,6 +457,30 @@ class Context:
         rc = lib().todhip_match_l2_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_float(radius),
                                           C.c_void_p(d_counts), C.c_void_p(d_matches), C.c_void_p(d_xyz))
         _check(rc, "todhip_match_l2_device")
+
+    def match_l2_radius(self, q_desc, radius, max_per_query):
+        """The true L2 radius search over a float DB, host-buffer form (todhip_match_l2_radius): every row whose distance is not
+        > radius, the nearest max_per_query of them per query. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3],
+        in_radius u32[nq]). The output buffers start at 16 matches per query and grow to the count the library asks for."""
+        q = np.ascontiguousarray(q_desc, np.float32)
+        nq = q.shape[0]
+        row_ptr, in_radius = np.zeros(nq + 1, np.uint32), np.zeros(nq, np.uint32)
+        cap = max(nq * min(max_per_query, 16), 1)
+        while True:
+            m, xyz = np.empty(cap, DMATCH_DTYPE), np.empty((cap, 3), np.float32)
+            n = C.c_uint32(cap)
+            rc = lib().todhip_match_l2_radius(self._h, _np_ptr(q), nq, radius, max_per_query, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz),
+                                              C.addressof(n), _np_ptr(in_radius))
+            if rc != ECAPACITY or n.value <= cap:
+                break
+            cap = n.value                                                 # the needed count: the same call fits now
+        _check(rc, "todhip_match_l2_radius")
+        return row_ptr, m[:n.value].copy(), xyz[:n.value].copy(), in_radius
+
+    def match_l2_radius_device(self, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
+        """Device-pointer form (ints from tensor.data_ptr()), fixed stride max_per_query; d_in_radius may be None."""
+        _check(lib().todhip_match_l2_radius_device(self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius),
+               "todhip_match_l2_radius_device")
 
     def match_device(self, d_q, nq, k, radius, d_counts, d_matches, d_xyz):
         """Device-pointer form (ints from tensor.data_ptr()). d_q: nq rows of the DB's width, 32 or 64 bytes (desc_bytes()) -- the

@@ -499,6 +499,8 @@ __global__ __launch_bounds__(256) void l2_finalize_kernel(const uint64_t* __rest
 
 }  // namespace
 
+#include "l2_radius.h"   // the radius search's kernels (todhip_match_l2_radius*, below)
+
 // called by todhip_db_load for 128 x f32 rows (already resident in ctx->db_desc): bf16 image, norms, Rmax
 int tod_l2_db_prepare(todhip_ctx* ctx) {
   L2Ws* ws = tod_ws<L2Ws>(ctx);
@@ -515,19 +517,11 @@ int tod_l2_db_prepare(todhip_ctx* ctx) {
   return TODHIP_OK;
 }
 
-static int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k, int exact_only) {
-  L2Ws* ws = tod_ws<L2Ws>(ctx);
-  hipStream_t st = ctx->stream;
-  const uint32_t n = (uint32_t)ctx->shard_rows;
-  TOD_HIP(ws->keys.reserve((size_t)nq * k * 8));
-  TOD_HIP(ws->cand_cnt.reserve(((size_t)nq + kBlockQueries) * 4 * 2));
-  uint32_t* overflow = ws->cand_cnt.as<uint32_t>() + nq + kBlockQueries;
-  if (exact_only) {
-    hipLaunchKernelGGL(l2_exact_scan_kernel, dim3(nq), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(), n, k,
-                       (const uint32_t*)nullptr, ws->keys.as<uint64_t>());
-    TOD_HIP(hipGetLastError());
-    return TODHIP_OK;
-  }
+// What every call that runs the DB pass (l2_gemm_kernel<2, 4>) over nq queries starts with: the launch geometry, the buffers the pass
+// reads and writes, and the queries' bf16 image, |q|^2 (behind eps in q_eps), eps and zeroed shared counters.
+struct L2Pass { uint32_t nq_pad, q_blocks, n_tiles, n_chunks, tiles_per_chunk, n_parts; };
+
+static int l2_pass_begin(todhip_ctx* ctx, L2Ws* ws, const float* d_q, uint32_t nq, L2Pass* out) {
   const uint32_t nq_pad = ((nq + kBlockQueries - 1u) / kBlockQueries) * kBlockQueries;
   const uint32_t q_blocks = nq_pad / kBlockQueries;
   const uint32_t n_tiles = ws->n_pad / kTileRows;
@@ -538,18 +532,38 @@ static int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k, i
   const uint32_t tiles_per_chunk = (n_tiles + n_chunks - 1u) / n_chunks;
   n_chunks = (n_tiles + tiles_per_chunk - 1u) / tiles_per_chunk;
   const uint32_t n_parts = 2u * n_chunks;
+  TOD_HIP(ws->cand_cnt.reserve(((size_t)nq + kBlockQueries) * 4 * 2));
   TOD_HIP(ws->q_bf16.reserve((size_t)nq_pad * kDim * 2));
   TOD_HIP(ws->q_eps.reserve((size_t)nq_pad * 4 * 2));
-  TOD_HIP(ws->part.reserve((size_t)std::max(n_parts, 64u) * nq_pad * kTop * 4));   // the seed pass writes up to 2 x 32 partitions
   TOD_HIP(ws->thr.reserve((size_t)nq_pad * 4 * 2));
   TOD_HIP(ws->cand.reserve((size_t)nq_pad * kCandCap * 4));
   TOD_HIP(ws->slots.reserve((size_t)nq_pad * n_parts * kSlot * 4));        // 2 x 512 partitions x 8 rows x 4 B x 512 queries per query block: 16 MB whatever nq
   TOD_HIP(ws->slot_cnt.reserve((size_t)nq_pad * n_parts * 4));
-  float* qnorm = ws->q_eps.as<float>() + nq_pad;
   // queries: bf16 image pre-scaled by -2 (a power of two: no extra rounding), |q|^2, eps
-  hipLaunchKernelGGL(l2_prepare_kernel, dim3((nq_pad + 3u) / 4u), dim3(256), 0, st, d_q, nq, nq_pad, -2.0f,
-                     ws->q_bf16.as<uint16_t>(), qnorm, (uint32_t*)nullptr, 0, (const uint32_t*)ws->scal.as<uint32_t>(), ws->q_eps.as<float>(),
-                     ws->cand_cnt.as<uint32_t>());
+  hipLaunchKernelGGL(l2_prepare_kernel, dim3((nq_pad + 3u) / 4u), dim3(256), 0, ctx->stream, d_q, nq, nq_pad, -2.0f,
+                     ws->q_bf16.as<uint16_t>(), ws->q_eps.as<float>() + nq_pad, (uint32_t*)nullptr, 0, (const uint32_t*)ws->scal.as<uint32_t>(),
+                     ws->q_eps.as<float>(), ws->cand_cnt.as<uint32_t>());
+  *out = L2Pass{nq_pad, q_blocks, n_tiles, n_chunks, tiles_per_chunk, n_parts};
+  return TODHIP_OK;
+}
+
+static int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k, int exact_only) {
+  L2Ws* ws = tod_ws<L2Ws>(ctx);
+  hipStream_t st = ctx->stream;
+  const uint32_t n = (uint32_t)ctx->shard_rows;
+  TOD_HIP(ws->keys.reserve((size_t)nq * k * 8));
+  if (exact_only) {
+    hipLaunchKernelGGL(l2_exact_scan_kernel, dim3(nq), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(), n, k,
+                       (const uint32_t*)nullptr, ws->keys.as<uint64_t>());
+    TOD_HIP(hipGetLastError());
+    return TODHIP_OK;
+  }
+  L2Pass g;
+  if (int rc = l2_pass_begin(ctx, ws, d_q, nq, &g)) return rc;
+  uint32_t* overflow = ws->cand_cnt.as<uint32_t>() + nq + kBlockQueries;
+  const uint32_t nq_pad = g.nq_pad, q_blocks = g.q_blocks, n_tiles = g.n_tiles, n_chunks = g.n_chunks, tiles_per_chunk = g.tiles_per_chunk,
+                 n_parts = g.n_parts;
+  TOD_HIP(ws->part.reserve((size_t)std::max(n_parts, 64u) * nq_pad * kTop * 4));   // the seed pass writes up to 2 x 32 partitions
   const uint32_t k_eff = std::min(k, std::max(1u, n));
   auto gemm1 = k_eff <= 4u ? l2_gemm_kernel<1, 4> : l2_gemm_kernel<1, 8>;
   float* const d_seed = ws->thr.as<float>() + nq_pad;
@@ -642,7 +656,96 @@ static int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k, i
   return TODHIP_OK;
 }
 
+// The radius search up to its outputs: LT, the DB pass, LR, LS, LE (l2_radius.h). d_counts / d_in_radius: device memory (d_in_radius
+// may be null); d_matches / d_xyz: device memory, or pinned host memory for the matches of the host form.
+static int l2_radius_search(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radius, uint32_t mpq, uint32_t* d_counts,
+                            todhip_dmatch* d_matches, float* d_xyz, uint32_t* d_in_radius) {
+  TOD_HIP(hipSetDevice(ctx->device));
+  L2Ws* ws = tod_ws<L2Ws>(ctx);
+  hipStream_t st = ctx->stream;
+  const float* db = ctx->db_desc.as<float>();
+  TOD_HIP(ws->keys.reserve((size_t)nq * mpq * 8));
+  L2Pass g;
+  if (int rc = l2_pass_begin(ctx, ws, d_q, nq, &g)) return rc;
+  uint32_t* flagged = ws->cand_cnt.as<uint32_t>() + nq + kBlockQueries;             // where l2_keys keeps its overflow flags
+  uint32_t* force = reinterpret_cast<uint32_t*>(ws->thr.as<float>() + g.nq_pad);    // where l2_keys keeps its seeds
+  hipLaunchKernelGGL(l2_radius_threshold_kernel, dim3((g.nq_pad + 255u) / 256u), dim3(256), 0, st, d_q, nq, g.nq_pad, radius,
+                     ws->q_eps.as<float>(), ws->thr.as<float>(), force);
+  KernelTimer timer{ctx};
+  if (int rc = timer.begin()) return rc;
+  hipLaunchKernelGGL((l2_gemm_kernel<2, 4>), dim3(g.n_chunks, g.q_blocks), dim3(256), 0, st, ws->db_bf16.as<uint16_t>(),
+                     ws->db_norm.as<float>(), g.n_tiles, g.tiles_per_chunk, 1u, ws->q_bf16.as<uint16_t>(), g.nq_pad, (float*)nullptr,
+                     ws->thr.as<float>(), ws->slots.as<uint32_t>(), ws->slot_cnt.as<uint32_t>(), ws->cand.as<uint32_t>(),
+                     ws->cand_cnt.as<uint32_t>());
+  if (int rc = timer.end()) return rc;
+  hipLaunchKernelGGL(l2_radius_refine_kernel, dim3(nq), dim3(256), 0, st, d_q, db, ws->slots.as<uint32_t>(), ws->slot_cnt.as<uint32_t>(),
+                     g.n_parts, ws->cand.as<uint32_t>(), ws->cand_cnt.as<uint32_t>(), force, radius, mpq, ws->keys.as<uint64_t>(), d_counts,
+                     d_in_radius, flagged);
+  hipLaunchKernelGGL(l2_radius_scan_kernel, dim3(nq), dim3(256), 0, st, d_q, db, (uint32_t)ctx->shard_rows, flagged, radius, mpq,
+                     ws->keys.as<uint64_t>(), d_counts, d_in_radius);
+  const size_t slots = (size_t)nq * mpq;
+  hipLaunchKernelGGL(l2_radius_emit_kernel, dim3((uint32_t)((slots + 255u) / 256u)), dim3(256), 0, st, ws->keys.as<uint64_t>(), d_counts, nq,
+                     mpq, ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), d_matches, d_xyz);
+  TOD_HIP(hipGetLastError());
+  return TODHIP_OK;
+}
+
+static int l2_radius_args(const todhip_ctx* ctx, uint32_t nq, float radius, uint32_t mpq) {
+  if (nq == 0 || mpq == 0 || mpq > kL2MaxPerQuery || !(radius > 0.f) || !std::isfinite(radius)) return TODHIP_EINVAL;
+  if (ctx->total_rows == 0) return TODHIP_ENODB;
+  if (ctx->desc_bytes != kDim * 4u || ctx->shard_rows != ctx->total_rows) return TODHIP_EINVAL;   // needs a 128 x f32 DB
+  return TODHIP_OK;
+}
+
 extern "C" {
+
+int todhip_match_l2_radius_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, float radius, uint32_t max_per_query, void* d_counts,
+                                  void* d_matches, void* d_matches_xyz, void* d_in_radius) {
+  if (!ctx || !d_q_desc || !d_counts || !d_matches || !d_matches_xyz) return TODHIP_EINVAL;
+  int rc = l2_radius_args(ctx, nq, radius, max_per_query);
+  if (rc != TODHIP_OK) return rc;
+  rc = l2_radius_search(ctx, reinterpret_cast<const float*>(d_q_desc), nq, radius, max_per_query, reinterpret_cast<uint32_t*>(d_counts),
+                        reinterpret_cast<todhip_dmatch*>(d_matches), reinterpret_cast<float*>(d_matches_xyz),
+                        reinterpret_cast<uint32_t*>(d_in_radius));
+  if (rc == TODHIP_OK) { ctx->counters.last_nq = nq; ctx->counters.last_k = max_per_query; }
+  return rc;
+}
+
+int todhip_match_l2_radius(todhip_ctx* ctx, const float* q_desc, uint32_t nq, float radius, uint32_t max_per_query, uint32_t* row_ptr,
+                           todhip_dmatch* matches, float* matches_xyz, uint32_t* n_matches, uint32_t* in_radius) {
+  if (!ctx || !q_desc || !row_ptr || !matches || !matches_xyz || !n_matches) return TODHIP_EINVAL;
+  int rc = l2_radius_args(ctx, nq, radius, max_per_query);
+  if (rc != TODHIP_OK) return rc;
+  TOD_HIP(hipSetDevice(ctx->device));
+  const size_t nm = (size_t)nq * max_per_query;
+  TOD_HIP(ctx->m_q.reserve((size_t)nq * kDim * 4));
+  TOD_HIP(ctx->m_counts.reserve(2u * (size_t)nq * sizeof(uint32_t)));
+  uint32_t* d_counts = ctx->m_counts.as<uint32_t>();
+  uint32_t* d_in = d_counts + nq;
+  // the emit kernel writes the kept matches straight into pinned host memory, as todhip_match_radius's does; the two count arrays
+  // are read by kernels and come over with one copy
+  TOD_HIP(ctx->h_stage.reserve(2u * (size_t)nq * sizeof(uint32_t) + nm * sizeof(todhip_dmatch) + nm * 3 * sizeof(float)));
+  uint32_t* h_counts = ctx->h_stage.as<uint32_t>();
+  uint32_t* h_in = h_counts + nq;
+  todhip_dmatch* h_m = reinterpret_cast<todhip_dmatch*>(h_in + nq);
+  float* h_xyz = reinterpret_cast<float*>(h_m + nm);
+  TOD_HIP(hipMemcpyAsync(ctx->m_q.p, q_desc, (size_t)nq * kDim * 4, hipMemcpyHostToDevice, ctx->stream));
+  rc = l2_radius_search(ctx, ctx->m_q.as<float>(), nq, radius, max_per_query, d_counts, h_m, h_xyz, d_in);
+  if (rc != TODHIP_OK) return rc;
+  TOD_HIP(hipMemcpyAsync(h_counts, d_counts, 2u * (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  TOD_HIP(hipStreamSynchronize(ctx->stream));
+  if (in_radius) std::memcpy(in_radius, h_in, (size_t)nq * sizeof(uint32_t));
+  uint64_t total = 0;
+  for (uint32_t qi = 0; qi < nq; ++qi) { row_ptr[qi] = (uint32_t)total; total += h_counts[qi]; }
+  row_ptr[nq] = (uint32_t)total;                            // nq * max_per_query < 2^32 matches or the reserve above has failed
+  const uint32_t capacity = *n_matches;
+  *n_matches = (uint32_t)total;
+  ctx->counters.last_nq = nq;
+  ctx->counters.last_k = max_per_query;
+  if (total > capacity) return TODHIP_ECAPACITY;            // row_ptr, in_radius and the needed count are the caller's already
+  ctx->counters.last_matches = tod_pack_csr(h_counts, h_m, h_xyz, nq, max_per_query, row_ptr, matches, matches_xyz);
+  return TODHIP_OK;
+}
 
 int todhip_match_l2_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint32_t k, float radius, void* d_counts,
                            void* d_matches, void* d_matches_xyz) {
