@@ -20,8 +20,10 @@
 // instead of 2.03 ms per 32 000 x 1M launch) and the headline 4 % (tools/ab_prio.sh), ORB's own stage time unchanged within the spread.
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "ctx.h"
+#include "orb_compass.h"
 #include "orb_stages.h"
 
 using namespace tod_orb;
@@ -37,7 +39,7 @@ namespace {
 // only (image and mask are copied in, keypoints copied out), so the caller's pointers may change from call to call without a
 // re-capture. The key says what the captured sequence depends on.
 struct OrbGraph {
-  struct Key { uint32_t H, W, n_features, n_levels, cap, F; float sf; const void *kp, *aux, *desc, *img0, *mask; } key = {};
+  struct Key { uint32_t H, W, n_features, n_levels, cap, F; float sf; const void *kp, *aux, *desc, *img0, *mask, *taps; } key = {};
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   void drop() {                                            // the only teardown
@@ -59,9 +61,10 @@ struct OrbGraph {
 
 struct OrbWs : TodWs {
   static constexpr int kSlot = kWsOrb;
-  DevBuf pyr, blur, cand, eq, sel1, sel2, small, pattern, in_img, kp_xy, kp_aux, desc, o_xy, o_aux, o_desc, maskbuf;
+  DevBuf pyr, blur, cand, eq, sel1, sel2, small, pattern, in_img, kp_xy, kp_aux, desc, o_xy, o_aux, o_desc, maskbuf, taps;
   HostBuf h_out, h_kp;                                     // h_kp: the host form's keypoints, written by copy_out_kernel itself
   bool pattern_is_default = false;
+  struct TapsFor { uint32_t H, W, n_levels; float sf; const void* p; } taps_for = {};   // the pyramid whose resize taps are in `taps`
   OrbGraph graph;
   OrbPlan plan = {};                                       // of the last call, tab.img filled in: for tod_orb_stages
   ~OrbWs() override { graph.drop(); }                      // the captured graph goes before the buffers it refers to
@@ -84,6 +87,7 @@ int reserve_buffers(todhip_ctx* ctx, OrbWs* ws, const OrbPlan& P, bool masked) {
   TOD_HIP(ws->o_xy.reserve((size_t)P.F * P.cap * 8)); TOD_HIP(ws->o_aux.reserve((size_t)P.F * P.cap * 16));
   TOD_HIP(ws->o_desc.reserve((size_t)P.F * P.cap * 32));
   if (masked) TOD_HIP(ws->maskbuf.reserve(P.F * P.px));
+  TOD_HIP(ws->taps.reserve((size_t)P.n_taps * sizeof(ResizeTap) + 32));
   return TODHIP_OK;
 }
 
@@ -98,6 +102,19 @@ int upload_pattern(todhip_ctx* ctx, OrbWs* ws, const int8_t* pattern) {
   return TODHIP_OK;
 }
 
+// the resize's tap tables (orb_plan.h), unless those of this pyramid are already there: they depend on the level sizes alone, so a
+// context that sees one geometry fills them once, and a replay of the cached graph uploads nothing
+int upload_taps(todhip_ctx* ctx, OrbWs* ws, const OrbPlan& P, float scale_factor) {
+  const OrbWs::TapsFor now = {P.H, P.W, P.n_levels, scale_factor, ws->taps.p};
+  if (std::memcmp(&now, &ws->taps_for, sizeof(now)) == 0 || P.n_taps == 0u) return TODHIP_OK;
+  std::vector<ResizeTap> taps(P.n_taps);
+  fill_resize_taps(P, taps.data());
+  TOD_HIP(hipMemcpyAsync(ws->taps.p, taps.data(), taps.size() * sizeof(ResizeTap), hipMemcpyHostToDevice, ctx->stream));
+  TOD_HIP(hipStreamSynchronize(ctx->stream));            // the vector lives on this stack frame
+  ws->taps_for = now;
+  return TODHIP_OK;
+}
+
 // The launch sequence and nothing else: the pyramid first (level l from level l - 1), then every kernel once for all levels and
 // frames. P is the workspace's plan (tab.img filled in); the image is in ws->pyr, the keypoints go to ws->o_*.
 void record_stages(const OrbPlan& P, const OrbWs* ws, const uint8_t* d_mask, hipStream_t st) {
@@ -108,8 +125,9 @@ void record_stages(const OrbPlan& P, const OrbWs* ws, const uint8_t* d_mask, hip
     // reads it, and with want == 0 no kernel looks at its image
     if (P.resize_x[lvl] == 0u) continue;
     uint8_t* img = ws->pyr.as<uint8_t>() + (size_t)lvl * P.F * px;
-    hipLaunchKernelGGL(resize_kernel, dim3(P.resize_x[lvl], P.F), dim3(256), 0, st, img - (size_t)P.F * px, T.h[lvl - 1], T.w[lvl - 1],
-                       img, T.h[lvl], T.w[lvl], px);
+    const ResizeTap* taps = ws->taps.as<ResizeTap>();
+    hipLaunchKernelGGL(resize_kernel, grid(P.resize[lvl]), dim3(256), 0, st, img - (size_t)P.F * px, T.w[lvl - 1], img, T.h[lvl], T.w[lvl],
+                       taps + P.tap_x[lvl], taps + P.tap_y[lvl], px);
   }
   uint32_t* ctl = ws->small.as<uint32_t>();
   uint32_t* level_counts = ctl + P.level_counts_off;
@@ -146,6 +164,7 @@ int orb_device(todhip_ctx* ctx, const OrbIn& in, const OrbParams& par, const Orb
   }
   if (const int rc = reserve_buffers(ctx, ws, P, in.d_mask != nullptr)) return rc;
   if (const int rc = upload_pattern(ctx, ws, par.pattern)) return rc;
+  if (const int rc = upload_taps(ctx, ws, P, par.scale_factor)) return rc;
   for (uint32_t lvl = 0; lvl < P.n_levels; ++lvl) P.tab.img[lvl] = ws->pyr.as<uint8_t>() + (size_t)lvl * P.F * P.px;
   ws->plan = P;
   uint32_t* ctl = ws->small.as<uint32_t>();
@@ -165,7 +184,7 @@ int orb_device(todhip_ctx* ctx, const OrbIn& in, const OrbParams& par, const Orb
   if (!use_graph) {
     record_stages(ws->plan, ws, ws_mask, st);
   } else {
-    const OrbGraph::Key key = {P.H, P.W, par.n_features, P.n_levels, P.cap, P.F, par.scale_factor, ws_xy, ws_aux, ws_desc, ws->pyr.p, ws_mask};
+    const OrbGraph::Key key = {P.H, P.W, par.n_features, P.n_levels, P.cap, P.F, par.scale_factor, ws_xy, ws_aux, ws_desc, ws->pyr.p, ws_mask, ws->taps.p};
     if (!ws->graph.matches(key)) {
       TOD_HIP(ws->graph.begin_capture(st));
       record_stages(ws->plan, ws, ws_mask, st);

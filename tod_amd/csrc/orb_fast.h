@@ -1,8 +1,7 @@
 // FAST-9/16 on every level in one launch: the score, its border rule, the compass pre-test, and fast_nms_kernel, which scores a tile
 // in LDS, suppresses non-maxima, applies the level-0 mask and appends the candidates with their score histogram.
-// Included by orb.hip inside its anonymous namespace, after orb_stages.h (wave_append, the tile size) and orb_pyramid.h (load_px4).
-
-constexpr int kFastThr = 20;
+// Included by orb.hip inside its anonymous namespace, after orb_stages.h (wave_append, the tile size), orb_compass.h (kFastThr,
+// compass4: the pre-test on four positions) and orb_pyramid.h (load_px4).
 
 // FAST-9/16 score: max over the 16 arcs of 9 contiguous circle pixels, both polarities, of the minimum difference.
 // Sliding minima over the (cyclic) circle: windows of 2, 4, 8, then 9.
@@ -20,12 +19,10 @@ __device__ __forceinline__ int arc9_max(const int (&d)[16]) {
   return best;
 }
 
-// the border rule of the score: positions whose ring or whose non-maximum neighbourhood cannot hold a keypoint score 0 and read nothing
-__device__ __forceinline__ bool fast_in_border(uint32_t h, uint32_t w, int x, int y) {
-  return x < kEdge - 1 || x >= (int)w - kEdge + 1 || y < kEdge - 1 || y >= (int)h - kEdge + 1;
-}
+// The border rule of the score: positions whose ring or whose non-maximum neighbourhood cannot hold a keypoint score 0 and read
+// nothing: x < kEdge - 1, x >= w - kEdge + 1, y < kEdge - 1 or y >= h - kEdge + 1 (pass 1 of fast_nms_kernel applies it).
 
-// the score of the pixel at c in an image of row pitch W (a position outside fast_in_border)
+// the score of the pixel at c in an image of row pitch W (a position inside the border rule's rectangle)
 __device__ __forceinline__ int fast_score_at(const uint8_t* c, int W) {
   const int p = c[0];
   int d[16], nd[16];
@@ -39,15 +36,24 @@ __device__ __forceinline__ int fast_score_at(const uint8_t* c, int W) {
   return best > kFastThr ? best : 0;
 }
 
-// What a 9-arc above the threshold needs: any 9 contiguous ring pixels hold two cyclically adjacent ones of the compass points
-// (ring positions 0, 4, 8, 12), so two adjacent compass points are both brighter than p + kFastThr or both darker than
-// p - kFastThr wherever fast_score_at is not 0. Same pixels, same comparisons (d > kFastThr, -d > kFastThr) as the score's.
-__device__ __forceinline__ bool fast_compass(const uint8_t* c, int W) {
-  const int p = c[0];
-  const int d0 = c[3 * W] - p, d4 = c[3] - p, d8 = c[-3 * W] - p, d12 = c[-3] - p;
-  const bool b0 = d0 > kFastThr, b4 = d4 > kFastThr, b8 = d8 > kFastThr, b12 = d12 > kFastThr;
-  const bool k0 = -d0 > kFastThr, k4 = -d4 > kFastThr, k8 = -d8 > kFastThr, k12 = -d12 > kFastThr;
-  return (b0 && b4) || (b4 && b8) || (b8 && b12) || (b12 && b0) || (k0 && k4) || (k4 && k8) || (k8 && k12) || (k12 && k0);
+// Append to a list whose order is free, up to four entries per lane (bit i of m: the lane appends p + i): one exclusive prefix sum
+// of the lanes' popcounts across the wave, taken bit by bit from four ballots, and one atomic on *counter. Called by all lanes of
+// the wave together.
+__device__ __forceinline__ void wave_append4(uint32_t* counter, uint16_t* list, uint32_t m, uint32_t p) {
+  uint32_t before = 0u, total = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(((m >> i) & 1u) != 0u);
+    before = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, before));
+    total += (uint32_t)__popcll(bal);
+  }
+  if (total == 0u) return;                                   // wave-uniform
+  uint32_t base = 0u;
+  if ((threadIdx.x & 63u) == 0u) base = atomicAdd(counter, total);
+  uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)base, 0) + before;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if ((m >> i) & 1u) list[slot++] = (uint16_t)(p + (uint32_t)i);
 }
 
 // FAST score + 3x3 strict non-maximum suppression + compaction in one pass: a block scores a 64 x 16 pixel tile and
@@ -55,14 +61,16 @@ __device__ __forceinline__ bool fast_compass(const uint8_t* c, int W) {
 // is fixed later by the ranking kernels, so appends are aggregated per wave (wave_append).
 //
 // The score is found in two passes over an LDS copy of the tile's pixels (tile + 1 pixel for the suppression + 3 for the ring,
-// loaded once as dwords; every ring read is an LDS read). Pass 1 visits all (64 + 2) x (16 + 2) positions, applies the border
-// rule and the compass test (fast_compass: necessary for a non-zero score, five pixels instead of seventeen and no arc search)
-// and appends the survivors to an LDS list (wave_append, one LDS atomic per wave). Pass 2 runs the exact score over that
-// list with dense lanes. On textured images 4 % of the positions score and 6-7 % survive pass 1, but they are spread so that
-// most 64-pixel row segments hold one: an early exit that needs a whole wave to fail the test would almost never be taken, so
+// loaded once as dwords; every ring read is an LDS read). Pass 1 visits all (64 + 2) x (16 + 2) positions, four neighbours of a
+// row per lane: it applies the border rule and the compass test (compass4: necessary for a non-zero score, five pixels instead of
+// seventeen and no arc search; the five windows of a group are seven aligned LDS words) and appends the survivors to an LDS list
+// (wave_append4, one LDS atomic per wave). Pass 2 runs the exact score over that list with dense lanes. On textured images 4 %
+// of the positions score and 6-7 % survive pass 1, but they are spread so that most 64-pixel row segments hold one: an early exit that needs a whole wave to fail the test would almost never be taken, so
 // the survivors are compacted instead. On noise every position survives; the list holds them all.
 constexpr int kNmsScoreW = kNmsTileW + 2, kNmsScoreN = (kNmsTileH + 2) * kNmsScoreW;     // scored positions: the tile and 1 pixel around
 constexpr int kNmsImgDw = (kNmsTileW + 8) / 4, kNmsImgW = 4 * kNmsImgDw, kNmsImgH = kNmsTileH + 8;   // staged pixels: 4 around
+constexpr int kNmsGroups = (kNmsScoreW + 3) / 4, kNmsGroupN = (kNmsTileH + 2) * kNmsGroups;           // pass 1's groups of four positions
+static_assert(kNmsScoreW % 4 == 2 && kNmsGroups + 1 == kNmsImgDw, "pass 1: a row's last group is two positions, its windows end with the staged row");
 __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, uint32_t cap, uint32_t* counter, uint32_t* hist,
                                                        const uint8_t* __restrict__ mask, uint32_t H0, uint32_t W0, size_t fs) {
   const uint32_t v = blockIdx.z, lvl = v / T.F, f = v - lvl * T.F;
@@ -71,7 +79,7 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, u
   const uint8_t* __restrict__ img = T.img[lvl] + f * fs;
   cand += (size_t)v * cap; counter += v * kCtlWords; hist += v * kCtlWords;
   if (mask) mask += f * fs;
-  __shared__ int s_score[kNmsScoreN];
+  __shared__ __align__(8) int s_score[kNmsScoreN];           // (pass 1 clears it two positions a store; a row starts on an even one)
   __shared__ uint32_t s_hist[256];
   __shared__ uint32_t s_img[kNmsImgH * kNmsImgDw];          // pixel (x0 - 4 + i, y0 - 4 + r) is byte r * kNmsImgW + i
   __shared__ uint16_t s_list[kNmsScoreN];                   // pass 1's survivors (positions of s_score), in any order
@@ -91,14 +99,27 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, u
   __syncthreads();
   const uint8_t* s_px = reinterpret_cast<const uint8_t*>(s_img);
 #pragma unroll
-  for (int p0 = 0; p0 < kNmsScoreN; p0 += 256) {             // pass 1
-    const int p = p0 + (int)threadIdx.x, py = p / kNmsScoreW, px = p - py * kNmsScoreW;
-    const bool valid = p < kNmsScoreN;
-    bool go = valid && !fast_in_border(h, w, x0 - 1 + px, y0 - 1 + py);
-    if (go) go = fast_compass(s_px + (py + 3) * kNmsImgW + px + 3, kNmsImgW);
-    if (valid) s_score[p] = 0;
-    const uint32_t slot = wave_append(&s_n, go);
-    if (go) s_list[slot] = (uint16_t)p;
+  for (int t0 = 0; t0 < kNmsGroupN; t0 += 256) {             // pass 1: positions 4 g .. 4 g + 3 of scored row py
+    if (t0 + (int)(threadIdx.x & ~63u) >= kNmsGroupN) break; // wave-uniform: no lane of this wave has a group left
+    const int t = t0 + (int)threadIdx.x, py = t / kNmsGroups, g = t - py * kNmsGroups, px = 4 * g;
+    uint32_t m = 0u;                                         // bit i: position px + i goes on to pass 2
+    if (t < kNmsGroupN) {
+      int2* z = reinterpret_cast<int2*>(&s_score[py * kNmsScoreW + px]);
+      z[0] = make_int2(0, 0);
+      if (g + 1 < kNmsGroups) z[1] = make_int2(0, 0);        // the last group of a row is its last two positions
+      // the group's positions that the border rule lets through and that lie inside the row are lo .. hi - 1
+      const int xs = x0 - 1 + px, y = y0 - 1 + py;
+      const int lo = max(kEdge - 1 - xs, 0), hi = min(min((int)w - kEdge + 1 - xs, kNmsScoreW - px), 4);
+      if (hi > lo && y >= kEdge - 1 && y < (int)h - kEdge + 1) m = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+      if (m) {
+        // the centre pixels are bytes 4 g + 3 .. 4 g + 6 of staged row py + 3. For a row's last group c[2] is the first word of the
+        // next staged row (py + 4 < kNmsImgH): it feeds the two positions past the row's end, which are not in m
+        const uint32_t* c = s_img + (py + 3) * kNmsImgDw + g;
+        const uint32_t *up = c - 3 * kNmsImgDw, *dn = c + 3 * kNmsImgDw;
+        m &= compass4(window4(c[0], c[1], 3), window4(dn[0], dn[1], 3), window4(c[1], c[2], 2), window4(up[0], up[1], 3), c[0]);
+      }
+    }
+    wave_append4(&s_n, s_list, m, (uint32_t)(py * kNmsScoreW + px));
   }
   __syncthreads();
   const uint32_t n_list = s_n;                               // <= kNmsScoreN: every position is appended at most once

@@ -1,7 +1,8 @@
 // Stage A's launch plan (host, plain C++, no HIP include; included by orb_stages.h; tested stand-alone by tests/orb_plan_host_test.cpp):
 // the constants and records the kernels and the host share, the pyramid's geometry, and OrbPlan -- every buffer capacity, the layout of
-// the control block and the grid extent of every launch, from the call's seven numbers. The floats of features_per_level and
-// level_table decide pyramid sizes that the CPU restatement must reproduce bit for bit: their expressions do not change.
+// the control block, the grid extent of every launch and the resize's tap tables, from the call's seven numbers. The floats of
+// features_per_level and level_table decide pyramid sizes, those of resize_taps the pixels of every resized level, and the CPU
+// restatement must reproduce both bit for bit: their expressions do not change.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -105,6 +106,26 @@ inline uint32_t level_table(uint32_t H, uint32_t W, uint32_t F, uint32_t n_featu
   return want_max;
 }
 
+// One axis of the bilinear resize, per destination index: the two source indices, clamped into the source, and their 11-bit weights
+// (wa + wb = 2048), laid out as the kernel uses them: one 16-byte load and no arithmetic. The sample position is
+// (i + 0.5) * (src_n / dst_n) - 0.5 in floats; these expressions are the CPU restatement's, term for term, and must not be contracted
+// or reassociated. They depend on the geometry alone, so resize_kernel reads them from tables that are filled once per geometry
+// instead of dividing and rounding for every pixel.
+struct ResizeTap { uint32_t a, b, wa, wb; };
+inline void resize_taps(uint32_t src_n, uint32_t dst_n, ResizeTap* taps) {
+  const float s = (float)src_n / (float)dst_n;
+  for (uint32_t i = 0; i < dst_n; ++i) {
+    const float f = ((float)i + 0.5f) * s - 0.5f;
+    const int i0 = (int)floorf(f);
+    const int w = (int)rintf((f - (float)i0) * 2048.f);
+    taps[i].a = (uint32_t)std::min(std::max(i0, 0), (int)src_n - 1); taps[i].b = (uint32_t)std::min(std::max(i0 + 1, 0), (int)src_n - 1);
+    taps[i].wa = (uint32_t)(2048 - w); taps[i].wb = (uint32_t)w;
+  }
+}
+
+// the pixel tile of a block of resize_kernel: a lane writes four neighbouring pixels of a row
+constexpr uint32_t kResizeGroups = 16, kResizeRows = 16;
+
 // One call's sizes and grids. (level l, frame f) is virtual frame l F + f: it owns slice l F + f of every per-level buffer and row
 // l F + f of the control block, and rides in the last grid dimension of every launch.
 struct OrbGrid { uint32_t x, y, z; };
@@ -116,8 +137,22 @@ struct OrbPlan {
   uint32_t want_max;                                       // 0: no level can hold a keypoint, nothing is launched
   LevelTab tab;                                            // img[] stays null here: the workspace's owner fills it in
   OrbGrid copy_rows, fast_nms, fast_threshold, split, rank_ties, harris, rank_harris, blur, describe, copy_out;
-  uint32_t resize_x[kMaxLevels];                           // blocks of level l's resize (y: F); 0: no launch (level 0, or no pixels)
+  uint32_t resize_x[kMaxLevels];                           // level l's pixels in blocks of 256; 0: no resize launch (level 0, or no pixels)
+  OrbGrid resize[kMaxLevels];                              // level l's resize launch where resize_x[l] != 0: tiles across, tiles down, frames
+  uint32_t tap_x[kMaxLevels], tap_y[kMaxLevels], n_taps;   // of such a level: where its column and row taps start in the tap table; its size
 };
+
+// the tap table of a plan: the column taps of every resized level, padded to whole groups of four with copies of the last column's
+// (a lane's four taps are always there and always name pixels of the source), and its row taps
+inline void fill_resize_taps(const OrbPlan& P, ResizeTap* taps) {
+  for (uint32_t lvl = 1; lvl < P.n_levels; ++lvl) {
+    if (P.resize_x[lvl] == 0u) continue;
+    const uint32_t w = P.tab.w[lvl];
+    resize_taps(P.tab.w[lvl - 1], w, taps + P.tap_x[lvl]);
+    for (uint32_t i = w; i < (w + 3u) / 4u * 4u; ++i) taps[P.tap_x[lvl] + i] = taps[P.tap_x[lvl] + w - 1u];
+    resize_taps(P.tab.h[lvl - 1], P.tab.h[lvl], taps + P.tap_y[lvl]);
+  }
+}
 
 // check_args' status; *P is filled when that is TODHIP_OK
 inline int orb_plan(uint32_t F, uint32_t H, uint32_t W, uint32_t n_features, uint32_t n_levels, float scale_factor, uint32_t cap,
@@ -131,9 +166,16 @@ inline int orb_plan(uint32_t F, uint32_t H, uint32_t W, uint32_t n_features, uin
   P->want_max = level_table(H, W, F, n_features, n_levels, scale_factor, &P->tab);
   const uint32_t Vg = (uint32_t)P->V;
   P->copy_rows = {(uint32_t)((P->px + 255) / 256), F, 1u};
+  P->n_taps = 0;
   for (uint32_t lvl = 0; lvl < (uint32_t)kMaxLevels; ++lvl) {
     const uint32_t hw = lvl < n_levels ? P->tab.h[lvl] * P->tab.w[lvl] : 0u;
     P->resize_x[lvl] = (lvl > 0 && hw > 0u) ? (hw + 255u) / 256u : 0u;
+    P->resize[lvl] = {0u, 0u, 0u}; P->tap_x[lvl] = P->tap_y[lvl] = 0u;
+    if (P->resize_x[lvl] == 0u) continue;
+    const uint32_t h = P->tab.h[lvl], w = P->tab.w[lvl], groups = (w + 3u) / 4u;
+    P->resize[lvl] = {(groups + kResizeGroups - 1u) / kResizeGroups, (h + kResizeRows - 1u) / kResizeRows, F};
+    P->tap_x[lvl] = P->n_taps; P->tap_y[lvl] = P->n_taps + 4u * groups;      // both start on a group of four
+    P->n_taps = P->tap_y[lvl] + (h + 3u) / 4u * 4u;
   }
   P->fast_nms = {(W + kNmsTileW - 1) / kNmsTileW, (H + kNmsTileH - 1) / kNmsTileH, Vg};
   P->fast_threshold = {Vg, 1u, 1u};

@@ -12,30 +12,39 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const uint8_t* __restric
   dst[i] = src[(size_t)(i / w) * stride + (i % w)];
 }
 
-// 11-bit fixed-point bilinear resize, sample positions (x + 0.5) * sx - 0.5, replicate border
-__global__ __launch_bounds__(256) void resize_kernel(const uint8_t* __restrict__ src, uint32_t sh, uint32_t sw, uint8_t* dst,
-                                                     uint32_t dh, uint32_t dw, size_t fs) {
-  src += blockIdx.y * fs; dst += blockIdx.y * fs;
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= dh * dw) return;
-  const uint32_t x = i % dw, y = i / dw;
-  const float sx = (float)sw / (float)dw, sy = (float)sh / (float)dh;
-  const float fy = ((float)y + 0.5f) * sy - 0.5f;
-  const int y0 = (int)floorf(fy);
-  const int wy = (int)rintf((fy - (float)y0) * 2048.f);
-  const int ya = clampi(y0, 0, (int)sh - 1), yb = clampi(y0 + 1, 0, (int)sh - 1);
-  const float fx = ((float)x + 0.5f) * sx - 0.5f;
-  const int x0 = (int)floorf(fx);
-  const int wx = (int)rintf((fx - (float)x0) * 2048.f);
-  const int xa = clampi(x0, 0, (int)sw - 1), xb = clampi(x0 + 1, 0, (int)sw - 1);
-  const int top = src[ya * sw + xa] * (2048 - wx) + src[ya * sw + xb] * wx;
-  const int bot = src[yb * sw + xa] * (2048 - wx) + src[yb * sw + xb] * wx;
-  dst[i] = (uint8_t)((top * (2048 - wy) + bot * wy + (1 << 21)) >> 22);
-}
-
 // four pixels of a row at any byte offset: level rows have pitch w, so a pixel group is not dword-aligned
 __device__ __forceinline__ uint32_t load_px4(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 __device__ __forceinline__ void store_px4(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
+
+// 11-bit fixed-point bilinear resize, sample positions (x + 0.5) * sx - 0.5, replicate border: the source indices and weights of
+// every column and row come from the plan's tap tables (resize_taps), the blend is the integer one. A block writes a tile of
+// 4 kResizeGroups x kResizeRows pixels, a lane four neighbouring pixels of a row; a group past the row's end has copies of the last
+// column's taps, so every lane of a row computes four pixels and stores those inside it.
+__global__ __launch_bounds__(256) void resize_kernel(const uint8_t* __restrict__ src, uint32_t sw, uint8_t* dst, uint32_t dh, uint32_t dw,
+                                                     const ResizeTap* __restrict__ xtaps, const ResizeTap* __restrict__ ytaps, size_t fs) {
+  src += blockIdx.z * fs; dst += blockIdx.z * fs;
+  const uint32_t x = 4u * (blockIdx.x * kResizeGroups + threadIdx.x % kResizeGroups), y = blockIdx.y * kResizeRows + threadIdx.x / kResizeGroups;
+  if (x >= dw || y >= dh) return;
+  const ResizeTap ty = ytaps[y];
+  const uint32_t ra = ty.a * sw, rb = ty.b * sw;             // 32-bit offsets into the frame's slice, as every pixel index of a level is
+  uint32_t px = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const ResizeTap tx = xtaps[x + i];
+    // every factor is below 2^24 and every sum below 2^31 (255 * 2048 * 2048 + 2^21): the 24-bit multiplies are exact
+    const uint32_t top = __umul24(src[ra + tx.a], tx.wa) + __umul24(src[ra + tx.b], tx.wb);
+    const uint32_t bot = __umul24(src[rb + tx.a], tx.wa) + __umul24(src[rb + tx.b], tx.wb);
+    px |= (uint32_t)(uint8_t)((__umul24(top, ty.wa) + __umul24(bot, ty.wb) + (1u << 21)) >> 22) << (8 * i);
+  }
+  uint8_t* o = dst + (y * dw + x);
+  if (x + 3u < dw) {
+    store_px4(o, px);
+  } else {                                                   // the row ends inside these four
+    o[0] = (uint8_t)px;
+    if (x + 1u < dw) o[1] = (uint8_t)(px >> 8);
+    if (x + 2u < dw) o[2] = (uint8_t)(px >> 16);
+  }
+}
 
 __constant__ int c_gauss7[7] = {18, 33, 49, 56, 49, 33, 18};
 

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "ctx.h"
+#include "orb_moments.h"
 #include "orb_plan.h"
 
 namespace tod_orb {
@@ -30,12 +31,9 @@ __device__ __forceinline__ void patch_moments(const uint8_t* __restrict__ img, i
   if (l < 31u) {
     const int v = (int)l - kHalfPatch;
     const int d = v == 0 ? kHalfPatch : umax[v < 0 ? -v : v];
-    int rs = 0;
-    for (int u = -d; u <= d; ++u) {
-      const int px = img[(size_t)(y + v) * W + x + u];
-      m10 += u * px;
-      rs += px;
-    }
+    int rs;
+    // the row from u = -15 as eight unaligned words (orb_moments.h): a keypoint is kEdge pixels inside its level, the 32 bytes in its row
+    row_moments(img + (size_t)(y + v) * W + x - kHalfPatch, d, rs, m10);
     m01 = v * rs;
   }
 #pragma unroll
