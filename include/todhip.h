@@ -783,6 +783,15 @@ int todhip_test_depth_lookup(todhip_ctx*, const void* d_depth, int depth_is_u16,
  * when it is <= minimal_size, a lower bound > minimal_size otherwise; out3[2] = steps actually walked. */
 int todhip_test_clique_gate(todhip_ctx*, uint32_t m, const uint32_t* edges, uint32_t n_edges, uint32_t minimal_size,
                             uint32_t* out3);
+/* The verifier's speculative draw table of one object alone (drawIndexSampleHelper, sac_model_registration_graph.h:102-132, started
+ * at every position 0 .. S - 1 of the window_len words rnd of the rand() stream): samp = the n x W sample bit matrix, valid = W
+ * words, W = ceil(n / 64), all host arrays. entries_out: S entries of six words {status (0 failed, 1 drawn, 2 the window ended
+ * first), draws consumed, the three samples deepest first, 0}. form: 0 = the kernel the verifier itself would pick for this n,
+ * 1 = one lane per position (n <= 512), 2 = one wave per position over 64 words (n <= 4096), 3 = over 512 words, 4 = one lane
+ * per position with eight words a lane also where n <= 128 (form 1 picks the two-word kernel there); a form that cannot hold n
+ * matches is TODHIP_EINVAL. */
+int todhip_test_draw_table(todhip_ctx*, const uint64_t* samp, const uint64_t* valid, uint32_t n, const uint32_t* rnd,
+                           uint32_t window_len, uint32_t S, uint32_t form, uint32_t* entries_out);
 
 /* FillAdjacency + selectWithinDistance (sac_model_registration_graph.h:171-269) for given sample triples
  * (samples_ order): counts[t] = consensus size, 0 when the clique gate rejects. stop_level 1 skips the clique

@@ -100,6 +100,7 @@ EXPORTS = [
     "todhip_test_depth_lookup", "todhip_pipeline_set_depth_size", "todhip_pipeline_submit_masked", "todhip_pipeline_submit_masked_device",
     "todhip_model_add_observations_device",
     "todhip_match_l2_radius", "todhip_match_l2_radius_device",
+    "todhip_test_draw_table",
 ]
 
 MAX_TRAIN_BATCH_VIEWS = 64
@@ -199,6 +200,9 @@ def lib():
             L.todhip_match_l2_radius.restype = C.c_int
             L.todhip_match_l2_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 4
             L.todhip_match_l2_radius_device.restype = C.c_int
+        if hasattr(L, "todhip_test_draw_table"):                      # (as above)
+            L.todhip_test_draw_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.todhip_test_draw_table.restype = C.c_int
         _lib = L
     return _lib
 
@@ -682,6 +686,20 @@ class Context:
                                          None if dbg is None else _np_ptr(dbg), C.c_uint32(dbg_stride))
         _check(rc, "todhip_test_consensus")
         return counts, dbg
+
+    def test_draw_table(self, samp, valid, n, rnd, S, form=0):
+        """The draw table of one object (todhip_test_draw_table): samp u64 [n, W], valid u64 [W], rnd u32 [window_len]. Returns
+        (status, entries u32 [S, 6]): OK, or EINVAL when `form` (0 routing, 1 lane, 2 wave of one slice, 3 of eight, 4 eight-word lane)
+        cannot hold n matches."""
+        W = (n + 63) // 64
+        samp = np.ascontiguousarray(samp, np.uint64).reshape(n, W)
+        valid = np.ascontiguousarray(valid, np.uint64).reshape(W)
+        rnd = np.ascontiguousarray(rnd, np.uint32).reshape(-1)
+        out = np.zeros((S, 6), np.uint32)
+        rc = lib().todhip_test_draw_table(self._h, _np_ptr(samp), _np_ptr(valid), n, _np_ptr(rnd), len(rnd), S, form, _np_ptr(out))
+        if rc not in (OK, EINVAL):
+            raise TodError(rc, "todhip_test_draw_table")
+        return rc, out
 
     def test_clique(self, m, edges, minimal_size=0xFFFFFFFF, gate=False):
         e = np.ascontiguousarray(np.asarray(edges, np.uint32).reshape(-1, 2))

@@ -9,8 +9,10 @@
 // Kernels
 //   K6  adjacency_kernel     (verify_prep.h) FillAdjacency (adjacency_ransac.cpp:127-172): one wave = 64 pair tests -> one
 //                            64-bit word of the physical and of the sample bit matrix via __ballot
-//   K7a draw_table_kernel    (verify_draw.h) drawIndexSampleHelper (sac_model_registration_graph.h:102-132) evaluated
-//                            speculatively from EVERY position of the rand() stream window, one wave each
+//   K7a draw_table_lane_kernel, draw_table_kernel (verify_draw.h, verify_draw_bits.h) drawIndexSampleHelper
+//                            (sac_model_registration_graph.h:102-132) evaluated speculatively from EVERY position of the rand()
+//                            stream window: one lane each for objects of up to 512 matches (bitsets of 2 or 8 words in the
+//                            lane's registers), one wave each beyond (bitsets of one or eight slices of 64 words)
 //   K7b chain_kernel         (verify_draw.h) getSamples (:141-168) x iterations: pointer chase through the table
 //   K8  eval_kernel          (verify_eval.h, verify_clique.h) selectWithinDistance (:171-269): 3-row AND + popcount, degree filter and the
 //                            maximum-clique gate (maximum_clique.cpp:286-369) on an LDS-resident induced graph
@@ -40,6 +42,7 @@
 #include "ctx.h"
 #include "depth_rescale.h"
 #include "verify_kernels.h"
+#include "verify_draw_bits.h"
 
 using namespace tod;
 

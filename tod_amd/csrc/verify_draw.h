@@ -1,6 +1,6 @@
 // The speculative draw table (K7a, drawIndexSampleHelper, sac_model_registration_graph.h:102-132) in its wave-per-position and
-// lane-per-position forms, and the chain walk through it (K7b, getSamples, :141-168).
-// Included by verify.hip inside its anonymous namespace, after verify_kernels.h and verify_launch.h.
+// lane-per-position forms with the routing between them, and the chain walk through it (K7b, getSamples, :141-168).
+// Included by verify.hip inside its anonymous namespace, after verify_kernels.h, verify_draw_bits.h and verify_launch.h.
 
 struct DrawArgs { ObjJob job; const uint32_t* rnd; uint32_t window_len, S; DrawEntry* table; };
 struct ChainArgs {
@@ -9,6 +9,10 @@ struct ChainArgs {
 };
 
 // ------------------------------------------------------------------------------------------------ K7a
+// Wave form: one wave per stream position, the bitsets distributed over its lanes. kSlices = 1 serves objects of up to 4096
+// matches (W <= 64: lane l holds word l), kSlices = kWPL any object; the scans, popcounts and predicated loads of the helpers are
+// per slice, so the one-slice form executes an eighth of them.
+template <int kSlices>
 __global__ __launch_bounds__(256) void draw_table_kernel(Slots<DrawArgs, kWideSlots> SL) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
   const ObjJob& job = SL.a[blockIdx.y].job;
@@ -17,8 +21,9 @@ __global__ __launch_bounds__(256) void draw_table_kernel(Slots<DrawArgs, kWideSl
   DrawEntry* const table = SL.a[blockIdx.y].table;
   const uint32_t s = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (s >= S) return;
-  const uint32_t W = job.W;
-  WaveBits VA;
+  const uint32_t W = job.W;                               // <= 64 kSlices
+  typedef WaveBitsT<kSlices> Bits;
+  Bits VA;
   wb_load(VA, job.valid, W);
   uint32_t nA = wb_count(VA);
   uint32_t pos = s, status = DRAW_FAIL, s0 = 0, s1 = 0, s2 = 0;
@@ -26,7 +31,7 @@ __global__ __launch_bounds__(256) void draw_table_kernel(Slots<DrawArgs, kWideSl
     if (pos >= window_len) { status = DRAW_OVERFLOW; break; }
     const uint32_t a = wb_select(VA, rnd[pos++] % nA);    // valid_samples[rand() % size], :111
     if (a >= job.n) break;                                // cannot happen; keeps every address in bounds
-    WaveBits VB = VA;
+    Bits VB = VA;
     wb_and(VB, job.samp + (size_t)a * W, W);              // set_intersection with the sample neighbours, :113-117
     uint32_t nB = wb_count(VB);
     bool ok = false;
@@ -35,7 +40,7 @@ __global__ __launch_bounds__(256) void draw_table_kernel(Slots<DrawArgs, kWideSl
       if (pos >= window_len) { status = DRAW_OVERFLOW; break; }
       b = wb_select(VB, rnd[pos++] % nB);
       if (b >= job.n) { nB = 0; break; }
-      WaveBits VC = VB;
+      Bits VC = VB;
       wb_and(VC, job.samp + (size_t)b * W, W);
       const uint32_t nC = wb_count(VC);
       if (nC > 0) {                                       // level "1 sample left": any pick succeeds
@@ -59,23 +64,21 @@ __global__ __launch_bounds__(256) void draw_table_kernel(Slots<DrawArgs, kWideSl
   }
 }
 
-// K7a for objects of at most 128 matches (W <= 2): ONE LANE per stream position instead of one wave -- the bitsets fit
-// two 64-bit registers, so a lane runs the helper's three levels on its own. Distractor objects (a few dozen random
-// matches, hopeless, burning their whole iteration budget and hundreds of failed attempts) are what makes the table
-// large, and they are small: 64 x fewer waves for the same table.
-__device__ __forceinline__ uint32_t nth_set_bit128(u64 w0, u64 w1, uint32_t n) {   // n-th set bit (ascending), n < popc
-  const uint32_t c0 = (uint32_t)__popcll(w0);
-  u64 w = w0; uint32_t base = 0;
-  if (n >= c0) { n -= c0; w = w1; base = 64u; }
-  uint32_t pos = 0;
+// Lane form, for objects of at most 64 WL matches (W <= WL): ONE LANE per stream position instead of one wave -- the three
+// levels' bitsets fit 3 x WL 64-bit registers, so a lane runs the helper's three levels on its own (verify_draw_bits.h: the n-th
+// set bit by running popcounts and a search inside the word, the removal of a failed pick by unrolled compares; no array is
+// indexed by a run-time value, so nothing goes to scratch). 64 x fewer waves for the same table, and each of them a few hundred
+// vector instructions where a wave of the other form executes ~1400 per attempt on a bitset that has a handful of words.
+// WL = 2: distractor objects (a few dozen random matches, hopeless, burning their whole iteration budget and hundreds of failed
+// attempts), which are what makes a table large. WL = 8: objects of up to 512 matches, the visible object of a frame among them.
+// A wave of this form lasts as long as its slowest lane's attempt; the entries are those of the wave form bit for bit.
+template <int WL>
+__device__ __forceinline__ void lane_and_row(u64 (&dst)[WL], const u64 (&src)[WL], const u64* __restrict__ row, uint32_t W) {
 #pragma unroll
-  for (uint32_t shift = 32; shift > 0; shift >>= 1) {
-    const uint32_t cnt = (uint32_t)__popcll((w >> pos) & ((1ull << shift) - 1ull));
-    if (n >= cnt) { n -= cnt; pos += shift; }
-  }
-  return base + pos;
+  for (int j = 0; j < WL; ++j) dst[j] = (uint32_t)j < W ? (src[j] & row[j]) : 0ull;   // W is uniform over the launch's slot
 }
-__global__ __launch_bounds__(256) void draw_table_small_kernel(Slots<DrawArgs, kWideSlots> SL) {
+template <int WL>
+__global__ __launch_bounds__(256) void draw_table_lane_kernel(Slots<DrawArgs, kWideSlots> SL) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
   const ObjJob& job = SL.a[blockIdx.y].job;
   const uint32_t* __restrict__ rnd = SL.a[blockIdx.y].rnd;
@@ -83,41 +86,62 @@ __global__ __launch_bounds__(256) void draw_table_small_kernel(Slots<DrawArgs, k
   DrawEntry* const table = SL.a[blockIdx.y].table;
   const uint32_t s = blockIdx.x * 256u + threadIdx.x;
   if (s >= S) return;
-  const uint32_t W = job.W;                                // 1 or 2
-  u64 a0 = job.valid[0], a1 = W > 1u ? job.valid[1] : 0ull;
-  uint32_t nA = (uint32_t)(__popcll(a0) + __popcll(a1));
+  const uint32_t W = job.W;                                 // 1 .. WL
+  u64 va[WL], vb[WL], vc[WL];
+#pragma unroll
+  for (int j = 0; j < WL; ++j) va[j] = (uint32_t)j < W ? job.valid[j] : 0ull;
+  uint32_t nA = tod_bits::count_bits(va);
   uint32_t pos = s, status = DRAW_FAIL, s0 = 0, s1 = 0, s2 = 0;
   while (nA > 0) {                                          // level "3 samples left"
     if (pos >= window_len) { status = DRAW_OVERFLOW; break; }
-    const uint32_t a = nth_set_bit128(a0, a1, rnd[pos++] % nA);   // valid_samples[rand() % size], :111
+    const uint32_t a = tod_bits::nth_set_bit(va, rnd[pos++] % nA);   // valid_samples[rand() % size], :111
     if (a >= job.n) break;                                  // cannot happen; keeps every address in bounds
-    u64 b0 = a0 & job.samp[(size_t)a * W], b1 = W > 1u ? (a1 & job.samp[(size_t)a * W + 1]) : 0ull;   // :113-117
-    uint32_t nB = (uint32_t)(__popcll(b0) + __popcll(b1));
+    lane_and_row(vb, va, job.samp + (size_t)a * W, W);      // set_intersection with the sample neighbours, :113-117
+    uint32_t nB = tod_bits::count_bits(vb);
     bool ok = false;
     uint32_t b = 0, c = 0;
     while (nB > 0) {                                        // level "2 samples left"
       if (pos >= window_len) { status = DRAW_OVERFLOW; break; }
-      b = nth_set_bit128(b0, b1, rnd[pos++] % nB);
+      b = tod_bits::nth_set_bit(vb, rnd[pos++] % nB);
       if (b >= job.n) { nB = 0; break; }
-      const u64 c0 = b0 & job.samp[(size_t)b * W], c1 = W > 1u ? (b1 & job.samp[(size_t)b * W + 1]) : 0ull;
-      const uint32_t nC = (uint32_t)(__popcll(c0) + __popcll(c1));
+      lane_and_row(vc, vb, job.samp + (size_t)b * W, W);
+      const uint32_t nC = tod_bits::count_bits(vc);
       if (nC > 0) {                                         // level "1 sample left": any pick succeeds
         if (pos >= window_len) { status = DRAW_OVERFLOW; break; }
-        c = nth_set_bit128(c0, c1, rnd[pos++] % nC);
+        c = tod_bits::nth_set_bit(vc, rnd[pos++] % nC);
         ok = true;
         break;
       }
-      if (b < 64u) b0 &= ~(1ull << b); else b1 &= ~(1ull << (b - 64u));   // std::remove of the failed pick, :125-128
+      tod_bits::clear_bit(vb, b);                           // std::remove of the failed pick, :125-128
       --nB;
     }
     if (status == DRAW_OVERFLOW) break;
     if (ok) { status = DRAW_OK; s0 = c; s1 = b; s2 = a; break; }   // samples_ is deepest-first, :118-121
-    if (a < 64u) a0 &= ~(1ull << a); else a1 &= ~(1ull << (a - 64u));
+    tod_bits::clear_bit(va, a);
     --nA;
   }
   DrawEntry e;
   e.status = status; e.consumed = pos - s; e.s0 = s0; e.s1 = s1; e.s2 = s2; e.pad = 0;
   table[s] = e;
+}
+
+// Which form builds an object's table: a plain function of its word count. The engine (PH_DRAW) and the test hook both ask here.
+// A hopeless object of 65-512 matches (hundreds of draws per attempt, a lane's wave as long as its slowest lane) stays with the
+// lane form, with no rule on the window's draws per iteration: the scene of six such objects of ~450 matches in
+// tools/time_verify_many_objects.py went from 8.73-8.75 ms per frame with one wave per position to 6.13-6.71 (median 6.14) with
+// one lane (five alternating turns, profiles/verify_draw.json), so the divergence costs less than the waves it replaces.
+enum DrawForm { DRAW_LANE2 = 0, DRAW_LANE8 = 1, DRAW_WAVE1 = 2, DRAW_WAVE8 = 3, DRAW_FORMS = 4 };
+inline DrawForm draw_form_of(uint32_t W) { return W <= 2u ? DRAW_LANE2 : W <= 8u ? DRAW_LANE8 : W <= 64u ? DRAW_WAVE1 : DRAW_WAVE8; }
+inline uint32_t draw_form_max_words(DrawForm f) { return f == DRAW_LANE2 ? 2u : f == DRAW_LANE8 ? 8u : f == DRAW_WAVE1 ? 64u : (uint32_t)kMaxWords; }
+inline void launch_draws(hipStream_t st, DrawForm f, const std::vector<DrawArgs>& v) {
+  auto per_wave = [](const DrawArgs& a) { return dim3((a.S + 3u) / 4u); };
+  auto per_lane = [](const DrawArgs& a) { return dim3((a.S + 255u) / 256u); };
+  switch (f) {
+    case DRAW_LANE2: launch_list<kWideSlots>(st, draw_table_lane_kernel<2>, v, 256, 0, 1, per_lane); break;
+    case DRAW_LANE8: launch_list<kWideSlots>(st, draw_table_lane_kernel<8>, v, 256, 0, 1, per_lane); break;
+    case DRAW_WAVE1: launch_list<kWideSlots>(st, draw_table_kernel<1>, v, 256, 0, 1, per_wave); break;
+    default: launch_list<kWideSlots>(st, draw_table_kernel<kWPL>, v, 256, 0, 1, per_wave); break;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ K7b

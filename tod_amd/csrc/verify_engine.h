@@ -67,10 +67,10 @@ struct Slot {
 struct Launches {
   std::vector<CopyArgs> copy_in, zero, copy_out;
   std::vector<InvArgs> inval, inval_after; std::vector<JobArgs> finite; std::vector<AdjArgs> adj; std::vector<PrepArgs> prep, prep_after;   // *_after: behind the growth kernels
-  std::vector<DrawArgs> draw, draw_small; std::vector<ChainArgs> chain;
+  std::vector<DrawArgs> draw[DRAW_FORMS]; std::vector<ChainArgs> chain;   // one draw list per form of the kernel (draw_form_of)
   // the rnd pointers of the draw lists are resolved at launch time: a later slot of the same tick may grow (move)
   // the shared stream buffer
-  std::vector<std::pair<StreamCache*, uint64_t>> draw_src, draw_small_src; std::vector<EvalArgs> eval_small, eval_big, eval_direct;
+  std::vector<std::pair<StreamCache*, uint64_t>> draw_src[DRAW_FORMS]; std::vector<EvalArgs> eval_small, eval_big, eval_direct;
   std::vector<GrowthArgs> growth;
   std::vector<SprintArgs> sprint; std::vector<StreamCache*> sprint_src;
   std::vector<ClusterArgs> cluster; std::vector<ClusterRescaledArgs> cluster_rescaled; std::vector<PrepSmallArgs> prep_small;
@@ -258,8 +258,9 @@ struct Engine {
       r.window_len = r.S + r.lookahead;
       SLOT_HIP(s.stream->ensure_device(s.abs_pos + r.consumed + r.window_len, st));
       SLOT_HIP(ws->table.reserve((size_t)r.S * sizeof(DrawEntry)));
-      (s.job.W <= 2u ? L.draw_small : L.draw).push_back({s.job, nullptr, r.window_len, r.S, ws->table.as<DrawEntry>()});
-      (s.job.W <= 2u ? L.draw_small_src : L.draw_src).push_back({s.stream, s.abs_pos + r.consumed});
+      const DrawForm form = draw_form_of(s.job.W);         // one lane per position up to 512 matches, one wave beyond
+      L.draw[form].push_back({s.job, nullptr, r.window_len, r.S, ws->table.as<DrawEntry>()});
+      L.draw_src[form].push_back({s.stream, s.abs_pos + r.consumed});
       ChainArgs ca = {ws->table.as<DrawEntry>(), r.S, r.want - r.got, r.attempts_carry, r.it_begin + r.got,
                       ws->iter_samples.as<uint32_t>(), ws->m_pos.as<uint32_t>(), &c->chain};
       L.chain.push_back(ca);
@@ -736,11 +737,10 @@ struct Engine {
       launch_either<kManySlots>(st, TOD_BOTH_FORMS(adjacency_kernel, AdjArgs, kManySlots), L.adj, many, stage, 2, ext_adj, 256u, 0u, true);
       launch_either<kManySlots>(st, TOD_BOTH_FORMS(round_prep_kernel, PrepArgs, kManySlots), L.prep, many, stage, 1, ext_rows, 256u, 0u, true);
     }
-    for (size_t i = 0; i < L.draw.size(); ++i) L.draw[i].rnd = L.draw_src[i].first->dev.as<uint32_t>() + L.draw_src[i].second;
-    for (size_t i = 0; i < L.draw_small.size(); ++i)
-      L.draw_small[i].rnd = L.draw_small_src[i].first->dev.as<uint32_t>() + L.draw_small_src[i].second;
-    launch_list<kWideSlots>(st, draw_table_kernel, L.draw, 256, 0, 1, [](const DrawArgs& a) { return dim3((a.S + 3u) / 4u); });
-    launch_list<kWideSlots>(st, draw_table_small_kernel, L.draw_small, 256, 0, 1, [](const DrawArgs& a) { return dim3((a.S + 255u) / 256u); });
+    for (int f = DRAW_FORMS - 1; f >= 0; --f) {              // (the wave forms first, as before)
+      for (size_t i = 0; i < L.draw[f].size(); ++i) L.draw[f][i].rnd = L.draw_src[f][i].first->dev.as<uint32_t>() + L.draw_src[f][i].second;
+      launch_draws(st, (DrawForm)f, L.draw[f]);
+    }
     {
       // dynamic LDS: the packed hop words of the largest window of the launch + the per-iteration start positions
       uint32_t lds = 0;
@@ -825,7 +825,7 @@ struct Engine {
   }
   void describe(char* what, size_t cap) const {
     snprintf(what, cap, "lookup %zu adj %zu prep %zu draw %zu+%zu chain %zu eval %zu+%zu growth %zu inval %zu sprint %zu", L.cluster.size() + L.cluster_rescaled.size(),
-             L.adj.size() + L.prep_small.size(), L.prep.size() + L.prep_small.size(), L.draw.size(), L.draw_small.size(), L.chain.size(), L.eval_small.size() + L.eval_direct.size(),
+             L.adj.size() + L.prep_small.size(), L.prep.size() + L.prep_small.size(), L.draw[DRAW_WAVE1].size() + L.draw[DRAW_WAVE8].size(), L.draw[DRAW_LANE2].size() + L.draw[DRAW_LANE8].size(), L.chain.size(), L.eval_small.size() + L.eval_direct.size(),
              L.eval_big.size(), L.growth.size(), L.inval.size(), L.sprint.size());
   }
   struct Lane {

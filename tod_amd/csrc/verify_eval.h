@@ -28,8 +28,9 @@ struct EvalArgs {
 
 // The gate of one hypothesis (sac_model_registration_graph.h:219-265): induced sample sub-graph of F, degree test,
 // maximum clique. Returns the consensus count to report (cnt, 0 = rejected, INT_MIN = error).
-template <bool kExt, bool kWide>
-__device__ __forceinline__ int32_t gate_eval(const EvalArgs& A, const WaveBits& F, uint32_t m, uint32_t it, uint32_t cnt,
+// F carries the slices its caller's objects need (eval_kernel: one for W <= 64 words, kWPL for any object).
+template <bool kExt, bool kWide, int kSlices>
+__device__ __forceinline__ int32_t gate_eval(const EvalArgs& A, const WaveBitsT<kSlices>& F, uint32_t m, uint32_t it, uint32_t cnt,
                                              unsigned char* lds_raw, uint16_t* stack) {
   const uint32_t l = lane_id();
   const ObjJob& job = A.job;
@@ -47,7 +48,7 @@ __device__ __forceinline__ int32_t gate_eval(const EvalArgs& A, const WaveBits& 
   // F in ascending order (:219) -> graph index = rank (:241-243)
   uint32_t base = 0;
 #pragma unroll
-  for (int j = 0; j < kWPL; ++j) {
+  for (int j = 0; j < kSlices; ++j) {
     const uint32_t c = (uint32_t)__popcll(F.w[j]);
     const uint32_t incl = wave_incl_scan(c);
     u64 w = F.w[j];
@@ -214,7 +215,8 @@ __device__ __forceinline__ int32_t gate_eval(const EvalArgs& A, const WaveBits& 
 
 // launched with 64 threads; the bound is deliberately larger so that hipcc keeps __syncthreads() as a real,
 // convergent s_barrier (with a 64-thread bound it drops the barrier and may split the lanes of the wave)
-// kWide = false: objects of up to 512 matches (job.W <= 8), the launch's every slot; true: any size
+// kWide = false: objects of up to 512 matches (job.W <= 8), the launch's every slot, so P and F are one slice of 64 words;
+// true: any size, eight slices
 template <bool kWide, class H = Slots<EvalArgs>>
 __global__ __launch_bounds__(128) void eval_kernel(H SL) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
@@ -238,7 +240,8 @@ __global__ __launch_bounds__(128) void eval_kernel(H SL) {
     }
     // common physical neighbours of the three samples (:178-184); the geometric test of :197 is
     // `finite < +inf` because threshold_ is DBL_MAX (D2), i.e. a finiteness test
-    WaveBits P;
+    typedef WaveBitsT<kWide ? kWPL : 1> Bits;
+    Bits P;
     wb_load(P, job.phys + (size_t)s0 * W, W);
     wb_and(P, job.phys + (size_t)s1 * W, W);
     wb_and(P, job.phys + (size_t)s2 * W, W);
@@ -248,7 +251,7 @@ __global__ __launch_bounds__(128) void eval_kernel(H SL) {
     int32_t result = (int32_t)cnt;
     uint32_t m_diag = 0;
     if (cnt > kGateMinimal && A.stop_level != 2u) {        // :203-205
-      WaveBits F = P;
+      Bits F = P;
       wb_set(F, s0); wb_set(F, s1); wb_set(F, s2);
       wb_and(F, job.deg7, W);                              // :211-213
       const uint32_t m = wb_count(F);

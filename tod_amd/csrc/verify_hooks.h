@@ -117,6 +117,45 @@ int todhip_test_consensus(todhip_ctx* ctx, const float* train, const float* quer
   return TODHIP_OK;
 }
 
+// Test hook: the speculative draw table of one object alone -- the S entries that the attempts starting at positions 0 .. S - 1 of
+// the window_len stream words rnd leave, for the n x W sample bit matrix samp and the W valid words (host arrays; W = ceil(n / 64);
+// bits of valid at or beyond n end an attempt as the kernels' in-bounds guard says). form picks the kernel: 0 = the engine's
+// routing (draw_form_of), 1 = one lane per position, 2 = one wave per position with one slice, 3 = with eight slices, 4 = one lane
+// per position with eight words a lane whatever W (form 1 gives an object of one or two words the two-word kernel, as the engine
+// does; 4 runs the eight-word one on it); a form that cannot hold the object's W words is TODHIP_EINVAL. entries_out: S x 6
+// words (DrawEntry).
+int todhip_test_draw_table(todhip_ctx* ctx, const uint64_t* samp, const uint64_t* valid, uint32_t n, const uint32_t* rnd,
+                           uint32_t window_len, uint32_t S, uint32_t form, uint32_t* entries_out) {
+  if (!ctx || !samp || !valid || !rnd || !entries_out || n == 0 || n > (uint32_t)kMaxWords * 64u || S == 0 || S > (1u << 20) ||
+      window_len == 0 || window_len > (1u << 24) || form > 4u)
+    return TODHIP_EINVAL;
+  const uint32_t W = (n + 63u) / 64u;
+  DrawForm f = draw_form_of(W);
+  if (form == 1u) f = W <= 2u ? DRAW_LANE2 : DRAW_LANE8;
+  if (form == 2u) f = DRAW_WAVE1;
+  if (form == 3u) f = DRAW_WAVE8;
+  if (form == 4u) f = DRAW_LANE8;
+  if (W > draw_form_max_words(f)) return TODHIP_EINVAL;
+  TOD_HIP(hipSetDevice(ctx->device));
+  VerifyWs* ws = ws_of(ctx);
+  hipStream_t st = ctx->stream;
+  TOD_HIP(ws->samp.reserve((size_t)n * W * 8)); TOD_HIP(ws->bits.reserve((size_t)8 * W * 8));
+  TOD_HIP(ws->iter_samples.reserve((size_t)window_len * 4));            // (the stream words)
+  TOD_HIP(ws->table.reserve((size_t)S * sizeof(DrawEntry)));
+  TOD_HIP(hipMemcpyAsync(ws->samp.p, samp, (size_t)n * W * 8, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->bits.as<u64>() + W, valid, (size_t)W * 8, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->iter_samples.p, rnd, (size_t)window_len * 4, hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemsetAsync(ws->table.p, 0xFF, (size_t)S * sizeof(DrawEntry), st));   // an entry nobody wrote does not pass for one
+  ObjJob job;
+  std::memset(&job, 0, sizeof(job));
+  job.n = n; job.W = W; job.samp = ws->samp.as<u64>(); job.valid = ws->bits.as<u64>() + W;
+  launch_draws(st, f, std::vector<DrawArgs>{{job, ws->iter_samples.as<uint32_t>(), window_len, S, ws->table.as<DrawEntry>()}});
+  TOD_HIP(hipGetLastError());
+  TOD_HIP(hipMemcpyAsync(entries_out, ws->table.p, (size_t)S * sizeof(DrawEntry), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));
+  return TODHIP_OK;
+}
+
 // Test hook: the depth lookup of cluster_frame_kernel alone -- z of the keypoint's 3D point for n pixel positions, out of a dH x dW
 // depth image seen as rescale_depth's H x W result (equal sizes: the plain load). A position outside the H x W image is what the
 // cluster kernel refuses (ClusterCtl::error 1, TODHIP_ERANGE from the verify calls): its z_out is left as it was and the call returns

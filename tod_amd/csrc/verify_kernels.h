@@ -143,44 +143,54 @@ __device__ __forceinline__ uint32_t nth_set_bit(u64 w, uint32_t n) {
   return (uint32_t)__ffsll((long long)w) - 1u;
 }
 
-// A bitset over the n matches, distributed over the wave: lane l holds words l, l + 64, ...
-struct WaveBits {
-  u64 w[kWPL];
+// A bitset over the n matches, distributed over the wave: lane l holds words l, l + 64, ... of kSlices x 64 words. kWPL slices
+// hold any object; a kernel that knows its objects to be smaller carries fewer (one slice: W <= 64 words, n <= 4096 matches) and
+// every helper below then loops over those alone.
+template <int kSlices = kWPL>
+struct WaveBitsT {
+  u64 w[kSlices];
 };
-__device__ __forceinline__ void wb_load(WaveBits& b, const u64* p, uint32_t W) {
+typedef WaveBitsT<> WaveBits;
+template <int kSlices>
+__device__ __forceinline__ void wb_load(WaveBitsT<kSlices>& b, const u64* p, uint32_t W) {
   const uint32_t l = lane_id();
 #pragma unroll
-  for (int j = 0; j < kWPL; ++j) b.w[j] = (j * 64u + l) < W ? p[j * 64u + l] : 0ull;
+  for (int j = 0; j < kSlices; ++j) b.w[j] = (j * 64u + l) < W ? p[j * 64u + l] : 0ull;
 }
-__device__ __forceinline__ void wb_and(WaveBits& b, const u64* p, uint32_t W) {
+template <int kSlices>
+__device__ __forceinline__ void wb_and(WaveBitsT<kSlices>& b, const u64* p, uint32_t W) {
   const uint32_t l = lane_id();
 #pragma unroll
-  for (int j = 0; j < kWPL; ++j) b.w[j] &= (j * 64u + l) < W ? p[j * 64u + l] : 0ull;
+  for (int j = 0; j < kSlices; ++j) b.w[j] &= (j * 64u + l) < W ? p[j * 64u + l] : 0ull;
 }
-__device__ __forceinline__ uint32_t wb_count(const WaveBits& b) {
+template <int kSlices>
+__device__ __forceinline__ uint32_t wb_count(const WaveBitsT<kSlices>& b) {
   uint32_t c = 0;
 #pragma unroll
-  for (int j = 0; j < kWPL; ++j) c += (uint32_t)__popcll(b.w[j]);
+  for (int j = 0; j < kSlices; ++j) c += (uint32_t)__popcll(b.w[j]);
   return wave_sum(c);
 }
-__device__ __forceinline__ void wb_clear(WaveBits& b, uint32_t v) {
+template <int kSlices>
+__device__ __forceinline__ void wb_clear(WaveBitsT<kSlices>& b, uint32_t v) {
   const uint32_t word = v >> 6, l = lane_id();
 #pragma unroll
-  for (int j = 0; j < kWPL; ++j)
+  for (int j = 0; j < kSlices; ++j)
     if (word == j * 64u + l) b.w[j] &= ~(1ull << (v & 63u));
 }
-__device__ __forceinline__ void wb_set(WaveBits& b, uint32_t v) {
+template <int kSlices>
+__device__ __forceinline__ void wb_set(WaveBitsT<kSlices>& b, uint32_t v) {
   const uint32_t word = v >> 6, l = lane_id();
 #pragma unroll
-  for (int j = 0; j < kWPL; ++j)
+  for (int j = 0; j < kSlices; ++j)
     if (word == j * 64u + l) b.w[j] |= (1ull << (v & 63u));
 }
 // index of the idx-th set bit (ascending); idx < count and idx wave-uniform
-__device__ __forceinline__ uint32_t wb_select(const WaveBits& b, uint32_t idx) {
+template <int kSlices>
+__device__ __forceinline__ uint32_t wb_select(const WaveBitsT<kSlices>& b, uint32_t idx) {
   idx = uni(idx);
   uint32_t result = 0xFFFFFFFFu;
 #pragma unroll
-  for (int j = 0; j < kWPL; ++j) {
+  for (int j = 0; j < kSlices; ++j) {
     const uint32_t c = (uint32_t)__popcll(b.w[j]);
     const uint32_t incl = wave_incl_scan(c);
     const uint32_t total = uni(__shfl(incl, 63));

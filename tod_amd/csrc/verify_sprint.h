@@ -440,10 +440,8 @@ __global__ __launch_bounds__(kSprintThreads) void sprint_kernel(Slots<SprintArgs
                 const u64 P = uni64(s_phys[t0] & s_phys[t1] & s_phys[t2] & valid & finite);
                 const u64 Fu = (P | (1ull << t0) | (1ull << t1) | (1ull << t2)) & deg7;
                 const uint32_t cu = (uint32_t)__popcll(P) + 3u;
-                WaveBits F;
-#pragma unroll
-                for (int q = 0; q < kWPL; ++q) F.w[q] = 0ull;
-                if (l == 0u) F.w[0] = Fu;
+                WaveBitsT<1> F;                                        // one word in lane 0: one slice
+                F.w[0] = l == 0u ? Fu : 0ull;
                 EvalArgs E;
                 E.job = job; E.iter_samples = nullptr; E.it_begin = 0; E.it_end = 0; E.counts = nullptr; E.gate_m = nullptr;
                 E.work = nullptr; E.status = A.status; E.deferred = nullptr; E.stacks = gstack; E.stack_cap = kSprintStackCap;
