@@ -369,7 +369,17 @@ void todhip_rng_seed(todhip_rng*, uint32_t seed);   /* srand(seed); the referenc
 /* Replaces GuessGenerator::process (GuessGenerator.cpp:127-250) and everything under src/common.
  * kp_xy: nq x 2 keypoint pixels (cv::KeyPoint::pt); cloud_xyz: H x W x 3 f32 organised cloud (NaN = no depth);
  * matches in CSR form as produced by todhip_match; spans: per object index (imgIdx).
- * poses: capacity *n_poses in, count out. inlier_kp: capacity *n_inlier_kp in, count out. */
+ * poses: capacity *n_poses in, count out. inlier_kp: capacity *n_inlier_kp in, count out.
+ * Range of the pose solve: R comes from a float 3x3 SVD of the inliers' correlation matrix H = sum (train - c_train)(query - c_query)^T.
+ * Supported: every H whose entries, rounded to float, are finite -- any rank (planar and collinear inliers included), any ratio of
+ * its singular values. R is then a rotation to 8 * 2^-23 and lies within 16 kappa 2^-23 of the float64 Kabsch solution,
+ * kappa = s1 / (s2 +- s3). Data in metres gives entries of about 1e-6 .. 1e3. Between 2^-32 and 2^40 the SVD works on H as it is;
+ * the one place where that alone would leave the float range (the product of two squared column norms, from s1 s2 = 1.8e19 on) takes
+ * its root factor by factor. An H whose largest entry lies outside is first scaled by a power of two, because the squares of its
+ * entries would overflow (beyond 1.8e19) or, for the rounding residue that stands in for a zero singular value, go denormal (a
+ * largest entry below 1e-12). tests/test_verify_pose_gpu.py pins this through todhip_test_kabsch at the scales 1e-30, 1e-12,
+ * 1e-8 .. 1e12, 1e30, a largest entry of 0.9 FLT_MAX, and on both sides of s1 s2 = 1.8e19. An H with an infinite or NaN entry
+ * gives NaN. */
 int todhip_verify(todhip_ctx*, const float* kp_xy, uint32_t nq, const float* cloud_xyz, uint32_t H, uint32_t W,
                   const uint32_t* row_ptr, const todhip_dmatch* matches, const float* matches_xyz,
                   const float* spans, uint32_t n_objs, const todhip_verify_params*, todhip_rng* rng,
@@ -792,6 +802,11 @@ int todhip_test_clique_gate(todhip_ctx*, uint32_t m, const uint32_t* edges, uint
  * matches is TODHIP_EINVAL. */
 int todhip_test_draw_table(todhip_ctx*, const uint64_t* samp, const uint64_t* valid, uint32_t n, const uint32_t* rnd,
                            uint32_t window_len, uint32_t S, uint32_t form, uint32_t* entries_out);
+/* The pose solve of the verifier's refinement alone (the tail of estimateRigidTransformationSVD, sac_model_registration_graph.h:330-346),
+ * one GPU lane per case: Hd = n_cases correlation matrices (9 doubles each, row-major, rounded to float as the verifier rounds its
+ * double sums), C = n_cases centroid pairs {train xyz, query xyz}; R (n_cases x 9) and T (n_cases x 3) map query -> train, i.e. the
+ * pose before todhip_verify inverts it. Host arrays. The range is that of todhip_verify (see there). */
+int todhip_test_kabsch(todhip_ctx*, uint32_t n_cases, const double* Hd, const float* C, float* R, float* T);
 
 /* FillAdjacency + selectWithinDistance (sac_model_registration_graph.h:171-269) for given sample triples
  * (samples_ order): counts[t] = consensus size, 0 when the clique gate rejects. stop_level 1 skips the clique

@@ -254,17 +254,36 @@ static inline P3 mulMV(const M33& R, const P3& p) { /* Matx33f * Vec3f: float ac
 
 /* 3x3 one-sided Jacobi SVD in float: A = U diag(w) Vt, w descending.
  * Stand-in for cv::SVD on a CV_32F 3x3 (sac_model_registration_graph.h:333), which is third-party
- * arithmetic absent from the reference tree: PARITY UNPINNED, absorbed by the 1e-3 pose tolerance. */
+ * arithmetic absent from the reference tree: PARITY UNPINNED, absorbed by the 1e-3 pose tolerance. Its ACCURACY is pinned
+ * all the same: against a float64 Kabsch (numpy.linalg.svd) within 16 kappa 2^-23, on general rotations, rotations by pi,
+ * reflections, rank-deficient and equal-spectrum matrices and both ends of the float range, in tests/test_pose_cases_cpu.py
+ * (this file) and tests/test_verify_pose_gpu.py (the kernels). */
 static void svd3(const float Ain[3][3], float U[3][3], float w[3], float Vt[3][3]) {
   float A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   std::memcpy(A, Ain, sizeof(A));
+  /* Far from 1 the squares below leave the float range (entries beyond 1.8e19) or go denormal (the rounding residue of a rank-deficient
+   * A, about 1e-7 of its largest entry, below 1e-12): such an A is first brought to a largest entry in [0.5, 1) by a power of two, in
+   * two exact steps that stay inside the range. U and Vt do not depend on the scale; w is then the scaled matrix's (its callers use
+   * no w). Between 2^-32 and 2^40, where all data in metres lies, nothing is scaled and no bit moves. */
+  float amax = 0.f;
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) amax = std::fabs(A[i][j]) > amax ? std::fabs(A[i][j]) : amax;
+  if (amax > 0.f && amax <= FLT_MAX && (amax < 2.3283064e-10f || amax > 1.0995116e12f)) {
+    int e;
+    std::frexp(amax, &e);
+    const float s1 = std::ldexp(1.f, -(e / 2)), s2 = std::ldexp(1.f, -(e - e / 2));
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i][j] = A[i][j] * s1 * s2;
+  }
   for (int sweep = 0; sweep < 30; ++sweep) {
     bool rotated = false;
     for (int p = 0; p < 2; ++p)
       for (int q = p + 1; q < 3; ++q) {
         float alpha = 0, beta = 0, gamma = 0;
         for (int i = 0; i < 3; ++i) { alpha += A[i][p] * A[i][p]; beta += A[i][q] * A[i][q]; gamma += A[i][p] * A[i][q]; }
-        if (std::fabs(gamma) <= FLT_EPSILON * std::sqrt(alpha * beta) || gamma == 0.f) continue;
+        /* alpha * beta leaves the float range long before alpha and beta do (sigma1 * sigma2 beyond 1.8e19, or below 1e-19):
+         * there the product's root is taken factor by factor; a finite non-zero product keeps the one root it always had */
+        const float ab = alpha * beta;
+        const float lim = (ab != 0.f && ab <= FLT_MAX) ? FLT_EPSILON * std::sqrt(ab) : FLT_EPSILON * std::sqrt(alpha) * std::sqrt(beta);
+        if (std::fabs(gamma) <= lim || gamma == 0.f) continue;
         rotated = true;
         float zeta = (beta - alpha) / (2.f * gamma);
         float t = (zeta >= 0.f ? 1.f : -1.f) / (std::fabs(zeta) + std::sqrt(1.f + zeta * zeta));
@@ -421,6 +440,11 @@ class GraphRegistrationModel {
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) Hd[r][c] += (double)a.v[r] * (double)b.v[c];
     }
+    kabsch_solve(Hd, ct, cq, R, T);
+    return true;
+  }
+  /* the tail of estimateRigidTransformationSVD, :330-346, from the float conversion of H on (orc_kabsch_solve calls it alone) */
+  static void kabsch_solve(const double Hd[3][3], const P3& ct, const P3& cq, M33& R, P3& T) {
     float H[3][3], U[3][3], w[3], Vt[3][3];
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) H[r][c] = (float)Hd[r][c];
     svd3(H, U, w, Vt);
@@ -434,7 +458,6 @@ class GraphRegistrationModel {
       }
     P3 rc = mulMV(R, cq);
     T = sub3(ct, rc);
-    return true;
   }
 
 
@@ -797,6 +820,14 @@ int orc_cluster_kabsch(const orc_cluster* h, const uint32_t* idx, uint32_t n, fl
   if (!m.kabsch(v, R, T)) return -1;
   for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R9[3 * r + c] = R.m[r][c]; T3[r] = T.v[r]; }
   return 0;
+}
+void orc_kabsch_solve(const double* Hd9, const float* C6, float* R9, float* T3) {
+  double Hd[3][3];
+  for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Hd[r][c] = Hd9[3 * r + c];
+  P3 ct = {{C6[0], C6[1], C6[2]}}, cq = {{C6[3], C6[4], C6[5]}};
+  M33 R; P3 T;
+  GraphRegistrationModel::kabsch_solve(Hd, ct, cq, R, T);
+  for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) R9[3 * r + c] = R.m[r][c]; T3[r] = T.v[r]; }
 }
 
 /* GuessGenerator::process, GuessGenerator.cpp:127-250 (+ ClusterPerObject, adjacency_ransac.cpp:176-205) */

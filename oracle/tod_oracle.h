@@ -89,6 +89,8 @@ uint32_t orc_cluster_ransac(orc_cluster*, float sensor_error, uint32_t n_iterati
 void orc_cluster_invalidate_kp(orc_cluster*, const uint32_t* kp, uint32_t n_kp);
 /* Kabsch on a list of match indices (estimateRigidTransformationSVD); query->training */
 int orc_cluster_kabsch(const orc_cluster*, const uint32_t* idx, uint32_t n, float* R9, float* T3);
+/* its tail alone, from the float conversion of H on: Hd9 the correlation matrix (row-major doubles), C6 = {c_train, c_query} */
+void orc_kabsch_solve(const double* Hd9, const float* C6, float* R9, float* T3);
 
 /* ---- stage C, whole frame (GuessGenerator::process) ------------------------------------ */
 int orc_verify(const float* kp_xy, uint32_t nq, const float* cloud_xyz, uint32_t H, uint32_t W,

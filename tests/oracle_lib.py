@@ -226,6 +226,18 @@ class Cluster:
         return rc, R.reshape(3, 3).copy(), T.copy()
 
 
+def kabsch_solve(Hd, Cc):
+    """orc_kabsch_solve per case: Hd f64 [n, 3, 3], Cc f32 [n, 6] (train, query centroids) -> R f32 [n, 3, 3], T f32 [n, 3]."""
+    Hd = np.ascontiguousarray(Hd, np.float64).reshape(-1, 9)
+    Cc = np.ascontiguousarray(Cc, np.float32).reshape(-1, 6)
+    R = np.zeros((len(Hd), 9), np.float32)
+    T = np.zeros((len(Hd), 3), np.float32)
+    fn = lib().orc_kabsch_solve
+    for i in range(len(Hd)):
+        fn(_p(Hd[i], C.c_double), _p(Cc[i], C.c_float), _p(R[i], C.c_float), _p(T[i], C.c_float))
+    return R.reshape(-1, 3, 3), T
+
+
 # ------------------------------------------------------------------------------------------ stage C whole frame
 def verify(kp_xy, cloud, row_ptr, matches, matches_xyz, spans_per_obj, min_inliers, n_iter, err, rng,
            max_poses=64):

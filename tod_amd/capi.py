@@ -100,7 +100,7 @@ EXPORTS = [
     "todhip_test_depth_lookup", "todhip_pipeline_set_depth_size", "todhip_pipeline_submit_masked", "todhip_pipeline_submit_masked_device",
     "todhip_model_add_observations_device",
     "todhip_match_l2_radius", "todhip_match_l2_radius_device",
-    "todhip_test_draw_table",
+    "todhip_test_draw_table", "todhip_test_kabsch",
 ]
 
 MAX_TRAIN_BATCH_VIEWS = 64
@@ -203,6 +203,8 @@ def lib():
         if hasattr(L, "todhip_test_draw_table"):                      # (as above)
             L.todhip_test_draw_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
             L.todhip_test_draw_table.restype = C.c_int
+        if hasattr(L, "todhip_test_kabsch"):                          # (as above)
+            L.todhip_test_kabsch.argtypes, L.todhip_test_kabsch.restype = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4, C.c_int
         _lib = L
     return _lib
 
@@ -700,6 +702,17 @@ class Context:
         if rc not in (OK, EINVAL):
             raise TodError(rc, "todhip_test_draw_table")
         return rc, out
+
+    def test_kabsch(self, Hd, Cc):
+        """kabsch_solve alone (todhip_test_kabsch): Hd f64 [n, 3, 3] correlation matrices, Cc f32 [n, 6] centroids (train, query).
+        Returns R f32 [n, 3, 3], T f32 [n, 3], query -> train, before the inversion."""
+        Hd = np.ascontiguousarray(Hd, np.float64).reshape(-1, 9)
+        Cc = np.ascontiguousarray(Cc, np.float32).reshape(-1, 6)
+        assert len(Hd) == len(Cc)
+        R = np.zeros((len(Hd), 9), np.float32)
+        T = np.zeros((len(Hd), 3), np.float32)
+        _check(lib().todhip_test_kabsch(self._h, len(Hd), _np_ptr(Hd), _np_ptr(Cc), _np_ptr(R), _np_ptr(T)), "todhip_test_kabsch")
+        return R.reshape(-1, 3, 3), T
 
     def test_clique(self, m, edges, minimal_size=0xFFFFFFFF, gate=False):
         e = np.ascontiguousarray(np.asarray(edges, np.uint32).reshape(-1, 2))

@@ -8,13 +8,29 @@
 __device__ void svd3(const float Ain[3][3], float U[3][3], float w[3], float Vt[3][3]) {
   float A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i][j] = Ain[i][j];
+  // Far from 1 the squares below leave the float range (entries beyond 1.8e19) or go denormal (the rounding residue of a rank-deficient
+  // A, about 1e-7 of its largest entry, below 1e-12): such an A is first brought to a largest entry in [0.5, 1) by a power of two, in
+  // two exact steps that stay inside the range. U and Vt do not depend on the scale; w is then the scaled matrix's (kabsch_solve uses
+  // no w). Between 2^-32 and 2^40, where all data in metres lies, nothing is scaled and no bit moves.
+  float amax = 0.f;
+  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) amax = fabsf(A[i][j]) > amax ? fabsf(A[i][j]) : amax;
+  if (amax > 0.f && amax <= 3.4028235e+38f && (amax < 2.3283064e-10f || amax > 1.0995116e12f)) {
+    int e;
+    frexpf(amax, &e);
+    const float s1 = ldexpf(1.f, -(e / 2)), s2 = ldexpf(1.f, -(e - e / 2));
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) A[i][j] = A[i][j] * s1 * s2;
+  }
   for (int sweep = 0; sweep < 30; ++sweep) {
     bool rotated = false;
     for (int p = 0; p < 2; ++p)
       for (int q = p + 1; q < 3; ++q) {
         float alpha = 0, beta = 0, gamma = 0;
         for (int i = 0; i < 3; ++i) { alpha += A[i][p] * A[i][p]; beta += A[i][q] * A[i][q]; gamma += A[i][p] * A[i][q]; }
-        if (fabsf(gamma) <= 1.1920929e-07f * sqrtf(alpha * beta) || gamma == 0.f) continue;
+        // alpha * beta leaves the float range long before alpha and beta do (sigma1 * sigma2 beyond 1.8e19, or below 1e-19): there the
+        // product's root is taken factor by factor; a finite non-zero product keeps the one root it always had, bit for bit
+        const float ab = alpha * beta;
+        const float lim = (ab != 0.f && ab <= 3.4028235e+38f) ? 1.1920929e-07f * sqrtf(ab) : 1.1920929e-07f * sqrtf(alpha) * sqrtf(beta);
+        if (fabsf(gamma) <= lim || gamma == 0.f) continue;
         rotated = true;
         const float zeta = (beta - alpha) / (2.f * gamma);
         const float t = (zeta >= 0.f ? 1.f : -1.f) / (fabsf(zeta) + sqrtf(1.f + zeta * zeta));

@@ -13,9 +13,43 @@ __global__ __launch_bounds__(256) void depth_lookup_kernel(LookupArgs a) {
   a.z[q] = a.rescale ? rescaled_depth_at(a.depth, a.is_u16, a.geom, (uint32_t)col, (uint32_t)row)
                      : depth_metres(a.depth, a.is_u16, (size_t)row * a.W + col);
 }
+// the kernel of todhip_test_kabsch: one lane per case
+__global__ __launch_bounds__(64) void kabsch_test_kernel(uint32_t n, const double* Hd, const float* C, float* R, float* T) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  double h[9]; float c[6], r[9], t[3];
+  for (int k = 0; k < 9; ++k) h[k] = Hd[(size_t)i * 9 + k];
+  for (int k = 0; k < 6; ++k) c[k] = C[(size_t)i * 6 + k];
+  kabsch_solve(h, c, r, t);
+  for (int k = 0; k < 9; ++k) R[(size_t)i * 9 + k] = r[k];
+  for (int k = 0; k < 3; ++k) T[(size_t)i * 3 + k] = t[k];
+}
 }  // namespace
 
 extern "C" {
+
+// Test hook: kabsch_solve (verify_growth.h) alone, as growth_kernel and sprint_kernel call it -- n_cases correlation matrices Hd
+// (n x 9 doubles, row-major) and centroid pairs C (n x 6: train, query) give R (n x 9) and T (n x 3), query -> train, before the
+// inversion. Host arrays. Whole frames cannot produce the matrices that try an SVD (rank deficient, equal singular values, the ends
+// of the float range); this can.
+int todhip_test_kabsch(todhip_ctx* ctx, uint32_t n_cases, const double* Hd, const float* C, float* R, float* T) {
+  if (!ctx || !Hd || !C || !R || !T || n_cases == 0 || n_cases > (1u << 20)) return TODHIP_EINVAL;
+  TOD_HIP(hipSetDevice(ctx->device));
+  VerifyWs* ws = ws_of(ctx);
+  hipStream_t st = ctx->stream;
+  const size_t n = n_cases;
+  TOD_HIP(ws->phys.reserve(n * 9 * sizeof(double))); TOD_HIP(ws->train.reserve(n * 6 * sizeof(float)));
+  TOD_HIP(ws->query.reserve(n * 9 * sizeof(float))); TOD_HIP(ws->kpxy.reserve(n * 3 * sizeof(float)));
+  TOD_HIP(hipMemcpyAsync(ws->phys.p, Hd, n * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+  TOD_HIP(hipMemcpyAsync(ws->train.p, C, n * 6 * sizeof(float), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(kabsch_test_kernel, dim3((n_cases + 63u) / 64u), dim3(64), 0, st, n_cases, ws->phys.as<double>(),
+                     ws->train.as<float>(), ws->query.as<float>(), ws->kpxy.as<float>());
+  TOD_HIP(hipGetLastError());
+  TOD_HIP(hipMemcpyAsync(R, ws->query.p, n * 9 * sizeof(float), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipMemcpyAsync(T, ws->kpxy.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  TOD_HIP(hipStreamSynchronize(st));
+  return TODHIP_OK;
+}
 
 int todhip_test_adjacency(todhip_ctx* ctx, const float* train, const float* query, const float* kpxy, uint32_t n,
                           float span, float err, uint64_t* phys, uint64_t* samp) {
