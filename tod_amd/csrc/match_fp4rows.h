@@ -201,12 +201,23 @@ __device__ __forceinline__ uint32_t pair_or(const mfma_f32x16& acc) {
 // Block FIELD of a pair goes on: its part is unpacked from its field (exact: the dot products of its first two MFMAs) and completes as
 // fp4rows_block_test_part's block does -- the tails of its own step from the copy, its query's tail words, the test against the
 // query's own thr, the walk. Unpacking keeps nothing for this path in registers across the fast path.
+// The exchange of distance bounds between tiles happens here too, and only here: the paired fast path tests at the launch's radius
+// and never reads thr, and a list changes nowhere else, so a periodic exchange_bounds in the loop bought the fast path nothing -- about
+// 60 vector instructions, six sc1 loads the next trip waited for, and ten v_mov_b32 at every back edge for the seen[] it kept across
+// the loop. The query's bound is loaded with the tails (one latency), applied in front of the test as exchange_bounds applies it (<=:
+// a smaller row index elsewhere may still win a tie) and the list's own bound published behind it: never later than a periodic
+// exchange would, and what is read is never staler. The tile-local row of the block (lane_row_base of its own step) is built here as
+// well, from the wave-uniform step and an h made opaque as qi is: the loop carries neither.
 template <int K, int FIELD>
 __device__ __forceinline__ void fp4rows_pair_complete(const mfma_f32x16& packed, int bias, const Fp4StepLoader& rows, uint32_t own_step,
                                                       const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, const Fp4Consts& kc,
-                                                      float& thr, uint32_t r_lane, uint32_t n_lim, uint32_t (&best)[K], uint32_t& n_pass) {
+                                                      float& thr, uint32_t n_lim, uint32_t (&best)[K], uint32_t& n_pass, uint32_t* bound) {
   ++n_pass;
   asm volatile("" : "+v"(qi));
+  asm volatile("" : "+v"(h));
+  const uint32_t r_lane = lane_row_base(own_step, h);
+  uint32_t* my_bound = bound + (qi < nq ? qi : nq - 1u);
+  const uint32_t seen = __hip_atomic_load(my_bound, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   mfma_f32x16 acc;
 #pragma unroll
   for (int i = 0; i < 16; ++i) acc[i] = (float)PairPack::unpack((uint32_t)__float_as_int(packed[i]), FIELD, bias);
@@ -217,7 +228,10 @@ __device__ __forceinline__ void fp4rows_pair_complete(const mfma_f32x16& packed,
 #pragma unroll
   for (int s = 2; s < 4; ++s)
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(tail[s - 2], expand_word(packed_word(p, s), kc), acc, 4, 4, 0, 0, 0, 0);
+  if (seen != 0xFFFFFFFFu) thr = fmaxf(thr, thr_of_limit(seen + 1u));
   mfma_block_test<K, false, true>(acc, thr, r_lane, n_lim, best);
+  const uint32_t worst_d = best[K - 1] >> kLocalBits;
+  if (worst_d < kNoLimit && worst_d < seen) atomicMin(my_bound, worst_d);
   asm("" : "+v"(thr));        // (a register of its own: see fp4rows_block_test_part)
 }
 // The test of a pair (blocks ta and ta + 1 of own_step; qi: this lane's query of block ta). n_pass counts each block that goes on, by
@@ -225,14 +239,14 @@ __device__ __forceinline__ void fp4rows_pair_complete(const mfma_f32x16& packed,
 template <int K>
 __device__ __forceinline__ void fp4rows_pair_test(const mfma_f32x16& acc, const PairConsts& pk, const Fp4StepLoader& rows, uint32_t own_step,
                                                   const uint32_t* __restrict__ q, uint32_t qi, uint32_t nq, uint32_t h, const Fp4Consts& kc,
-                                                  float& thr_a, float& thr_b, uint32_t r_lane, uint32_t n_lim, uint32_t (&best_a)[K],
-                                                  uint32_t (&best_b)[K], uint32_t& n_pass) {
+                                                  float& thr_a, float& thr_b, uint32_t n_lim, uint32_t (&best_a)[K],
+                                                  uint32_t (&best_b)[K], uint32_t& n_pass, uint32_t* bound) {
   const uint32_t o = pair_or(acc);
   if (__builtin_expect(__builtin_amdgcn_ballot_w64((o & PairPack::kFlagMask) != 0u) == 0ull, 1)) return;
   if (__builtin_amdgcn_ballot_w64((o & PairPack::kFlagA) != 0u) != 0ull)
-    fp4rows_pair_complete<K, 0>(acc, pk.bias, rows, own_step, q, qi, nq, h, kc, thr_a, r_lane, n_lim, best_a, n_pass);
+    fp4rows_pair_complete<K, 0>(acc, pk.bias, rows, own_step, q, qi, nq, h, kc, thr_a, n_lim, best_a, n_pass, bound);
   if (__builtin_amdgcn_ballot_w64((o & PairPack::kFlagB) != 0u) != 0ull)
-    fp4rows_pair_complete<K, 1>(acc, pk.bias, rows, own_step, q, qi + 32u, nq, h, kc, thr_b, r_lane, n_lim, best_b, n_pass);
+    fp4rows_pair_complete<K, 1>(acc, pk.bias, rows, own_step, q, qi + 32u, nq, h, kc, thr_b, n_lim, best_b, n_pass, bound);
 }
 // fp4rows_split_step in pairs: QT / 2 pairs per step into two alternating accumulators, the test of a pair behind the MFMAs of the
 // next (three accumulators, the test trailing further, measured no better), the step's last pair carried into the next step. With
@@ -242,8 +256,8 @@ template <int K, int QT, int PH>
 __device__ __forceinline__ void fp4rows_pair_step(const Fp4Frags<2>& a, Fp4Frags<2>& a_next, const Fp4StepLoader& rows, uint32_t step,
                                                   const Fp4Frags<2> (&qh)[QT], const uint32_t* __restrict__ q, uint32_t q0c, uint32_t nq,
                                                   uint32_t h, const Fp4Consts& kc, const PairConsts& pk, float (&thr)[QT],
-                                                  uint32_t (&best)[QT][K], mfma_f32x16& acc_even, mfma_f32x16& acc_odd, uint32_t r_lane,
-                                                  uint32_t n_lim, uint32_t& n_pass) {
+                                                  uint32_t (&best)[QT][K], mfma_f32x16& acc_even, mfma_f32x16& acc_odd,
+                                                  uint32_t n_lim, uint32_t& n_pass, uint32_t* bound) {
   static_assert(QT >= 4 && QT % 2 == 0, "whole pairs; the pending pair alternates between two accumulators");
   constexpr int NP = QT / 2;
 #pragma unroll
@@ -255,8 +269,8 @@ __device__ __forceinline__ void fp4rows_pair_step(const Fp4Frags<2>& a, Fp4Frags
       for (int m = 0; m < 2; ++m) a_next.s[m] = rows.template load<false>(step + 1u, m);
     }
     constexpr int kLast = NP - 1;
-    if (j == 0) fp4rows_pair_test<K>(odd ? acc_even : acc_odd, pk, rows, step - 1u, q, q0c + 64u * kLast, nq, h, kc, thr[2 * kLast], thr[2 * kLast + 1], r_lane - 32u, n_lim, best[2 * kLast], best[2 * kLast + 1], n_pass);   // previous step's last pair, its rows
-    else fp4rows_pair_test<K>(odd ? acc_even : acc_odd, pk, rows, step, q, q0c + 64u * (j - 1), nq, h, kc, thr[2 * j - 2], thr[2 * j - 1], r_lane, n_lim, best[2 * j - 2], best[2 * j - 1], n_pass);
+    if (j == 0) fp4rows_pair_test<K>(odd ? acc_even : acc_odd, pk, rows, step - 1u, q, q0c + 64u * kLast, nq, h, kc, thr[2 * kLast], thr[2 * kLast + 1], n_lim, best[2 * kLast], best[2 * kLast + 1], n_pass, bound);   // previous step's last pair, its rows
+    else fp4rows_pair_test<K>(odd ? acc_even : acc_odd, pk, rows, step, q, q0c + 64u * (j - 1), nq, h, kc, thr[2 * j - 2], thr[2 * j - 1], n_lim, best[2 * j - 2], best[2 * j - 1], n_pass, bound);
   }
 }
 
@@ -358,10 +372,14 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc_odd[i] = kNoBlock;
   }
-  uint32_t seen[QT];
+  // The periodic exchange of bounds and its state, in every form but the paired one, which exchanges where a block goes on
+  // (fp4rows_pair_complete) and so ignores share_period
+  [[maybe_unused]] uint32_t seen[QT], next_share = 2u;
+  if constexpr (!PAIRS) {
 #pragma unroll
-  for (int t = 0; t < QT; ++t) seen[t] = 0xFFFFFFFFu;                // "nothing published"
-  uint32_t next_share = 2u, step = 0, n_pass = 0;
+    for (int t = 0; t < QT; ++t) seen[t] = 0xFFFFFFFFu;              // "nothing published"
+  }
+  uint32_t step = 0, n_pass = 0;
   // Static priority for half of the workgroups, set once in front of the loop: the two waves of a SIMD run the same program, and at
   // equal priority the older one wins every arbitration. Workgroups are dealt out over the 8 XCDs and then over an XCD's 32 CUs, so
   // bit 5 of the slot tells a CU's first workgroup from its second in the first round and splits the later ones evenly. Measured at
@@ -372,8 +390,8 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
   if (TOD_K4X_STATIC_PRIO && HALF == 2 && QT == 6 && ((slot >> 5) & 1u)) __builtin_amdgcn_s_setprio(1);
   for (; step + 2u <= n_full; step += 2u) {                           // two steps per trip: the fragments ping-pong between a0 and a1
     if constexpr (PAIRS) {
-      fp4rows_pair_step<K, QT, 0>(a0, a1, rows, step, qb, q, q0 + c, nq, h, kc, pk, thr, best, acc_even, acc_odd, lane_row_base(step, h), n_local, n_pass);
-      fp4rows_pair_step<K, QT, 1>(a1, a0, rows, step + 1u, qb, q, q0 + c, nq, h, kc, pk, thr, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, n_pass);
+      fp4rows_pair_step<K, QT, 0>(a0, a1, rows, step, qb, q, q0 + c, nq, h, kc, pk, thr, best, acc_even, acc_odd, n_local, n_pass, bound);
+      fp4rows_pair_step<K, QT, 1>(a1, a0, rows, step + 1u, qb, q, q0 + c, nq, h, kc, pk, thr, best, acc_even, acc_odd, n_local, n_pass, bound);
     } else if constexpr (TAILS) {
       fp4rows_split_step<K, QT, NF>(a0, a1, rows, step, qb, q, q0 + c, nq, h, kc, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local, n_pass);
       fp4rows_split_step<K, QT, NF>(a1, a0, rows, step + 1u, qb, q, q0 + c, nq, h, kc, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, n_pass);
@@ -381,17 +399,19 @@ __global__ __launch_bounds__(kBlock, 2) void hamming_topk_fp4rows(const uint4* _
       fp4rows_step<K, QT, false, IMAX, HALF>(a0, a1, rows, step + 1u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h), n_local, n_pass);
       fp4rows_step<K, QT, false, IMAX, HALF>(a1, a0, rows, step + 2u, qb, thr, thrp, best, acc_even, acc_odd, lane_row_base(step, h) + 32u, n_local, n_pass);
     }
-    if (step + 2u >= next_share) {                                    // wave-uniform
-      next_share += share_period;
-      exchange_bounds<K, QT>(bound, q0, c, nq, best, seen, thr, [](uint32_t limit) { return thr_of_limit(limit); },
-                             [&](int t) { if constexpr (!PAIRS) thrp[t] = thr[t] - kPartOff; });
+    if constexpr (!PAIRS) {
+      if (step + 2u >= next_share) {                                  // wave-uniform
+        next_share += share_period;
+        exchange_bounds<K, QT>(bound, q0, c, nq, best, seen, thr, [](uint32_t limit) { return thr_of_limit(limit); },
+                               [&](int t) { thrp[t] = thr[t] - kPartOff; });
+      }
     }
   }
   if constexpr (TAILS) {
     // the last unmasked step's last block is still a part: it completes here, in the same form, with the tails of step - 1
     if (step > 0u) {
       if constexpr (PAIRS)                                            // (the last pair, likewise)
-        fp4rows_pair_test<K>(acc_odd, pk, rows, step - 1u, q, q0 + c + 32u * (QT - 2), nq, h, kc, thr[QT - 2], thr[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 2], best[QT - 1], n_pass);
+        fp4rows_pair_test<K>(acc_odd, pk, rows, step - 1u, q, q0 + c + 32u * (QT - 2), nq, h, kc, thr[QT - 2], thr[QT - 1], n_local, best[QT - 2], best[QT - 1], n_pass, bound);
       else
         fp4rows_block_test_part<K, NF>(acc_odd, rows, step - 1u, q, q0 + c + 32u * (QT - 1), nq, h, kc, thr[QT - 1], thrp[QT - 1], lane_row_base(step - 1u, h), n_local, best[QT - 1], n_pass);
 #pragma unroll

@@ -12,7 +12,7 @@ struct MatchEnv {
   int k4_mode;          // TODHIP_K4_MODE=0..3             K4's elimination schedule (default -1: by radius)
   int k4_wpc;           // TODHIP_K4_WAVES_PER_CU=n        K4 tiling: n waves per CU instead of the oversubscribed default (0)
   int k4x_wpc;          // TODHIP_K4X_WAVES_PER_CU=n       K4x tiling: n waves per CU instead of 8 / 16 / 32 by launch shape (0)
-  int k4x_share;        // TODHIP_K4X_SHARE=n              K4x: steps between two exchanges of the distance bounds (16; each launcher has a floor)
+  int k4x_share;        // TODHIP_K4X_SHARE=n              K4x: steps between two exchanges of the distance bounds (16; each launcher has a floor). The paired split-2 step ignores it: it exchanges where a block goes on (fp4rows_pair_complete)
   int k4x_qt;           // TODHIP_K4X_QT=2|4|6|8           K4x: query blocks per wave, also for <= 32 queries (0: by launch shape)
   int k4x_half;         // TODHIP_K4X_HALF=0|2|3           the process's default for todhip_set_matcher_block_split (-1: adaptive; 1 = 2)
   bool k4x_half_debug;  // TODHIP_K4X_HALF_DEBUG           print every report of the split controller to stderr
