@@ -165,7 +165,7 @@ def test_one_gemm_path_with_overflowing_candidate_lists(ctx):
 
 def test_candidates_clustered_in_one_chunk_spill_from_slot_to_shared_list(ctx):
     """Pass 2 keeps a (query, DB chunk, lane half)'s first 8 candidates in a private slot and appends the rest to the query's shared
-    list (csrc/l2.hip, CandSink). 60 near-copies of one vector in CONSECUTIVE rows land in one or two chunks, so both
+    list (csrc/l2_gemm.h, CandSink). 60 near-copies of one vector in CONSECUTIVE rows land in one or two chunks, so both
     containers are in use for the queries next to it and neither overflows; pass 3 must merge them into the oracle's answer."""
     rng = np.random.Generator(np.random.PCG64(321))
     n = 70000
@@ -182,3 +182,51 @@ def test_candidates_clustered_in_one_chunk_spill_from_slot_to_shared_list(ctx):
         glob = (off[m["imgIdx"]].astype(np.int64) + m["trainIdx"]).reshape(len(q), k)
         assert ((glob[:6] >= 31000) & (glob[:6] < 31060)).all()
 
+
+
+# ------------------------------------------------------------ the launch plan's path switch (csrc/l2_plan.h) and the timing bracket
+@pytest.fixture(scope="module")
+def switch_db():
+    """65 537 uniform-random rows, two ragged objects around an empty one; 40 queries, 8 of them a DB row plus small noise (rows of
+    every prefix the tests load), so that the top of those lists is not arbitrary. The tests load prefixes and leave it unchanged."""
+    rng = np.random.Generator(np.random.PCG64(2048))
+    n = 65537
+    desc = (rng.random((n, 128)) * 200).astype(np.float32)
+    pts = rng.random((n, 3)).astype(np.float32)
+    q = (rng.random((40, 128)) * 200).astype(np.float32)
+    q[::5] = desc[rng.integers(0, 65504, 8)] + rng.normal(0, 0.5, (8, 128)).astype(np.float32)
+    return desc, pts, q
+
+
+def _switch_off(n):
+    return np.array([0, 20011, 20011, n], np.uint32)
+
+
+@pytest.mark.parametrize("n", [65504, 65536, 65537])
+def test_path_switch_at_2048_tiles(ctx, switch_db, n):
+    """2047 tiles of 32 rows: the classic two-GEMM path (pass 1 over the whole DB, then pass 2); 2048 tiles: the one-GEMM path (an
+    evenly spaced sample of 512 tiles, its seed is pass 2's threshold); 2049 tiles: the same with one row in a tile of padding."""
+    desc, pts, q = switch_db
+    off = _switch_off(n)
+    ctx.db_load(desc[:n], pts[:n], off)
+    for k in (2, 8):
+        _assert_same(ctx, desc[:n], pts[:n], off, q, k, 1.0e9)
+
+
+def test_match_l2_opens_one_timing_bracket_per_call_on_both_paths(ctx, switch_db):
+    """todhip_set_kernel_timing brackets one kernel per match_l2 call: pass 1's GEMM on the two-GEMM path (a 2 100-row DB), pass 2's
+    GEMM, l2_gemm_kernel<2, 4>, on the one-GEMM path (65 536 rows). With timing off the counter stands still."""
+    desc, pts, q = switch_db
+    for n in (2100, 65536):
+        ctx.db_load(desc[:n], pts[:n], np.array([0, 700, 700, n], np.uint32))
+        before = ctx.counters().n_match_kernel_launches
+        ctx.match_l2(q, 2, 1.0e9)
+        assert ctx.counters().n_match_kernel_launches == before, n
+        ctx.set_kernel_timing(True)
+        try:
+            ctx.match_l2(q, 2, 1.0e9)
+            cnt = ctx.counters()
+            print("n %d: launches %d -> %d, last_match_kernel_ms %.4f" % (n, before, cnt.n_match_kernel_launches, cnt.last_match_kernel_ms))
+            assert cnt.n_match_kernel_launches == before + 1 and cnt.last_match_kernel_ms > 0, n
+        finally:
+            ctx.set_kernel_timing(False)

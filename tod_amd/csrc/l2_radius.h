@@ -1,12 +1,12 @@
 // todhip_match_l2_radius[_device]: the true L2 radius search over a float DB -- every row whose distance is not > radius, counted
-// exactly, the nearest max_per_query of them in the order (d2, row). Included by l2.hip behind its kernels: the query preparation,
-// the DB pass (l2_gemm_kernel<2, 4>), the candidate sink, d2_exact and object_of_row are l2.hip's, unchanged. Definition:
-// include/todhip.h; DESIGN 6l.
+// exactly, the nearest max_per_query of them in the order (d2, row). Included by l2.hip behind the k-NN call's kernels: the query
+// preparation (l2_prepare.h), the DB pass (l2_gemm_kernel<2, 4>) and its candidate sink (l2_gemm.h), d2_exact, the slot copy, the
+// overflow conditions and the match writer (l2_refine.h) are that call's, unchanged. Definition: include/todhip.h; DESIGN 6l.
 //
 // The k-NN call filters with a threshold that comes from a seed (A_k + 2 eps); this one filters with a threshold that comes from the
 // radius, so it needs ONE pass over the DB and no seed GEMM:
 //   LT  l2_radius_threshold_kernel   thr(q) from the radius, |q|^2 and eps(q)               one thread per query
-//   L2G l2_gemm_kernel<2, 4>         candidates = { r : score(q, r) <= thr(q) }             l2.hip's, as l2_keys launches it
+//   L2G l2_gemm_kernel<2, 4>         candidates = { r : score(q, r) <= thr(q) }             l2_gemm.h's, as l2_keys launches it
 //   LR  l2_radius_refine_kernel      exact d2 of the candidates, the cut, the count, a sort one workgroup per query
 //   LS  l2_radius_scan_kernel        the same answer from every DB row in order             one workgroup per FLAGGED query
 //   LE  l2_radius_emit_kernel        key -> match and 3D point                              one thread per output slot
@@ -37,8 +37,6 @@
 
 namespace {
 
-constexpr uint32_t kL2MaxPerQuery = 1024;                 // max_per_query; the lower half of LS's buffer
-constexpr uint32_t kL2SortKeys = 2u * kL2MaxPerQuery;     // keys LR and LS sort in LDS (16 KB); LR holds at most kListCap candidates
 static_assert(kL2SortKeys >= kListCap, "LR sorts every candidate of a query that did not overflow");
 constexpr float kThrMax = 1.0e38f;                        // below the padding rows' score (3e38)
 
@@ -111,19 +109,14 @@ __global__ __launch_bounds__(256) void l2_radius_refine_kernel(const float* __re
   for (uint32_t p = tid; p < n_parts; p += 256u) {
     const uint32_t c = min(slot_cnt[(size_t)qi * n_parts + p], kSlot);
     if (c == 0u) continue;
-    const uint32_t at = atomicAdd(&s_total, c);
-    const uint4* src = reinterpret_cast<const uint4*>(slots + ((size_t)qi * n_parts + p) * kSlot);
-    const uint4 lo = src[0], hi = src[1];
-    const uint32_t rows[kSlot] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-    for (uint32_t j = 0; j < kSlot; ++j) if (j < c && at + j < kListCap) s_rows[at + j] = rows[j];
+    l2_copy_slot(slots + ((size_t)qi * n_parts + p) * kSlot, c, s_rows, atomicAdd(&s_total, c));
   }
   __syncthreads();
   const uint32_t in_slots = s_total, cnt = cand_cnt[qi];
   for (uint32_t c = tid; c < min(cnt, kCandCap); c += 256u)   // what did not fit a slot
     if (in_slots + c < kListCap) s_rows[in_slots + c] = cand[(size_t)qi * kCandCap + c];
   const uint32_t total = in_slots + cnt;
-  if (cnt > kCandCap || total > kListCap) { if (tid == 0) flagged[qi] = 1u; return; }   // redone by LS
+  if (l2_lists_overflowed(cnt, total)) { if (tid == 0) flagged[qi] = 1u; return; }   // redone by LS
   if (tid == 0) flagged[qi] = 0u;
   __syncthreads();
   uint32_t n2 = 1u;
@@ -197,13 +190,7 @@ __global__ __launch_bounds__(256) void l2_radius_emit_kernel(const uint64_t* __r
   const uint32_t qi = (uint32_t)(i / mpq), j = (uint32_t)(i % mpq);
   if (j >= counts[qi]) return;                              // slots behind counts[q] are not written
   const uint64_t key = keys[i];
-  const uint32_t row = (uint32_t)key;
-  const uint32_t lo = object_of_row(obj_off, n_objs, row);
-  todhip_dmatch m;
-  m.queryIdx = (int)qi; m.trainIdx = (int)(row - obj_off[lo]); m.imgIdx = (int)lo; m.distance = sqrtf(__uint_as_float((uint32_t)(key >> 32)));
-  matches[i] = m;
-  float* o = xyz + i * 3;
-  o[0] = pts[(size_t)row * 3 + 0]; o[1] = pts[(size_t)row * 3 + 1]; o[2] = pts[(size_t)row * 3 + 2];
+  l2_write_match(key, l2_key_distance(key), qi, i, obj_off, n_objs, pts, matches, xyz);
 }
 
 }  // namespace
