@@ -364,6 +364,48 @@ int todhip_merge_radius_shards_device_on(todhip_ctx*, void* hip_stream, const vo
                                          uint32_t max_per_query, void* d_counts, void* d_matches, void* d_matches_xyz,
                                          void* d_in_radius /*may be NULL*/);
 
+/* The cross-check, cv::BFMatcher(normType, crossCheck = true): a match stays only where its query is the nearest query of its frame
+ * to the DB row it names. The ratio test judges a query's list in isolation; this filter sees that many keypoints of a frame claim
+ * the same model row and keeps the one that is nearest to it.
+ * Inputs: a match output in the fixed-stride device layout -- d_counts[nq] u32, d_matches[nq * stride], d_matches_xyz[nq * stride * 3],
+ * what todhip_match_device, todhip_merge_shards_device[_on], todhip_match_radius_device and todhip_merge_radius_shards_device[_on]
+ * leave, stride = k or max_per_query --, the nq query descriptors that produced it (d_q_desc, rows of the DB's width), a frame size
+ * frame_queries = Q >= 1 and optionally the host array frame_nq[n_frames], n_frames = ceil(nq / Q).
+ * Definition (exact, deterministic):
+ *   frame f      owns query rows f Q ... min((f + 1) Q, nq) - 1. Its valid queries V(f) are the first min(frame_nq[f], rows of f) of
+ *                those rows; all of them when frame_nq is NULL.
+ *   g(m)         = the row of the full DB that match m names: obj_off[imgIdx] + trainIdx.
+ *   d(q, g)      = the Hamming distance over the DB's width (256 or 512 bits).
+ *   A kept match m of query q in frame f survives iff q is in V(f) and no q' in V(f) has (d(q', g), q') < (d(q, g), q)
+ *   lexicographically: q is the nearest valid query of its frame to row g, ties to the lower query index. With stride 1 this is
+ *   BFMatcher's cross-check with ties to the first index.
+ *   Survivors of a query keep their order and move to the front of the query's slots, each xyz beside its match; counts[q] becomes
+ *   their number. Slots in [new counts[q], old counts[q]) are unspecified afterwards, slots at or behind the old counts[q] are not
+ *   written. A query outside V(f) ends with counts[q] = 0. (A slot that names no row of the DB -- nothing a match call leaves -- is
+ *   dropped.)
+ *   The predicate depends on (q, g, V(f)) only, not on a query's list and not on other frames; the filter is idempotent. Behind the
+ *   ratio test and the radius cut it filters what those two left. Selections (todhip_db_select_objects) and the LSH mode do not
+ *   enter: the reverse search runs over the frame's queries, not over DB rows, and reads row g from the resident full DB. A bit
+ *   order (todhip_set_db_bit_order) is honoured: the queries are permuted as every match form permutes them, the result does not
+ *   change.
+ * In place, asynchronous on the context's stream; frame_nq is copied before the call returns. Two kernels: the test (a lane per kept
+ * match holds its DB row in registers, the frame's valid queries pass through LDS) and an order-preserving compaction per query
+ * (DESIGN 6m).
+ * TODHIP_EINVAL: a null context, query or output pointer, nq == 0, frame_queries == 0, stride == 0 or > 1024 (or nq * stride >=
+ * 2^31), a float DB (desc_bytes == 512), a context whose resident shard is not the whole DB (loaded with shard_count > 1: the rows a
+ * match names are then not all resident -- filter a sharded DB's merged output on a context that holds the whole DB).
+ * TODHIP_ENODB without a DB. */
+int todhip_cross_check_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t frame_queries,
+                              const uint32_t* frame_nq /* host, [ceil(nq / frame_queries)], may be NULL */,
+                              uint32_t stride, void* d_counts, void* d_matches, void* d_matches_xyz);
+/* Switches the cross-check on for todhip_match and todhip_match_device: while frame_queries = Q > 0, those two calls run
+ * todhip_cross_check_device(Q, frame_nq = NULL, stride = k) behind their finalize step (the host form packs its CSR from the
+ * filtered counts). 0 = off, the default: no launch is added and every output is what it was. The sharded and the radius entry points
+ * (todhip_match_shard_device, todhip_merge_shards_device[_on], todhip_match_radius*, todhip_merge_radius_shards_device[_on]) and the
+ * float forms ignore the setting: a caller filters their device outputs with todhip_cross_check_device itself.
+ * TODHIP_EINVAL, and the setting does not change: Q > 0 on a context whose DB is float or is one shard of several. */
+int todhip_set_cross_check(todhip_ctx*, uint32_t frame_queries /* 0 = off, the default */);
+
 /* ---- stage C: GuessGenerator ------------------------------------------------------------------- */
 void todhip_rng_seed(todhip_rng*, uint32_t seed);   /* srand(seed); the reference never seeds => seed 1 */
 /* Replaces GuessGenerator::process (GuessGenerator.cpp:127-250) and everything under src/common.
@@ -624,6 +666,12 @@ int  todhip_pipeline_submit_masked_device(todhip_pipeline*, const void* d_frames
 /* todhip_db_select_objects on the pipeline's matcher context, from the next submit on; the verifier workers keep the spans of every
  * object (poses name objects of the full DB). TODHIP_EBUSY while a ticket is outstanding. */
 int  todhip_pipeline_select_objects(todhip_pipeline*, const uint32_t* ids, uint32_t n_ids);
+/* The cross-check (todhip_cross_check_device) behind each step's matcher call, from the next submit on: on the matcher's stream, in
+ * front of the event the verifier waits on, with frame_queries = n_features and frame_nq = the step's n_kp -- the rows behind n_kp[f]
+ * hold an earlier step's descriptors and do not compete. Frame f of a step then yields what the chain todhip_orb_device ->
+ * todhip_match_device -> todhip_cross_check_device(frame_nq = {n_kp}) -> todhip_verify_device_depth yields on that frame alone.
+ * enable 0 (the default): the steps are those of a pipeline that never called this. TODHIP_EBUSY while a ticket is outstanding. */
+int  todhip_pipeline_set_cross_check(todhip_pipeline*, int enable);
 /* One device-resident BGR8 / BGRA8 image (channels 3 | 4, row stride src_stride bytes) -> gray (row stride gray_stride bytes), the
  * conversion the pipeline runs in front of ORB: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14, what adapter/ecto_cells.hpp computes on
  * the host. Asynchronous on the context's stream. */

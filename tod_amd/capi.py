@@ -101,6 +101,7 @@ EXPORTS = [
     "todhip_model_add_observations_device",
     "todhip_match_l2_radius", "todhip_match_l2_radius_device",
     "todhip_test_draw_table", "todhip_test_kabsch",
+    "todhip_cross_check_device", "todhip_set_cross_check", "todhip_pipeline_set_cross_check",
 ]
 
 MAX_TRAIN_BATCH_VIEWS = 64
@@ -205,6 +206,11 @@ def lib():
             L.todhip_test_draw_table.restype = C.c_int
         if hasattr(L, "todhip_test_kabsch"):                          # (as above)
             L.todhip_test_kabsch.argtypes, L.todhip_test_kabsch.restype = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4, C.c_int
+        if hasattr(L, "todhip_cross_check_device"):                   # (as above)
+            L.todhip_cross_check_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+            L.todhip_cross_check_device.restype = C.c_int
+            L.todhip_set_cross_check.argtypes, L.todhip_set_cross_check.restype = [C.c_void_p, C.c_uint32], C.c_int
+            L.todhip_pipeline_set_cross_check.argtypes, L.todhip_pipeline_set_cross_check.restype = [C.c_void_p, C.c_int], C.c_int
         _lib = L
     return _lib
 
@@ -494,6 +500,21 @@ class Context:
         rc = lib().todhip_match_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius),
                                        C.c_void_p(d_counts), C.c_void_p(d_matches), C.c_void_p(d_xyz))
         _check(rc, "todhip_match_device")
+
+    def cross_check_device(self, d_q, nq, frame_queries, stride, d_counts, d_matches, d_xyz, frame_nq=None):
+        """The cross-check filter in place on a fixed-stride device output (todhip_cross_check_device): a match stays only where its
+        query is the nearest valid query of its frame (frame_queries rows each) to the DB row it names, ties to the lower query
+        index. frame_nq: per frame, how many of its first rows compete (None: all). Asynchronous on the context's stream."""
+        fn = None if frame_nq is None else np.ascontiguousarray(frame_nq, np.uint32)
+        if fn is not None and len(fn) != (nq + frame_queries - 1) // max(frame_queries, 1):
+            raise TodError(EINVAL, "todhip_cross_check_device (frame_nq of %d entries for %d queries in frames of %d)" % (len(fn), nq, frame_queries))
+        _check(lib().todhip_cross_check_device(self._h, d_q, nq, frame_queries, None if fn is None else _np_ptr(fn), stride, d_counts,
+                                               d_matches, d_xyz), "todhip_cross_check_device")
+
+    def set_cross_check(self, frame_queries):
+        """match() and match_device() run the cross-check behind their finalize step, in frames of frame_queries query rows (0 = off,
+        the default). The sharded and radius forms ignore it: filter their outputs with cross_check_device."""
+        _check(lib().todhip_set_cross_check(self._h, frame_queries), "todhip_set_cross_check")
 
     def match_shard_device(self, d_q, nq, k, radius, d_keys):
         rc = lib().todhip_match_shard_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius),
@@ -1027,6 +1048,11 @@ class Pipeline:
         pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
         assert pat is None or pat.size == 1024
         return lib().todhip_pipeline_set_pattern(self._h, None if pat is None else _np_ptr(pat))
+
+    def set_cross_check(self, enable):
+        """The cross-check behind each step's matcher call, per frame among its n_kp keypoints (todhip_pipeline_set_cross_check).
+        Returns the status (EBUSY while a ticket is outstanding)."""
+        return lib().todhip_pipeline_set_cross_check(self._h, C.c_int(1 if enable else 0))
 
     def select_objects(self, ids):
         """Context.select_objects on the pipeline's matcher, from the next submit on; returns the status (EBUSY while a ticket is

@@ -357,6 +357,9 @@ int todhip_match_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint
   rc = tod_match_finalize(ctx, ctx->m_keys.as<uint64_t>(), n_lists, nq, k_in, k, radius,
                           reinterpret_cast<uint32_t*>(d_counts), reinterpret_cast<todhip_dmatch*>(d_matches),
                           reinterpret_cast<float*>(d_matches_xyz));
+  if (rc == TODHIP_OK && ctx->cross_check_q)                             // todhip_set_cross_check: the filter behind the finalize step
+    rc = tod_cross_check(ctx, d_q_desc, nq, ctx->cross_check_q, nullptr, k, reinterpret_cast<uint32_t*>(d_counts),
+                         reinterpret_cast<todhip_dmatch*>(d_matches), reinterpret_cast<float*>(d_matches_xyz));
   if (rc == TODHIP_OK) { ctx->counters.last_nq = nq; ctx->counters.last_k = k; }
   return rc;
 }
@@ -382,8 +385,19 @@ int todhip_match(todhip_ctx* ctx, const uint8_t* q_desc, uint32_t nq, uint32_t k
   uint32_t* h_counts = ctx->h_stage.as<uint32_t>();
   todhip_dmatch* h_m = reinterpret_cast<todhip_dmatch*>(h_counts + nq);
   float* h_xyz = reinterpret_cast<float*>(h_m + nm);
-  int rc = todhip_match_device(ctx, ctx->m_q.p, nq, k, radius, h_counts, h_m, h_xyz);
-  if (rc != TODHIP_OK) return rc;
+  int rc = TODHIP_OK;
+  if (!ctx->cross_check_q) {
+    rc = todhip_match_device(ctx, ctx->m_q.p, nq, k, radius, h_counts, h_m, h_xyz);
+    if (rc != TODHIP_OK) return rc;
+  } else {
+    // todhip_set_cross_check: the filter reads and compacts the outputs in place -- in device memory, not slot by slot over PCIe --
+    // and the filtered image follows in three copies
+    rc = todhip_match_device(ctx, ctx->m_q.p, nq, k, radius, ctx->m_counts.p, ctx->m_matches.p, ctx->m_xyz.p);
+    if (rc != TODHIP_OK) return rc;
+    TOD_HIP(hipMemcpyAsync(h_counts, ctx->m_counts.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    TOD_HIP(hipMemcpyAsync(h_m, ctx->m_matches.p, nm * sizeof(todhip_dmatch), hipMemcpyDeviceToHost, ctx->stream));
+    TOD_HIP(hipMemcpyAsync(h_xyz, ctx->m_xyz.p, nm * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  }
   TOD_HIP(hipStreamSynchronize(ctx->stream));
   ctx->counters.last_matches = tod_pack_csr(h_counts, h_m, h_xyz, nq, k, row_ptr, matches, matches_xyz);
   return TODHIP_OK;

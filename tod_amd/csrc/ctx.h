@@ -100,7 +100,7 @@ struct HostBuf {
 // A stage's workspace: defined in the stage's translation unit (struct XWs : TodWs with kSlot = its slot), created on first use by
 // tod_ws<XWs>(ctx), owned by the context. Its destructor is the stage's whole teardown. The slots are released in this order.
 struct TodWs { virtual ~TodWs() {} };
-enum TodWsSlot { kWsVerify, kWsOrb, kWsL2, kWsPnp, kWsLsh, kWsLearn, kWsCompact, kWsRadius, kWsSlots };
+enum TodWsSlot { kWsVerify, kWsOrb, kWsL2, kWsPnp, kWsLsh, kWsLearn, kWsCompact, kWsRadius, kWsCrossCheck, kWsSlots };
 
 struct todhip_ctx {
   int device = 0;
@@ -135,6 +135,7 @@ struct todhip_ctx {
   HostBuf k4x_stats_host; DevBuf k4x_stats_dev;
   K4xSplit k4x;                              // k4x.force: todhip_set_matcher_block_split
   float ratio = 0.f;                         // todhip_set_ratio_test (0 = off)
+  uint32_t cross_check_q = 0;                // todhip_set_cross_check: the frame size todhip_match[_device] filter with (0 = off)
   // todhip_set_db_bit_order (db_bitorder.hip): the mode the next load uses; the order of the resident shard (stored position p holds
   // original bit bit_src_of[p]) and whether it differs from the identity; its device copy and the queries' workspace -- both stay
   // empty until a load computes an order
@@ -231,6 +232,9 @@ int tod_match_shard_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t
 int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k_in, uint32_t k_out,
                        uint32_t radius, uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz,
                        hipStream_t stream = nullptr);   // nullptr: the context's stream
+// cross_check.hip: todhip_cross_check_device behind its argument checks (what todhip_match[_device] run while todhip_set_cross_check is on)
+int tod_cross_check(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t frame_queries, const uint32_t* frame_nq, uint32_t stride,
+                    uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz);
 // verify.hip: ClusterPerObject of F frames on the device without a cloud (pnp.hip's 2D-only branch); d_err: 8 words per frame
 // (ClusterCtl of verify_kernels.h: word 0 = error, word 4 = matches kept)
 int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy, uint32_t nq, const uint32_t* d_counts,

@@ -143,6 +143,7 @@ struct todhip_pipeline {
   todhip_rng rng0;
   int8_t pattern[1024] = {};             // todhip_pipeline_set_pattern: written only while every slot is free
   bool has_pattern = false;
+  bool cross_check = false;              // todhip_pipeline_set_cross_check: written only while every slot is free
 
   std::mutex mu;                         // slot states, tickets, stats, dead, stop
   std::condition_variable cv;
@@ -220,6 +221,12 @@ int todhip_pipeline::match_step(Slot* s) {
   if (any_short) {
     hipLaunchKernelGGL(mask_short_frames_kernel, dim3((nq + 255u) / 256u, n), dim3(256), 0, streams[0], s->counts.as<uint32_t>(), nq, fc);
     PIPE_HIP(hipGetLastError());
+  }
+  if (cross_check) {
+    // per frame, among its n_kp keypoints: the rows behind n_kp[f] hold an earlier step's descriptors and do not compete (the
+    // matcher's stream is the context's, and up to kMaxFrames frame counts travel as a kernel argument: no copy, no wait)
+    const int rc2 = todhip_cross_check_device(mctx, s->desc.p, n * nq, nq, s->n_kp, prm.k, s->counts.p, s->matches.p, s->xyz.p);
+    if (rc2 != TODHIP_OK) return rc2;
   }
   PIPE_HIP(hipEventRecord(s->matched, streams[0]));
   return TODHIP_OK;
@@ -500,6 +507,16 @@ int todhip_pipeline_set_pattern(todhip_pipeline* p, const int8_t* pattern) {
     if (s.state != kFree) return TODHIP_EBUSY;
   p->has_pattern = pattern != nullptr;
   if (pattern) std::memcpy(p->pattern, pattern, sizeof(p->pattern));
+  return TODHIP_OK;
+}
+
+int todhip_pipeline_set_cross_check(todhip_pipeline* p, int enable) {
+  if (!p) return TODHIP_EINVAL;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (p->dead) return TODHIP_EHIP;
+  for (const Slot& s : p->slots)
+    if (s.state != kFree) return TODHIP_EBUSY;
+  p->cross_check = enable != 0;
   return TODHIP_OK;
 }
 
