@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "orb_arc.h"
 #include "orb_compass.h"
 #include "orb_stages.h"
 

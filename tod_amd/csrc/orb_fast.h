@@ -1,59 +1,36 @@
 // FAST-9/16 on every level in one launch: the score, its border rule, the compass pre-test, and fast_nms_kernel, which scores a tile
 // in LDS, suppresses non-maxima, applies the level-0 mask and appends the candidates with their score histogram.
 // Included by orb.hip inside its anonymous namespace, after orb_stages.h (wave_append, the tile size), orb_compass.h (kFastThr,
-// compass4: the pre-test on four positions) and orb_pyramid.h (load_px4).
-
-// FAST-9/16 score: max over the 16 arcs of 9 contiguous circle pixels, both polarities, of the minimum difference.
-// Sliding minima over the (cyclic) circle: windows of 2, 4, 8, then 9.
-__device__ __forceinline__ int arc9_max(const int (&d)[16]) {
-  int m2[16], m4[16], best = -(1 << 30);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) m2[i] = min(d[i], d[(i + 1) & 15]);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) m4[i] = min(m2[i], m2[(i + 2) & 15]);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int m8 = min(m4[i], m4[(i + 4) & 15]);
-    best = max(best, min(m8, d[(i + 8) & 15]));
-  }
-  return best;
-}
+// compass4: the pre-test on four positions), orb_arc.h (the arc search, the survivor list's entries) and orb_pyramid.h (load_px4).
 
 // The border rule of the score: positions whose ring or whose non-maximum neighbourhood cannot hold a keypoint score 0 and read
 // nothing: x < kEdge - 1, x >= w - kEdge + 1, y < kEdge - 1 or y >= h - kEdge + 1 (pass 1 of fast_nms_kernel applies it).
 
-// the score of the pixel at c in an image of row pitch W (a position inside the border rule's rectangle)
+// the FAST-9/16 score (orb_arc.h) of the pixel at c in an image of row pitch W (a position inside the border rule's rectangle): ring
+// pixels i and i + 8 lie opposite each other
 __device__ __forceinline__ int fast_score_at(const uint8_t* c, int W) {
-  const int p = c[0];
-  int d[16], nd[16];
-  d[0] = c[3 * W] - p;       d[1] = c[3 * W + 1] - p;   d[2] = c[2 * W + 2] - p;   d[3] = c[W + 3] - p;
-  d[4] = c[3] - p;           d[5] = c[-W + 3] - p;      d[6] = c[-2 * W + 2] - p;  d[7] = c[-3 * W + 1] - p;
-  d[8] = c[-3 * W] - p;      d[9] = c[-3 * W - 1] - p;  d[10] = c[-2 * W - 2] - p; d[11] = c[-W - 3] - p;
-  d[12] = c[-3] - p;         d[13] = c[W - 3] - p;      d[14] = c[2 * W - 2] - p;  d[15] = c[3 * W - 1] - p;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) nd[i] = -d[i];
-  const int best = max(0, max(arc9_max(d), arc9_max(nd)));
-  return best > kFastThr ? best : 0;
+  const uint32_t pp = (uint32_t)c[0] * 0x00010001u;
+  pair16 d[8];
+  d[0] = pk_diff(c[3 * W], c[-3 * W], pp);          d[1] = pk_diff(c[3 * W + 1], c[-3 * W - 1], pp);
+  d[2] = pk_diff(c[2 * W + 2], c[-2 * W - 2], pp);  d[3] = pk_diff(c[W + 3], c[-W - 3], pp);
+  d[4] = pk_diff(c[3], c[-3], pp);                  d[5] = pk_diff(c[-W + 3], c[W - 3], pp);
+  d[6] = pk_diff(c[-2 * W + 2], c[2 * W - 2], pp);  d[7] = pk_diff(c[-3 * W + 1], c[3 * W - 1], pp);
+  return fast_score_pairs(d);
 }
 
-// Append to a list whose order is free, up to four entries per lane (bit i of m: the lane appends p + i): one exclusive prefix sum
-// of the lanes' popcounts across the wave, taken bit by bit from four ballots, and one atomic on *counter. Called by all lanes of
-// the wave together.
+// Append to a list whose order is free, up to four entries per lane (bit i of m: the lane appends p + i): one popcount per lane, one
+// prefix sum of the popcounts across the wave (wave_prefix_sum: six DPP additions, where four ballots with their lane counts took
+// sixteen instructions) and one atomic on *counter. Called by all lanes of the wave together.
 __device__ __forceinline__ void wave_append4(uint32_t* counter, uint16_t* list, uint32_t m, uint32_t p) {
-  uint32_t before = 0u, total = 0u;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const unsigned long long bal = __builtin_amdgcn_ballot_w64(((m >> i) & 1u) != 0u);
-    before = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, before));
-    total += (uint32_t)__popcll(bal);
-  }
+  const uint32_t c = (uint32_t)__popc(m), v = wave_prefix_sum(c);
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
   if (total == 0u) return;                                   // wave-uniform
   uint32_t base = 0u;
   if ((threadIdx.x & 63u) == 0u) base = atomicAdd(counter, total);
-  uint32_t slot = (uint32_t)__builtin_amdgcn_readlane((int)base, 0) + before;
+  uint16_t* dst = list + ((uint32_t)__builtin_amdgcn_readlane((int)base, 0) + v - c);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    if ((m >> i) & 1u) list[slot++] = (uint16_t)(p + (uint32_t)i);
+    if ((m >> i) & 1u) *dst++ = (uint16_t)(p + (uint32_t)i);
 }
 
 // FAST score + 3x3 strict non-maximum suppression + compaction in one pass: a block scores a 64 x 16 pixel tile and
@@ -66,7 +43,8 @@ __device__ __forceinline__ void wave_append4(uint32_t* counter, uint16_t* list, 
 // seventeen and no arc search; the five windows of a group are seven aligned LDS words) and appends the survivors to an LDS list
 // (wave_append4, one LDS atomic per wave). Pass 2 runs the exact score over that list with dense lanes. On textured images 4 %
 // of the positions score and 6-7 % survive pass 1, but they are spread so that most 64-pixel row segments hold one: an early exit that needs a whole wave to fail the test would almost never be taken, so
-// the survivors are compacted instead. On noise every position survives; the list holds them all.
+// the survivors are compacted instead. On noise every position survives; the list holds them all. The suppression and the append
+// walk the same list: only a position on it can score, so the other 93 % of the tile are never visited again.
 constexpr int kNmsScoreW = kNmsTileW + 2, kNmsScoreN = (kNmsTileH + 2) * kNmsScoreW;     // scored positions: the tile and 1 pixel around
 constexpr int kNmsImgDw = (kNmsTileW + 8) / 4, kNmsImgW = 4 * kNmsImgDw, kNmsImgH = kNmsTileH + 8;   // staged pixels: 4 around
 constexpr int kNmsGroups = (kNmsScoreW + 3) / 4, kNmsGroupN = (kNmsTileH + 2) * kNmsGroups;           // pass 1's groups of four positions
@@ -82,7 +60,7 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, u
   __shared__ __align__(8) int s_score[kNmsScoreN];           // (pass 1 clears it two positions a store; a row starts on an even one)
   __shared__ uint32_t s_hist[256];
   __shared__ uint32_t s_img[kNmsImgH * kNmsImgDw];          // pixel (x0 - 4 + i, y0 - 4 + r) is byte r * kNmsImgW + i
-  __shared__ uint16_t s_list[kNmsScoreN];                   // pass 1's survivors (positions of s_score), in any order
+  __shared__ uint16_t s_list[kNmsScoreN];                   // pass 1's survivors (nms_entry of their positions), in any order
   __shared__ uint32_t s_n;
   const int x0 = (int)blockIdx.x * kNmsTileW, y0 = (int)blockIdx.y * kNmsTileH;
   const uint32_t lane = threadIdx.x & 63u;
@@ -119,35 +97,44 @@ __global__ __launch_bounds__(256) void fast_nms_kernel(LevelTab T, Cand* cand, u
         m &= compass4(window4(c[0], c[1], 3), window4(dn[0], dn[1], 3), window4(c[1], c[2], 2), window4(up[0], up[1], 3), c[0]);
       }
     }
-    wave_append4(&s_n, s_list, m, (uint32_t)(py * kNmsScoreW + px));
+    wave_append4(&s_n, s_list, m, nms_entry(px, py));
   }
   __syncthreads();
   const uint32_t n_list = s_n;                               // <= kNmsScoreN: every position is appended at most once
   for (uint32_t i = threadIdx.x; i < n_list; i += 256u) {    // pass 2
-    const int p = s_list[i], py = p / kNmsScoreW, px = p - py * kNmsScoreW;
-    s_score[p] = fast_score_at(s_px + (py + 3) * kNmsImgW + px + 3, kNmsImgW);
+    const uint32_t e = s_list[i];
+    const int py = nms_entry_py(e), px = nms_entry_px(e);
+    s_score[py * kNmsScoreW + px] = fast_score_at(s_px + (py + 3) * kNmsImgW + px + 3, kNmsImgW);
   }
   __syncthreads();
-  const int tx = (int)lane;
-#pragma unroll
-  for (int j = 0; j < kNmsTileH / 4; ++j) {
-    const int ty = (int)(threadIdx.x >> 6) + 4 * j;
-    const uint32_t x = (uint32_t)(x0 + tx), y = (uint32_t)(y0 + ty);
-    const int* c = &s_score[(ty + 1) * kNmsScoreW + tx + 1];
-    const int s = c[0];
-    bool keep = s != 0 && !(x < (uint32_t)kEdge || x >= w - kEdge || y < (uint32_t)kEdge || y >= h - kEdge);
-    if (keep) {
-      constexpr int R = kNmsScoreW;
-      keep = c[-R - 1] < s && c[-R] < s && c[-R + 1] < s && c[-1] < s && c[1] < s && c[R - 1] < s && c[R] < s && c[R + 1] < s;
+  // Suppression walks the list too, with dense lanes: a position that is not on it scores 0 and is no candidate. An entry in the
+  // one-pixel halo belongs to the neighbouring tile; one inside the tile has all eight neighbours in s_score.
+  for (uint32_t i0 = threadIdx.x & ~63u; i0 < n_list; i0 += 256u) {   // wave-uniform: wave_append is called by the whole wave
+    const uint32_t i = i0 + lane;
+    uint32_t x = 0u, y = 0u;
+    int s = 0;
+    bool keep = false;
+    if (i < n_list) {
+      const uint32_t e = s_list[i];
+      const int py = nms_entry_py(e), px = nms_entry_px(e);
+      const int* c = &s_score[py * kNmsScoreW + px];
+      s = c[0];
+      x = (uint32_t)(x0 + px - 1); y = (uint32_t)(y0 + py - 1);
+      keep = s != 0 && px >= 1 && px <= kNmsTileW && py >= 1 && py <= kNmsTileH &&
+             !(x < (uint32_t)kEdge || x >= w - kEdge || y < (uint32_t)kEdge || y >= h - kEdge);
+      if (keep) {
+        constexpr int R = kNmsScoreW;
+        keep = c[-R - 1] < s && c[-R] < s && c[-R + 1] < s && c[-1] < s && c[1] < s && c[R - 1] < s && c[R] < s && c[R + 1] < s;
+      }
+      if (keep && mask) {   // level-0 mask sampled at the nearest pixel (the training cell passes obs.mask to the detector, Trainer.cpp:144-150)
+        uint32_t my = (uint32_t)floorf(((float)y + 0.5f) * (float)H0 / (float)h), mx = (uint32_t)floorf(((float)x + 0.5f) * (float)W0 / (float)w);
+        my = min(my, H0 - 1u); mx = min(mx, W0 - 1u);
+        keep = mask[(size_t)my * W0 + mx] != 0;
+      }
     }
-    if (keep && mask) {   // level-0 mask sampled at the nearest pixel (the training cell passes obs.mask to the detector, Trainer.cpp:144-150)
-      uint32_t my = (uint32_t)floorf(((float)y + 0.5f) * (float)H0 / (float)h), mx = (uint32_t)floorf(((float)x + 0.5f) * (float)W0 / (float)w);
-      my = min(my, H0 - 1u); mx = min(mx, W0 - 1u);
-      keep = mask[(size_t)my * W0 + mx] != 0;
-    }
-    const uint32_t i = wave_append(counter, keep);           // the counter runs on past cap: fast_threshold_kernel clamps it
-    if (keep && i < cap) {
-      Cand cd; cd.x = (int)x; cd.y = (int)y; cd.score = s; cd.harris = 0.f; cand[i] = cd;
+    const uint32_t slot = wave_append(counter, keep);        // the counter runs on past cap: fast_threshold_kernel clamps it
+    if (keep && slot < cap) {
+      Cand cd; cd.x = (int)x; cd.y = (int)y; cd.score = s; cd.harris = 0.f; cand[slot] = cd;
       atomicAdd(&s_hist[s & 255], 1u);
     }
   }

@@ -24,6 +24,18 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t* counter, bool flag) {
   return base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
 }
 
+// The inclusive prefix sum of v over the wave's 64 lanes (lane 63 holds the wave's sum), on the DPP path: shifts by 1, 2, 4 and 8
+// inside a row of 16 lanes, then lane 15 of every row into the next row and lane 31 into the upper half. A lane whose source lies
+// outside its row, or whose row is not in the row mask, adds the 0 given as the old value. Called by all lanes of the wave together.
+__device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v) {
+#define TOD_ORB_DPP_ADD(ctrl, rows) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xF, false)
+  TOD_ORB_DPP_ADD(0x111, 0xF); TOD_ORB_DPP_ADD(0x112, 0xF); TOD_ORB_DPP_ADD(0x114, 0xF); TOD_ORB_DPP_ADD(0x118, 0xF);   // row_shr:1, 2, 4, 8
+  TOD_ORB_DPP_ADD(0x142, 0xA); TOD_ORB_DPP_ADD(0x143, 0xC);                                                             // row_bcast:15, row_bcast:31
+#undef TOD_ORB_DPP_ADD
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_prefix_sum(v), 63); }
+
 // integer moments over the radius-15 disc around (x, y): lane l < 31 owns row l - 15, every lane of the wave gets the sums
 __device__ __forceinline__ void patch_moments(const uint8_t* __restrict__ img, int W, int x, int y, const int (&umax)[kHalfPatch + 2],
                                               uint32_t l, int& m10, int& m01) {
@@ -36,8 +48,7 @@ __device__ __forceinline__ void patch_moments(const uint8_t* __restrict__ img, i
     row_moments(img + (size_t)(y + v) * W + x - kHalfPatch, d, rs, m10);
     m01 = v * rs;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { m10 += __shfl_xor(m10, off); m01 += __shfl_xor(m01, off); }
+  m10 = (int)wave_sum((uint32_t)m10); m01 = (int)wave_sum((uint32_t)m01);      // (two's complement: the sums are exact in any order)
 }
 
 // the patch's orientation as (cos, sin), no angle quantisation
@@ -50,7 +61,8 @@ __device__ __forceinline__ void steer_of(float fm10, float fm01, float& ca, floa
 __device__ __forceinline__ bool steered_test(const uint8_t* __restrict__ blur, int W, int x, int y, float ca, float sa, const int8_t* pp) {
   const int x0 = (int)rintf((float)pp[0] * ca - (float)pp[1] * sa), y0 = (int)rintf((float)pp[0] * sa + (float)pp[1] * ca);
   const int x1 = (int)rintf((float)pp[2] * ca - (float)pp[3] * sa), y1 = (int)rintf((float)pp[2] * sa + (float)pp[3] * ca);
-  const int t0 = blur[(size_t)(y + y0) * W + (x + x0)], t1 = blur[(size_t)(y + y1) * W + (x + x1)];
+  // (32-bit offsets into the frame's slice, as every pixel index of a level is)
+  const int t0 = blur[(uint32_t)(y + y0) * (uint32_t)W + (uint32_t)(x + x0)], t1 = blur[(uint32_t)(y + y1) * (uint32_t)W + (uint32_t)(x + x1)];
   return t0 < t1;
 }
 
