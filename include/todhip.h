@@ -234,10 +234,18 @@ int todhip_match_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t
  * 195-252): order (distance asc, global row asc), truncated at the first distance > radius; DMatch.distance =
  * sqrtf(d2), d2 = sum over i = 0..127 in index order of (q[i] - r[i])^2 in IEEE binary32 without fused multiply-add
  * (the CPU checker of this definition is oracle/l2_oracle.c). The candidates come from a
- * bf16 MFMA GEMM with a proven error bound, the final order from the exact distances.
+ * bf16 MFMA GEMM whose distance from d2 is bounded by eps(q) = 2^-6 (1 + 2^-6) |q| Rmax + 2^-14 (|q| + Rmax)^2 (derived in
+ * tod_amd/csrc/l2_bound.h, held against binary64 on worst-case inputs by tests/l2_bound_host_test.cpp and on the GPU by
+ * tests/test_l2_numerics_gpu.py), the final order from the exact distances.
+ * Domain (this call and todhip_match_l2_radius): every component of the DB and of the queries is finite, and every squared norm
+ * |q|^2, |r|^2 is zero or lies in [2^-64, 2^64], so that no square, product or sum of the search leaves the normal range of
+ * binary32 (a score stays far below the 3e38 that marks a padding row, and no bf16 product underflows). The bound is relative: it
+ * says nothing about a DB or a query whose norms underflow, and outside the domain the result is not defined.
  * Batch form: the nq queries may be those of F frames (F x Q rows, frame f's query q at row f Q + q, which is also its
  * queryIdx): they share ONE pass over the DB, and every query's matches are those of a call that carried its frame alone
- * (16 frames of 1000 queries against 500k rows: 0.12 ms per frame instead of 0.19). */
+ * (16 frames of 1000 queries against 500k rows under the first, too narrow eps: 0.12 ms per frame instead of 0.19; under the
+ * corrected one a 16-frame call has too few private candidate slots per query and is slower per frame than single calls, 0.75 ms
+ * against 0.24: DESIGN 6b, "The bound"). */
 int todhip_match_l2(todhip_ctx*, const float* q_desc, uint32_t nq, uint32_t k, float radius, uint32_t* row_ptr,
                     todhip_dmatch* matches, float* matches_xyz);
 int todhip_match_l2_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t k, float radius, void* d_counts,
@@ -266,7 +274,7 @@ int todhip_match_l2_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint3
  * TODHIP_EINVAL: a null context, query or output pointer, nq == 0, max_per_query == 0 or > 1024, a radius that is not > 0 or not
  * finite, a DB that is not float (or is sharded). TODHIP_ENODB without a DB. todhip_get_counters: last_nq, last_k = max_per_query,
  * last_matches (host form); todhip_set_kernel_timing brackets the pass over the DB.
- * How: one pass of the k-NN call's bf16 GEMM with a threshold derived from the radius and the GEMM's proven error bound, the exact
+ * How: one pass of the k-NN call's bf16 GEMM with a threshold derived from the radius and the GEMM's error bound eps(q), the exact
  * distance of every candidate, a sort. A query whose candidate lists overflow (more than about 2000 candidates) is answered by a
  * second, ordered pass over the f32 rows for that query (same result). Workspace: the k-NN call's, with
  * nq * max_per_query * 8 bytes of keys. */

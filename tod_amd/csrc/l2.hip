@@ -6,15 +6,18 @@
 //
 // Exact result from an approximate GEMM -- filter and refine:
 //   score(q, r) = |r|^2 - 2 <q^, r^>          q^, r^ = bf16 roundings, product on the matrix cores (f32 accumulate)
-//   |score + |q|^2 - d2(q, r)| <= eps(q)      eps(q) = 2^-7 (1 + 2^-6) |q| Rmax + 2^-14 (|q| + Rmax)^2, Rmax = max |r|
-//   (bf16 rounding moves each vector by <= 2^-9 of its norm, Cauchy-Schwarz on the two error terms, the f32
-//   accumulation of 128 products and of the norms is below 2^-16 of |q||r|; the second term covers the rounding
-//   of the sequential f32 sum that DEFINES d2, see include/todhip.h).
+//   |score + |q|^2 - d2(q, r)| <= eps(q)      eps(q) = 2^-6 (1 + 2^-6) |q| Rmax + 2^-14 (|q| + Rmax)^2, Rmax = max |r|
+//   (l2_bound.h states eps and derives it: bf16 keeps 8 significant bits, so rounding moves every COMPONENT by up to u = 2^-8 of
+//   its magnitude; -2 <q^, r^> is then off by at most (4 u + 2 u^2) |q||r| = 2^-6 (1 + 2^-9) |q||r| by Cauchy-Schwarz on each of the
+//   three error terms, and inputs exist that reach it. The second term covers every f32 rounding: the f32 norms, the matrix cores'
+//   accumulation of the 128 products onto |r|^2, and the sequential f32 sum that DEFINES d2, see include/todhip.h.
+//   tests/l2_bound_host_test.cpp holds the inequality against binary64; domain: finite components, normal f32 squared norms.)
 //   pass 0  seed(q) >= A_k from a sample of the DB                  (the k-th smallest of per-partition minima, or of per-lane lists)
 //   pass 1  A_k(q) = k-th smallest score over the DB                (GEMM + per-lane top-8 in registers; only scores
 //                                                                    below the seed are ever inserted)
 //   pass 2  candidates = { r : score <= A_k + 2 eps }                (same GEMM; a lane's candidates go to its private slot)
-//           every row of the true top-k is a candidate: its d2 <= T_k <= A_k + |q|^2 + eps
+//           every row of the true top-k is a candidate: the k rows of the smallest scores have d2 <= A_k + |q|^2 + eps, so the k-th
+//           smallest d2, T_k, is at most that, and a row with d2 <= T_k scores at most d2 - |q|^2 + eps <= A_k + 2 eps
 //   DBs of >= 64k rows skip pass 1: the sample is an evenly spaced quarter of the DB (at most 64k rows) and seed + 2 eps
 //   is used as the threshold of pass 2 -- seed >= A_k, so the candidates are a superset (rows of rank <= ~k N / n_sample
 //   plus the eps band) and pass 3 returns the same result from it
@@ -23,6 +26,7 @@
 //
 // One translation unit, headers by concern; this file is the host side (workspace, launches, the four C entry points):
 //   l2_plan.h     host, no HIP: shared constants, L2Knobs (the environment), L2Plan = geometry, seed-pass decision, buffer sizes
+//   l2_bound.h    host and device, plain C++: the bf16 rounding and eps(q), with the derivation
 //   l2_prepare.h  l2_prepare_kernel: bf16 images of the DB (A-fragment order) and of the queries, norms, eps
 //   l2_gemm.h     L2G  l2_gemm_kernel<PASS, KT>: wave = (DB chunk, 4 query tiles of 32), the DB streams through a per-wave ring in LDS,
 //                 the accumulator IS the score; CandSink and the epilogues of passes 0, 1, 2

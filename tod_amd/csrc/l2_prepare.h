@@ -1,13 +1,9 @@
 // The float matcher's bf16 images: the DB's at load time (A-fragment order, row norms, Rmax) and the queries' in every call (bf16
-// scaled by -2, |q|^2, eps, zeroed shared candidate counters). Included by l2.hip.
+// scaled by -2, |q|^2, eps, zeroed shared candidate counters). Included by l2.hip. The rounding and eps are l2_bound.h's.
 #pragma once
+#include "l2_bound.h"
 
 namespace {
-
-__device__ __forceinline__ uint16_t bf16_rne(float x) {
-  const uint32_t b = __float_as_uint(x);
-  return (uint16_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-}
 
 // one wave per row: bf16 image (scaled by `scale`, a power of two) and |row|^2; rows >= n are padding
 // frag != 0 (the DB image): a 32-row tile is stored in MFMA A-fragment order -- 8 segments (k-steps s) of 64 lanes x 16 bytes,
@@ -28,7 +24,7 @@ __global__ __launch_bounds__(256) void l2_prepare_kernel(const float* __restrict
   const size_t at = frag ? ((size_t)(row >> 5) * (kTileRows * kDim) + (k0 >> 4) * 512u + (((k0 >> 3) & 1u) * 32u + (row & 31u)) * 8u + (k0 & 7u)) / 2u
                          : (size_t)row * (kDim / 2u) + l;
   reinterpret_cast<uint32_t*>(dst)[at] =
-      (uint32_t)bf16_rne(a * scale) | ((uint32_t)bf16_rne(b * scale) << 16);
+      (uint32_t)tod::l2_bf16_rne(a * scale) | ((uint32_t)tod::l2_bf16_rne(b * scale) << 16);
   float s = a * a + b * b;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
@@ -37,8 +33,7 @@ __global__ __launch_bounds__(256) void l2_prepare_kernel(const float* __restrict
     norm2[row] = n2;
     if (row < n && max_norm2_bits) atomicMax(max_norm2_bits, __float_as_uint(s));
     if (rmax2_bits) {
-      const float nq = sqrtf(n2), rmax = sqrtf(__uint_as_float(*rmax2_bits));
-      eps[row] = 0.0079345703125f * nq * rmax + 6.103515625e-05f * (nq + rmax) * (nq + rmax);   // 2^-7 (1 + 2^-6), 2^-14
+      eps[row] = tod::l2_eps(n2, __uint_as_float(*rmax2_bits));
       zero_cnt[row] = 0u;
     }
   }

@@ -17,13 +17,17 @@
 //   sqrtf is correctly rounded, so its result is >= sqrt(d2) / (1 + 2^-24):       sqrt(d2) <= radius (1 + 2^-24), and
 //       d2 <= radius^2 (1 + 2^-24)^2 < radius^2 (1 + 2^-22) <= r2_up              r2_up = radius^2 (1 + 2^-21), formed in binary64
 //                                                                                  (its own rounding, 2^-52, is far inside the slack)
-//   l2.hip's bound, |score + |q|^2 - d2| <= eps(q) with |q|^2 the exact norm, gives for such a row
+//   the filter's bound (l2_bound.h: eps(q) = 2^-6 (1 + 2^-6) |q| Rmax + 2^-14 (|q| + Rmax)^2, the bf16 rounding of every component by
+//   up to 2^-8 of its magnitude and every f32 rounding included), |score + |q|^2 - d2| <= eps(q) with |q|^2 the exact norm, gives for
+//   such a row
 //       score <= d2 - |q|^2 + eps(q) <= r2_up - |q|^2 + eps(q)
 //   thr(q) = r2_up - |q|^2 + 2 eps(q), rounded UP to binary32. |q|^2 is summed here in binary64 from the f32 query (relative error
 //   below 2^-45; the f32 value the prepare kernel leaves behind is a shuffle-tree sum with a rounding of its own and is not used).
 //   The second eps is the band pass 2 of the k-NN call uses too: it covers the f32 rounding inside eps(q) itself (|q| and Rmax
 //   come from f32 norms, relative error ~2^-21 of eps) and the binary64 roundings above, each many orders below eps(q).
-//   A looser threshold costs candidates, never rows.
+//   A looser threshold costs candidates, never rows. (This one-sided use needs a single eps; the second one is slack. It is what kept
+//   this search exact while eps was half of what bf16 rounding can do -- 2^-7 for 2^-6, the one-sided error reached 1.9 of it --
+//   and tests/test_l2_numerics_gpu.py::test_the_radius_search_on_the_triple pins it.)
 // Padding DB rows carry the norm 3e38 and a zero bf16 image, so their score is 3e38. A threshold at or beyond kThrMax = 1e38 is not
 // used: such a query (a radius whose square leaves the range in which scores separate real rows from padding) collects nothing in
 // the DB pass and is FLAGGED, and LS answers it from the rows themselves -- exact whatever the radius, and no padding row is ever a
