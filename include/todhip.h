@@ -285,6 +285,57 @@ int todhip_match_l2_radius_device(todhip_ctx*, const void* d_q_desc, uint32_t nq
                                   void* d_counts /*[nq] u32*/, void* d_matches /*[nq*max_per_query]*/,
                                   void* d_matches_xyz /*[nq*max_per_query*3]*/, void* d_in_radius /*[nq] u32, may be NULL*/);
 
+/* The float searches over a sharded DB, merged on the device: what todhip_match_shard_device + todhip_merge_shards_device[_on] and
+ * todhip_match_radius_shard_device + todhip_merge_radius_shards_device[_on] (below) are to the Hamming searches. A float DB
+ * (desc_bytes == 512) loads with any shard_count: the shard's rows alone are resident and prepared (their bf16 image, norms and
+ * Rmax), model points and the object table are complete, an empty shard is legal. todhip_match_l2* and todhip_match_l2_radius* stay
+ * TODHIP_EINVAL on a context that holds one shard of several; these six calls serve it (and an unsharded context, as one shard).
+ * Definition (exact, deterministic):
+ *   key          = (IEEE binary32 bits of d2) << 32 | row of the full DB, d2 the defining sequential f32 sum of todhip_match_l2.
+ *                  d2 >= 0, so the order of the bits is the order of the values; row < 2^32, so the row cannot carry into the distance.
+ *   k-NN, step 1 (todhip_match_l2_shard_device), on every rank: row q of d_keys, nq x k u64, holds the shard's min(k, shard rows)
+ *                  nearest rows in key order, UINT64_MAX behind them. The plain top-k: the call takes no radius. EVERY slot is
+ *                  written (the buffer goes through a collective as it is); a shard without rows writes padding only.
+ *   k-NN, step 2 (todhip_merge_l2_shards_device[_on]), on the rank that owns the queries: d_keys_all is [n_shards][nq][k], step 1's
+ *                  outputs. Per query the k smallest of the n_shards x k keys, cut at the first sqrtf(d2) > radius, each resolved as
+ *                  todhip_match_l2_device resolves it (imgIdx, trainIdx, distance = sqrtf(d2), the gathered model point); fixed
+ *                  stride k, slots behind counts[q] not written.
+ *   radius, step 1 (todhip_match_l2_radius_shard_device): row q of d_keys, nq x (max_per_query + 1) u64, holds the first
+ *                  min(|R_s(q)|, max_per_query) keys of R_s(q) -- the rows of R(q) in this shard -- ascending, UINT64_MAX behind
+ *                  them, and |R_s(q)| as a u64 in slot max_per_query: the row todhip_match_radius_shard_device writes. Every slot
+ *                  is written; a shard without rows writes padding and count 0.
+ *   radius, step 2 (todhip_merge_l2_radius_shards_device[_on]): in_radius[q] = the sum of the shards' counts, counts[q] =
+ *                  min(in_radius[q], max_per_query), the matches the first counts[q] keys of the union in key order, resolved as
+ *                  todhip_match_l2_radius_device resolves them; fixed stride max_per_query, slots behind counts[q] not written.
+ *   Result: the merged outputs (counts, the kept slots of matches and xyz, in_radius) are byte for byte what todhip_match_l2_device
+ *   or todhip_match_l2_radius_device leaves on a context that holds the whole DB. Why: every shard's answer is its EXACT top-k or its
+ *   exact radius set -- the bf16 filter with the shard's own Rmax and eps(q), and whichever path the shard's row count selects (seed
+ *   and two GEMMs, one GEMM, the exact scan), only decide how the rows are found; the keys come from the defining d2 of each row --
+ *   a key among the first n of the union is among the first n of its own shard's list, and keys are unique over the shards because the
+ *   row is part of the key. The merge compares integers.
+ *   The merges read only the context's object table and model points (every rank holds the full DB's), so any rank's context will do,
+ *   and the _on forms may run on a stream of the caller's beside a shard call that is in flight on the context's own, as
+ *   todhip_merge_shards_device_on does; the caller orders that stream against the producer of d_keys_all and the consumers.
+ *   The ratio test, LSH, selections and the cross-check do not apply to float DBs, sharded or not.
+ * TODHIP_EINVAL: a null pointer other than d_in_radius, nq == 0, k == 0 or > 8, max_per_query == 0 or > 1024, n_shards == 0 or > 64,
+ * a radius that is not > 0 (or, for the radius pair's step 1, not finite), a DB that is not float. TODHIP_ENODB without a DB.
+ * todhip_get_counters: step 1 sets last_nq and last_k (k, or max_per_query); todhip_set_kernel_timing brackets step 1's DB pass as
+ * in the unsharded calls. The exchange carries world * nq * k * 8 or world * nq * (max_per_query + 1) * 8 bytes per rank and step
+ * (DESIGN 6n). */
+int todhip_match_l2_shard_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t k, void* d_keys /*[nq*k] u64*/);
+int todhip_merge_l2_shards_device(todhip_ctx*, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k, float radius,
+                                  void* d_counts /*[nq] u32*/, void* d_matches /*[nq*k]*/, void* d_matches_xyz /*[nq*k*3]*/);
+int todhip_merge_l2_shards_device_on(todhip_ctx*, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k,
+                                     float radius, void* d_counts, void* d_matches, void* d_matches_xyz);
+int todhip_match_l2_radius_shard_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, float radius, uint32_t max_per_query,
+                                        void* d_keys /*[nq*(max_per_query+1)] u64*/);
+int todhip_merge_l2_radius_shards_device(todhip_ctx*, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t max_per_query,
+                                         void* d_counts /*[nq] u32*/, void* d_matches /*[nq*max_per_query]*/,
+                                         void* d_matches_xyz /*[nq*max_per_query*3]*/, void* d_in_radius /*[nq] u32, may be NULL*/);
+int todhip_merge_l2_radius_shards_device_on(todhip_ctx*, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq,
+                                            uint32_t max_per_query, void* d_counts, void* d_matches, void* d_matches_xyz,
+                                            void* d_in_radius /*may be NULL*/);
+
 /* Sharded form, step 1: this shard's top-k per query as keys (distance << 32 | global_row), ascending,
  * UINT64_MAX padded; d_keys[nq*k]. The ranks exchange these with one RCCL all-gather. `radius` is the radius of
  * step 2: rows farther away never survive the truncation of DescriptorMatcher.cpp:212-220, so the search is

@@ -102,6 +102,8 @@ EXPORTS = [
     "todhip_match_l2_radius", "todhip_match_l2_radius_device",
     "todhip_test_draw_table", "todhip_test_kabsch",
     "todhip_cross_check_device", "todhip_set_cross_check", "todhip_pipeline_set_cross_check",
+    "todhip_match_l2_shard_device", "todhip_merge_l2_shards_device", "todhip_merge_l2_shards_device_on",
+    "todhip_match_l2_radius_shard_device", "todhip_merge_l2_radius_shards_device", "todhip_merge_l2_radius_shards_device_on",
 ]
 
 MAX_TRAIN_BATCH_VIEWS = 64
@@ -201,6 +203,17 @@ def lib():
             L.todhip_match_l2_radius.restype = C.c_int
             L.todhip_match_l2_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 4
             L.todhip_match_l2_radius_device.restype = C.c_int
+        if hasattr(L, "todhip_match_l2_shard_device"):                # (as above)
+            u32, vp, f32 = C.c_uint32, C.c_void_p, C.c_float
+            L.todhip_match_l2_shard_device.argtypes, L.todhip_match_l2_shard_device.restype = [vp, vp, u32, u32, vp], C.c_int
+            L.todhip_merge_l2_shards_device.argtypes, L.todhip_merge_l2_shards_device.restype = [vp, vp, u32, u32, u32, f32, vp, vp, vp], C.c_int
+            L.todhip_merge_l2_shards_device_on.argtypes = [vp, vp, vp, u32, u32, u32, f32, vp, vp, vp]
+            L.todhip_merge_l2_shards_device_on.restype = C.c_int
+            L.todhip_match_l2_radius_shard_device.argtypes, L.todhip_match_l2_radius_shard_device.restype = [vp, vp, u32, f32, u32, vp], C.c_int
+            L.todhip_merge_l2_radius_shards_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp]
+            L.todhip_merge_l2_radius_shards_device.restype = C.c_int
+            L.todhip_merge_l2_radius_shards_device_on.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
+            L.todhip_merge_l2_radius_shards_device_on.restype = C.c_int
         if hasattr(L, "todhip_test_draw_table"):                      # (as above)
             L.todhip_test_draw_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
             L.todhip_test_draw_table.restype = C.c_int
@@ -493,6 +506,38 @@ class Context:
         """Device-pointer form (ints from tensor.data_ptr()), fixed stride max_per_query; d_in_radius may be None."""
         _check(lib().todhip_match_l2_radius_device(self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius),
                "todhip_match_l2_radius_device")
+
+    def match_l2_shard_device(self, d_q, nq, k, d_keys):
+        """The sharded float k-NN search, step 1: this context's shard -> d_keys u64[nq, k] (ascending keys
+        binary32 bits of d2 << 32 | row of the full DB, UINT64_MAX padding; the plain top-k, every slot written)."""
+        _check(lib().todhip_match_l2_shard_device(self._h, d_q, nq, k, d_keys), "todhip_match_l2_shard_device")
+
+    def merge_l2_shards_device(self, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz, stream=None):
+        """Step 2: d_keys_all u64[n_shards, nq, k] -> what match_l2_device leaves on the unsharded DB. stream: a HIP stream of the
+        caller's instead of the context's (the merge only reads the context's immutable tables)."""
+        if stream is None:
+            _check(lib().todhip_merge_l2_shards_device(self._h, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz),
+                   "todhip_merge_l2_shards_device")
+        else:
+            _check(lib().todhip_merge_l2_shards_device_on(self._h, stream, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz),
+                   "todhip_merge_l2_shards_device_on")
+
+    def match_l2_radius_shard_device(self, d_q, nq, radius, max_per_query, d_keys):
+        """The sharded float radius search, step 1: this context's shard -> d_keys u64[nq, max_per_query + 1] (ascending keys,
+        UINT64_MAX padding, the shard's exact count in the last slot; every slot written)."""
+        _check(lib().todhip_match_l2_radius_shard_device(self._h, d_q, nq, radius, max_per_query, d_keys),
+               "todhip_match_l2_radius_shard_device")
+
+    def merge_l2_radius_shards_device(self, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None,
+                                      stream=None):
+        """Step 2: d_keys_all u64[n_shards, nq, max_per_query + 1] -> what match_l2_radius_device leaves on the unsharded DB.
+        stream: as merge_l2_shards_device."""
+        if stream is None:
+            _check(lib().todhip_merge_l2_radius_shards_device(self._h, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz,
+                                                              d_in_radius), "todhip_merge_l2_radius_shards_device")
+        else:
+            _check(lib().todhip_merge_l2_radius_shards_device_on(self._h, stream, d_keys_all, n_shards, nq, max_per_query, d_counts,
+                                                                 d_matches, d_xyz, d_in_radius), "todhip_merge_l2_radius_shards_device_on")
 
     def match_device(self, d_q, nq, k, radius, d_counts, d_matches, d_xyz):
         """Device-pointer form (ints from tensor.data_ptr()). d_q: nq rows of the DB's width, 32 or 64 bytes (desc_bytes()) -- the

@@ -194,9 +194,9 @@ __global__ __launch_bounds__(256) void spans_kernel(const float* __restrict__ pt
 static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_objs, uint32_t desc_bytes,
                         uint32_t shard_rank, uint32_t shard_count, float* spans_out, bool device_src) {
   if (!ctx || (!objs && n_objs) || shard_count == 0 || shard_rank >= shard_count) return TODHIP_EINVAL;
-  // 32: 256-bit binary descriptors (ORB), 64: 512-bit ones (BRISK, FREAK; match_wide.hip), Hamming; 512: 128 x f32 (SIFT-like), L2 --
-  // one device only
-  if (desc_bytes != 32 && desc_bytes != 64 && !(desc_bytes == 512 && shard_count == 1)) return TODHIP_EINVAL;
+  // 32: 256-bit binary descriptors (ORB), 64: 512-bit ones (BRISK, FREAK; match_wide.hip), Hamming; 512: 128 x f32 (SIFT-like), L2
+  // (a shard of several is searched by the sharded forms alone, l2_sharded.h)
+  if (desc_bytes != 32 && desc_bytes != 64 && desc_bytes != 512) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
   tod_view_reset(ctx);                                      // todhip_db_select_objects: a load selects all objects
   tod_db_rows_written(ctx);                                 // the fp4 copy of the old rows is stale (match_launch.h builds the next)

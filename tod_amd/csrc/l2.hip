@@ -24,7 +24,7 @@
 //   pass 3  exact d2 of the candidates in the defining order (sequential f32, no fma), k smallest by (d2, row);
 //           a query whose candidate lists overflowed is redone by an exact scan of the whole DB
 //
-// One translation unit, headers by concern; this file is the host side (workspace, launches, the four C entry points):
+// One translation unit, headers by concern; this file is the host side (workspace, launches, the C entry points):
 //   l2_plan.h     host, no HIP: shared constants, L2Knobs (the environment), L2Plan = geometry, seed-pass decision, buffer sizes
 //   l2_bound.h    host and device, plain C++: the bf16 rounding and eps(q), with the derivation
 //   l2_prepare.h  l2_prepare_kernel: bf16 images of the DB (A-fragment order) and of the queries, norms, eps
@@ -32,6 +32,7 @@
 //                 the accumulator IS the score; CandSink and the epilogues of passes 0, 1, 2
 //   l2_refine.h   l2_threshold_kernel, pass 3 (l2_rerank_kernel, l2_exact_scan_kernel), l2_finalize_kernel, shared device helpers
 //   l2_radius.h   the radius search's kernels (todhip_match_l2_radius*): LT, LR, LS, LE around the same DB pass
+//   l2_sharded.h  the sharded forms' kernels (todhip_match_l2[_radius]_shard_device, todhip_merge_l2[_radius]_shards_device[_on]): SK, SR, LK, LM
 //   l2_trace.h    host: the wave-trace report of TODHIP_L2_TRACE
 #include <cfloat>
 #include <cmath>
@@ -47,6 +48,7 @@
 #include "l2_gemm.h"
 #include "l2_refine.h"
 #include "l2_radius.h"
+#include "l2_sharded.h"
 #include "l2_trace.h"
 
 namespace {
@@ -60,6 +62,7 @@ struct L2Ws : TodWs {
   DevBuf slots, slot_cnt, cand, cand_cnt;     // CandSink (l2_gemm.h); cand_cnt is zeroed by the query preparation
   DevBuf flags;                               // per query: 1 = its candidate lists overflowed (or scan_marks said so), the exact scan answers it
   DevBuf part, keys;                          // passes 0 and 1: [partition][query][kTop] scores (pass 2: the wave trace); the result keys
+  DevBuf shard_counts, shard_in_radius;       // per query: what LR / LS count for the radius search's sharded form (SR reads them)
 };
 
 const L2Knobs& l2_knobs() {                                 // the environment, read once
@@ -148,10 +151,10 @@ int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k) {
   return TODHIP_OK;
 }
 
-// The radius search up to its outputs: LT, the DB pass, LR, LS, LE (l2_radius.h). d_counts / d_in_radius: device memory (d_in_radius
-// may be null); d_matches / d_xyz: device memory, or pinned host memory for the matches of the host form.
-int l2_radius_search(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radius, uint32_t mpq, uint32_t* d_counts,
-                     todhip_dmatch* d_matches, float* d_xyz, uint32_t* d_in_radius) {
+// The radius search up to its keys: LT, the DB pass, LR, LS (l2_radius.h) over the resident rows (there is at least one). ws->keys:
+// [nq][mpq], the first d_counts[q] of a row valid, rows numbered within the shard. d_counts / d_in_radius: device memory (d_in_radius
+// may be null).
+int l2_radius_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radius, uint32_t mpq, uint32_t* d_counts, uint32_t* d_in_radius) {
   TOD_HIP(hipSetDevice(ctx->device));
   L2Ws* ws = tod_ws<L2Ws>(ctx);
   hipStream_t st = ctx->stream;
@@ -171,6 +174,17 @@ int l2_radius_search(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radiu
                      ws->keys.as<uint64_t>(), d_counts, d_in_radius, ws->flags.as<uint32_t>());
   hipLaunchKernelGGL(l2_radius_scan_kernel, dim3(nq), dim3(256), 0, st, d_q, db, (uint32_t)ctx->shard_rows, ws->flags.as<uint32_t>(), radius,
                      mpq, ws->keys.as<uint64_t>(), d_counts, d_in_radius);
+  TOD_HIP(hipGetLastError());
+  return TODHIP_OK;
+}
+
+// The radius search up to its outputs: l2_radius_keys, then LE. d_matches / d_xyz: device memory, or pinned host memory for the
+// matches of the host form.
+int l2_radius_search(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radius, uint32_t mpq, uint32_t* d_counts,
+                     todhip_dmatch* d_matches, float* d_xyz, uint32_t* d_in_radius) {
+  if (int rc = l2_radius_keys(ctx, d_q, nq, radius, mpq, d_counts, d_in_radius)) return rc;
+  L2Ws* ws = tod_ws<L2Ws>(ctx);
+  hipStream_t st = ctx->stream;
   const size_t slots = (size_t)nq * mpq;
   hipLaunchKernelGGL(l2_radius_emit_kernel, dim3((uint32_t)((slots + 255u) / 256u)), dim3(256), 0, st, ws->keys.as<uint64_t>(), d_counts, nq,
                      mpq, ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), d_matches, d_xyz);
@@ -178,15 +192,46 @@ int l2_radius_search(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radiu
   return TODHIP_OK;
 }
 
-// the DB every float call needs: not empty, 128 x f32, not sharded
-int l2_db_check(const todhip_ctx* ctx) {
+// the DB every float call needs: not empty, 128 x f32; the unsharded calls: the whole of it resident
+int l2_db_check(const todhip_ctx* ctx, bool sharded = false) {
   if (ctx->total_rows == 0) return TODHIP_ENODB;
-  return ctx->desc_bytes != kDim * 4u || ctx->shard_rows != ctx->total_rows ? TODHIP_EINVAL : TODHIP_OK;
+  return ctx->desc_bytes != kDim * 4u || (!sharded && ctx->shard_rows != ctx->total_rows) ? TODHIP_EINVAL : TODHIP_OK;
 }
 
-int l2_radius_args(const todhip_ctx* ctx, uint32_t nq, float radius, uint32_t mpq) {
+int l2_radius_args(const todhip_ctx* ctx, uint32_t nq, float radius, uint32_t mpq, bool sharded = false) {
   if (nq == 0 || mpq == 0 || mpq > kL2MaxPerQuery || !(radius > 0.f) || !std::isfinite(radius)) return TODHIP_EINVAL;
-  return l2_db_check(ctx);
+  return l2_db_check(ctx, sharded);
+}
+
+// LK or LM on `stream` (null: the context's) behind the argument checks of the two merges. They read the context's object table and
+// model points only. KNN: width = k and the radius cuts; otherwise width = max_per_query and the keys carry the shards' counts.
+template <bool KNN>
+int l2_merge_shards(todhip_ctx* ctx, hipStream_t stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t width, float radius,
+                    void* d_counts, void* d_matches, void* d_xyz, void* d_in_radius) {
+  if (!ctx || !d_keys_all || !d_counts || !d_matches || !d_xyz) return TODHIP_EINVAL;
+  if (nq == 0 || width == 0 || width > (KNN ? kTop : kL2MaxPerQuery) || n_shards == 0 || n_shards > kMaxMergeShards) return TODHIP_EINVAL;
+  if (KNN && !(radius > 0.f)) return TODHIP_EINVAL;
+  if (int rc = l2_db_check(ctx, true)) return rc;
+  TOD_HIP(hipSetDevice(ctx->device));
+  hipStream_t st = stream ? stream : ctx->stream;
+  const uint64_t* keys = reinterpret_cast<const uint64_t*>(d_keys_all);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(d_counts);
+  todhip_dmatch* matches = reinterpret_cast<todhip_dmatch*>(d_matches);
+  float* xyz = reinterpret_cast<float*>(d_xyz);
+  if (KNN) {
+    dispatch_k(width, [&](auto kc) {
+      hipLaunchKernelGGL(l2_merge_knn_kernel<decltype(kc)::value>, dim3((nq + kMergeBlock - 1u) / kMergeBlock), dim3(kMergeBlock), 0, st, keys,
+                         n_shards, nq, radius, ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), counts, matches, xyz);
+      return TODHIP_OK;
+    });
+  } else {
+    const ShardMergeGrid g = shard_merge_grid(n_shards, nq, width);
+    hipLaunchKernelGGL(g.staged ? l2_merge_radius_kernel<true> : l2_merge_radius_kernel<false>, dim3(g.blocks), dim3(kMergeBlock), 0, st, keys,
+                       n_shards, nq, width, g.qpb, ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), counts,
+                       reinterpret_cast<uint32_t*>(d_in_radius), matches, xyz);
+  }
+  TOD_HIP(hipGetLastError());
+  return TODHIP_OK;
 }
 
 }  // namespace
@@ -207,6 +252,73 @@ int tod_l2_db_prepare(todhip_ctx* ctx) {
 }
 
 extern "C" {
+
+int todhip_match_l2_shard_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint32_t k, void* d_keys) {
+  if (!ctx || !d_q_desc || !d_keys || nq == 0 || k == 0 || k > kTop) return TODHIP_EINVAL;
+  int rc = l2_db_check(ctx, true);
+  if (rc != TODHIP_OK) return rc;
+  TOD_HIP(hipSetDevice(ctx->device));
+  const uint64_t* keys = nullptr;                           // no resident row: padding only
+  if (ctx->shard_rows != 0) {
+    rc = l2_keys(ctx, reinterpret_cast<const float*>(d_q_desc), nq, k);
+    if (rc != TODHIP_OK) return rc;
+    keys = tod_ws<L2Ws>(ctx)->keys.as<uint64_t>();
+  }
+  const size_t slots = (size_t)nq * k;
+  hipLaunchKernelGGL(l2_shard_keys_kernel, dim3((uint32_t)((slots + 255u) / 256u)), dim3(256), 0, ctx->stream, keys, slots,
+                     (uint32_t)ctx->shard_first, reinterpret_cast<uint64_t*>(d_keys));
+  TOD_HIP(hipGetLastError());
+  ctx->counters.last_nq = nq; ctx->counters.last_k = k;
+  return TODHIP_OK;
+}
+
+int todhip_merge_l2_shards_device_on(todhip_ctx* ctx, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k,
+                                     float radius, void* d_counts, void* d_matches, void* d_matches_xyz) {
+  if (!ctx || !hip_stream) return TODHIP_EINVAL;
+  return l2_merge_shards<true>(ctx, reinterpret_cast<hipStream_t>(hip_stream), d_keys_all, n_shards, nq, k, radius, d_counts, d_matches,
+                               d_matches_xyz, nullptr);
+}
+
+int todhip_merge_l2_shards_device(todhip_ctx* ctx, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t k, float radius,
+                                  void* d_counts, void* d_matches, void* d_matches_xyz) {
+  return l2_merge_shards<true>(ctx, nullptr, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_matches_xyz, nullptr);
+}
+
+int todhip_match_l2_radius_shard_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, float radius, uint32_t max_per_query,
+                                        void* d_keys) {
+  if (!ctx || !d_q_desc || !d_keys) return TODHIP_EINVAL;
+  int rc = l2_radius_args(ctx, nq, radius, max_per_query, true);
+  if (rc != TODHIP_OK) return rc;
+  TOD_HIP(hipSetDevice(ctx->device));
+  L2Ws* ws = tod_ws<L2Ws>(ctx);
+  const uint32_t* d_in = nullptr;                           // no resident row: every query's count is 0
+  if (ctx->shard_rows != 0) {
+    TOD_HIP(ws->shard_counts.reserve((size_t)nq * sizeof(uint32_t)));
+    TOD_HIP(ws->shard_in_radius.reserve((size_t)nq * sizeof(uint32_t)));
+    rc = l2_radius_keys(ctx, reinterpret_cast<const float*>(d_q_desc), nq, radius, max_per_query, ws->shard_counts.as<uint32_t>(),
+                        ws->shard_in_radius.as<uint32_t>());
+    if (rc != TODHIP_OK) return rc;
+    d_in = ws->shard_in_radius.as<uint32_t>();
+  }
+  const size_t slots = (size_t)nq * (max_per_query + 1u);
+  hipLaunchKernelGGL(l2_radius_shard_keys_kernel, dim3((uint32_t)((slots + 255u) / 256u)), dim3(256), 0, ctx->stream, ws->keys.as<uint64_t>(),
+                     ws->shard_counts.as<uint32_t>(), d_in, nq, max_per_query, (uint32_t)ctx->shard_first, reinterpret_cast<uint64_t*>(d_keys));
+  TOD_HIP(hipGetLastError());
+  ctx->counters.last_nq = nq; ctx->counters.last_k = max_per_query;
+  return TODHIP_OK;
+}
+
+int todhip_merge_l2_radius_shards_device_on(todhip_ctx* ctx, void* hip_stream, const void* d_keys_all, uint32_t n_shards, uint32_t nq,
+                                            uint32_t max_per_query, void* d_counts, void* d_matches, void* d_matches_xyz, void* d_in_radius) {
+  if (!ctx || !hip_stream) return TODHIP_EINVAL;
+  return l2_merge_shards<false>(ctx, reinterpret_cast<hipStream_t>(hip_stream), d_keys_all, n_shards, nq, max_per_query, 0.f, d_counts,
+                                d_matches, d_matches_xyz, d_in_radius);
+}
+
+int todhip_merge_l2_radius_shards_device(todhip_ctx* ctx, const void* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t max_per_query,
+                                         void* d_counts, void* d_matches, void* d_matches_xyz, void* d_in_radius) {
+  return l2_merge_shards<false>(ctx, nullptr, d_keys_all, n_shards, nq, max_per_query, 0.f, d_counts, d_matches, d_matches_xyz, d_in_radius);
+}
 
 int todhip_match_l2_radius_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, float radius, uint32_t max_per_query, void* d_counts,
                                   void* d_matches, void* d_matches_xyz, void* d_in_radius) {

@@ -31,6 +31,7 @@
 
 #include "ctx.h"
 #include "row_ops.h"
+#include "shard_merge.h"
 
 namespace {
 
@@ -238,28 +239,9 @@ __global__ __launch_bounds__(kBlock) void radius_shard_keys_kernel(const uint64_
   keys[slot] = v;
 }
 
-// keys of an ascending list of n (padding ~0 at its end) that are below `key`
-__device__ __forceinline__ uint32_t keys_below(const uint64_t* lst, uint32_t n, uint64_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (lst[mid] < key) lo = mid + 1u; else hi = mid;
-  }
-  return lo;
-}
-
-// M1, the merge of the shards' radius answers: keys_all[n_shards][nq][max_per_query + 1] as S1 writes them. A rank merge -- the keys
-// of a query are unique over the shards (the row is part of the key), so element j of shard s stands at position
-// j + sum over t != s of (keys of shard t below it), one binary search per other shard; the padding sorts last, so a search runs over
-// all max_per_query slots. A list that was cut at max_per_query answers max_per_query for a key behind its cut; the position is then
-// >= max_per_query, as the true one is. An element whose position is below max_per_query is one of the query's first max_per_query:
-// store_match puts it there. No sort, no atomics, each output slot has one writer.
-// thread = (shard, slot) element of a query; E = n_shards * max_per_query elements per query. A workgroup takes qpb queries:
-// floor(256 / E) while E <= 128 (max_per_query = 5 on two shards: 25 queries), else one, its threads striding over the elements.
-// STAGED: the workgroup's lists fit kMergeLdsKeys keys and are searched in LDS; otherwise (up to 64 x 1024) in global memory.
-constexpr uint32_t kMergeLdsKeys = 4096;                    // 32 KB
-constexpr uint32_t kMaxMergeShards = 64;
-
+// M1, the merge of the shards' radius answers: keys_all[n_shards][nq][max_per_query + 1] as S1 writes them. The rank merge by binary
+// search of shard_merge.h (shard_rank_merge: its comment says why a position below max_per_query is right, how the threads share
+// the elements of qpb queries, and what STAGED means), shared with the float keys' merge (l2_sharded.h); store_match resolves a key.
 template <bool STAGED>
 __global__ __launch_bounds__(kBlock) void radius_merge_kernel(const uint64_t* __restrict__ keys_all, uint32_t n_shards, uint32_t nq,
                                                               uint32_t max_per_query, uint32_t qpb, const uint32_t* __restrict__ obj_off,
@@ -268,36 +250,9 @@ __global__ __launch_bounds__(kBlock) void radius_merge_kernel(const uint64_t* __
                                                               float* __restrict__ xyz) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
   __shared__ uint64_t s_keys[STAGED ? kMergeLdsKeys : 1];
-  const uint32_t tid = threadIdx.x, q0 = blockIdx.x * qpb;
-  const uint32_t stride = max_per_query + 1u, elems = n_shards * max_per_query;
-  const uint32_t n_here = min(qpb, nq - q0) * elems;        // elements of this workgroup's queries (q0 < nq by the grid)
-  if (tid < qpb && q0 + tid < nq) {                         // the count slots
-    uint64_t n = 0;
-    for (uint32_t s = 0; s < n_shards; ++s) n += keys_all[((size_t)s * nq + q0 + tid) * stride + max_per_query];
-    counts[q0 + tid] = n < max_per_query ? (uint32_t)n : max_per_query;
-    if (in_radius) in_radius[q0 + tid] = (uint32_t)n;
-  }
-  if (STAGED) {                                             // image [query][shard][slot], n_here <= kMergeLdsKeys
-    for (uint32_t i = tid; i < n_here; i += kBlock) {
-      const uint32_t ql = i / elems, e = i % elems, s = e / max_per_query, j = e % max_per_query;
-      s_keys[i] = keys_all[((size_t)s * nq + q0 + ql) * stride + j];
-    }
-    __syncthreads();
-  }
-  for (uint32_t i = tid; i < n_here; i += kBlock) {
-    const uint32_t ql = i / elems, e = i % elems, s = e / max_per_query, j = e % max_per_query;
-    const uint32_t qi = q0 + ql;
-    const uint64_t key = STAGED ? s_keys[i] : keys_all[((size_t)s * nq + qi) * stride + j];
-    if (key == ~0ull) continue;                             // padding
-    uint32_t pos = j;
-    for (uint32_t t = 0; t < n_shards && pos < max_per_query; ++t) {
-      if (t == s) continue;
-      if constexpr (STAGED) pos += keys_below(s_keys + ql * elems + t * max_per_query, max_per_query, key);
-      else pos += keys_below(keys_all + ((size_t)t * nq + qi) * stride, max_per_query, key);
-    }
-    if (pos < max_per_query)
-      store_match(qi, (uint32_t)(key >> 32), (uint32_t)key, (size_t)qi * max_per_query + pos, obj_off, n_objs, pts, matches, xyz);
-  }
+  shard_rank_merge<STAGED>(keys_all, n_shards, nq, max_per_query, qpb, counts, in_radius, s_keys, [&](uint64_t key, uint32_t qi, size_t at) {
+    store_match(qi, (uint32_t)(key >> 32), (uint32_t)key, at, obj_off, n_objs, pts, matches, xyz);
+  });
 }
 
 template <int QT>
@@ -399,10 +354,9 @@ int radius_shard_keys(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t ra
 int radius_merge(todhip_ctx* ctx, hipStream_t stream, const uint64_t* d_keys_all, uint32_t n_shards, uint32_t nq, uint32_t mpq,
                  uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz, uint32_t* d_in_radius) {
   TOD_HIP(hipSetDevice(ctx->device));
-  const uint32_t elems = n_shards * mpq;                    // <= 64 * 1024
-  const uint32_t qpb = elems <= kBlock / 2 ? kBlock / elems : 1u;
-  auto kern = qpb * elems <= kMergeLdsKeys ? radius_merge_kernel<true> : radius_merge_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((nq + qpb - 1u) / qpb), dim3(kBlock), 0, stream ? stream : ctx->stream, d_keys_all, n_shards, nq, mpq, qpb,
+  const ShardMergeGrid g = shard_merge_grid(n_shards, nq, mpq);
+  auto kern = g.staged ? radius_merge_kernel<true> : radius_merge_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(kBlock), 0, stream ? stream : ctx->stream, d_keys_all, n_shards, nq, mpq, g.qpb,
                      ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), d_counts, d_in_radius, d_matches, d_xyz);
   TOD_HIP(hipGetLastError());
   return TODHIP_OK;

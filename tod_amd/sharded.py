@@ -19,6 +19,11 @@ todhip_merge_radius_shards_device[_on]): a key row is then max_per_qu
 the radius, max_per_query + 1 wide, and the merge returns every query's nearest max_per_query rows within the radius and
 in_radius. The choreography does not change: the key rows are opaque to it.
 
+A float DB (128 x f32 rows, L2) goes through the same steps: `ShardedMatcher(desc_bytes=512)` gathers the float queries
+as bytes, `GpuOps(metric="l2")` calls todhip_match_l2_shard_device + todhip_merge_l2_shards_device[_on], or with `max_per_query`
+todhip_match_l2_radius_shard_device + todhip_merge_l2_radius_shards_device[_on]. A key is then binary32 bits of d2 << 32 | global row,
+the radius is a float, and the merged result is that of todhip_match_l2_device / todhip_match_l2_radius_device on the whole DB.
+
 `ShardedMatcher` is the ONE implementation of steps 1-4's choreography: bench.py runs it on the GPU (GpuOps: torch
 streams/events, RCCL through torch.distributed, libtodhip for the compute) and tests/test_sharded_cpu.py runs the same
 class over gloo with a CPU restatement as the compute. With `overlap` the collectives and the merge have a stream of
@@ -156,14 +161,17 @@ class GpuOps:
     over xGMI; "gloo" stages through the host -- rehearsals on a one-GPU box only), libtodhip for the compute. `out` is a
     dict of torch tensors: counts [n] i32, matches [n*k, 4] i32, xyz [n*k, 3] f32 (todhip_match_device's outputs). With
     max_per_query the two calls are the radius pair: matches and xyz have stride max_per_query instead of k and `out` also holds
-    in_radius [n] i32 (todhip_match_radius_device's outputs)."""
+    in_radius [n] i32 (todhip_match_radius_device's outputs). metric "l2": the context holds a shard of a float DB, the queries are
+    128 x f32 rows, `radius` is a float and the two calls are the float pairs (todhip_match_l2_device's or
+    todhip_match_l2_radius_device's outputs)."""
 
-    def __init__(self, ctx, compute_stream, comm_stream, backend, k, radius, max_per_query=None):
+    def __init__(self, ctx, compute_stream, comm_stream, backend, k, radius, max_per_query=None, metric="hamming"):
         import torch
         import torch.distributed as dist
+        assert metric in ("hamming", "l2")
         self.torch, self.dist = torch, dist
         self.ctx, self.compute, self.comm = ctx, compute_stream, comm_stream
-        self.backend, self.k, self.radius, self.max_per_query = backend, k, radius, max_per_query
+        self.backend, self.k, self.radius, self.max_per_query, self.metric = backend, k, radius, max_per_query, metric
         self.world = dist.get_world_size()
 
     def alloc(self, shape, dtype_name):
@@ -199,12 +207,27 @@ class GpuOps:
             out.view(-1).copy_(o.to(out.device))
 
     def match_shard(self, q_all, n, keys_out):
-        if self.max_per_query is not None:
+        if self.metric == "l2" and self.max_per_query is not None:
+            self.ctx.match_l2_radius_shard_device(q_all.data_ptr(), n, self.radius, self.max_per_query, keys_out.data_ptr())
+        elif self.metric == "l2":
+            self.ctx.match_l2_shard_device(q_all.data_ptr(), n, self.k, keys_out.data_ptr())
+        elif self.max_per_query is not None:
             self.ctx.match_radius_shard_device(q_all.data_ptr(), n, self.radius, self.max_per_query, keys_out.data_ptr())
         else:
             self.ctx.match_shard_device(q_all.data_ptr(), n, self.k, self.radius, keys_out.data_ptr())
 
+    def _merge_l2(self, keys_mine, n_shards, n, out, stream):
+        on = None if stream is self.compute else stream.cuda_stream
+        if self.max_per_query is not None:
+            self.ctx.merge_l2_radius_shards_device(keys_mine.data_ptr(), n_shards, n, self.max_per_query, out["counts"].data_ptr(),
+                                                   out["matches"].data_ptr(), out["xyz"].data_ptr(), out["in_radius"].data_ptr(), stream=on)
+        else:
+            self.ctx.merge_l2_shards_device(keys_mine.data_ptr(), n_shards, n, self.k, self.radius, out["counts"].data_ptr(),
+                                            out["matches"].data_ptr(), out["xyz"].data_ptr(), stream=on)
+
     def merge(self, keys_mine, n_shards, n, out, stream):
+        if self.metric == "l2":
+            return self._merge_l2(keys_mine, n_shards, n, out, stream)
         if self.max_per_query is not None:
             args = (keys_mine.data_ptr(), n_shards, n, self.max_per_query, out["counts"].data_ptr(), out["matches"].data_ptr(),
                     out["xyz"].data_ptr(), out["in_radius"].data_ptr())
