@@ -195,13 +195,18 @@ inline double ransac_k(double w) {
 }
 
 // launch(staged kernel, by-value kernel, extent) with eval_kernel's instantiations for the objects' width (wide: more than 512 matches)
-// in the two forms of passing argument sets (SlotsPtr<EvalArgs>: launch_many, Slots<EvalArgs>: launch_list), and the blocks one
+// in the two forms of passing argument sets (SlotsPtr<EvalArgs>: launch_many, Slots<EvalArgs>: launch_list), the pass (deferred: the
+// instantiations that carry the third tier; every argument set of such a launch has from_deferred set), and the blocks one
 // argument set needs: its iterations, or its deferred ones.
 template <class Launch>
 void pick_eval(bool wide, bool deferred, Launch launch) {
   auto extent = [deferred](const EvalArgs& a) { return dim3(deferred ? a.n_deferred : a.it_end - a.it_begin); };
-  if (wide) launch(eval_kernel<true, SlotsPtr<EvalArgs>>, eval_kernel<true>, extent);
-  else launch(eval_kernel<false, SlotsPtr<EvalArgs>>, eval_kernel<false>, extent);
+  typedef SlotsPtr<EvalArgs> P;
+  typedef Slots<EvalArgs> V;
+  if (wide && deferred) launch(eval_kernel<true, P, true>, eval_kernel<true, V, true>, extent);
+  else if (wide) launch(eval_kernel<true, P>, eval_kernel<true, V>, extent);
+  else if (deferred) launch(eval_kernel<false, P, true>, eval_kernel<false, V, true>, extent);
+  else launch(eval_kernel<false, P>, eval_kernel<false, V>, extent);
 }
 
 int set_big_lds_once(todhip_ctx* ctx) {
@@ -210,7 +215,12 @@ int set_big_lds_once(todhip_ctx* ctx) {
     const void* const big[] = {reinterpret_cast<const void*>(eval_kernel<false>), reinterpret_cast<const void*>(eval_kernel<true>),
                                reinterpret_cast<const void*>(eval_kernel<false, SlotsPtr<EvalArgs>>),
                                reinterpret_cast<const void*>(eval_kernel<true, SlotsPtr<EvalArgs>>),
+                               reinterpret_cast<const void*>(eval_kernel<false, Slots<EvalArgs>, true>),
+                               reinterpret_cast<const void*>(eval_kernel<true, Slots<EvalArgs>, true>),
+                               reinterpret_cast<const void*>(eval_kernel<false, SlotsPtr<EvalArgs>, true>),
+                               reinterpret_cast<const void*>(eval_kernel<true, SlotsPtr<EvalArgs>, true>),
                                reinterpret_cast<const void*>(clique_test_kernel<false>), reinterpret_cast<const void*>(clique_test_kernel<true>),
+                               reinterpret_cast<const void*>(clique_test_kernel<false, false>), reinterpret_cast<const void*>(clique_test_kernel<true, false>),
                                reinterpret_cast<const void*>(chain_kernel)};
     for (const void* f : big) TOD_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEvalLdsBig));
     TOD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sprint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,

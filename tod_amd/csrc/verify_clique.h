@@ -281,13 +281,15 @@ __device__ __forceinline__ bool colour_first_fit(const GateLds& L, uint16_t* lis
     const uint32_t cnt = min(64u, r - c0);
     const uint32_t vmine = (c0 + l) < r ? (uint32_t)list[c0 + l] : 0u;
     uint32_t rec = 0u;                                     // lane li: (class << 16 | index inside the class) of position c0 + li
-    // one vertex: `row` holds its adjacency row (loaded one vertex ahead), `next` receives the following vertex's
-    auto place = [&](const u64 (&row)[MWT], u64 (&next)[MWT], uint32_t li) {
+    // one vertex. Its adjacency row is loaded here, not one vertex ahead as colour_first_fit64 does: with two class sets a second
+    // row buffer made this rare form the register peak of the whole hypothesis kernel (16 registers at MWT = 8)
+    auto place = [&](uint32_t li) {
       const uint32_t v = rdlane(vmine, li);
+      u64 row[MWT];
       {
-        const u64* g = L.adjc + (size_t)rdlane(vmine, min(li + 1u, cnt - 1u)) * MWT;   // the chunk's last re-reads itself
+        const u64* g = L.adjc + (size_t)v * MWT;
 #pragma unroll
-        for (uint32_t w = 0; w < MWT; ++w) next[w] = g[w];
+        for (uint32_t w = 0; w < MWT; ++w) row[w] = g[w];
       }
       u64 hit = 0ull;
 #pragma unroll
@@ -328,18 +330,7 @@ __device__ __forceinline__ bool colour_first_fit(const GateLds& L, uint16_t* lis
       }
       if (l == li) rec = ((second ? k + 64u : k) << 16) | idx;
     };
-    u64 rowA[MWT], rowB[MWT];
-    {
-      const u64* g = L.adjc + (size_t)rdlane(vmine, 0u) * MWT;
-#pragma unroll
-      for (uint32_t w = 0; w < MWT; ++w) rowA[w] = g[w];
-    }
-    uint32_t li = 0;
-    for (; li + 2u <= cnt && !overflow; li += 2u) {        // two vertices per trip: the row buffers swap roles, nothing is copied
-      place(rowA, rowB, li);
-      place(rowB, rowA, li + 1u);
-    }
-    if (li < cnt && !overflow) place(rowA, rowB, li);
+    for (uint32_t li = 0; li < cnt && !overflow; ++li) place(li);
     if (overflow) return false;                            // nothing has been written to the list or to C
     if (c0 + l < r) L.keys[c0 + l] = rec;
   }
@@ -624,8 +615,9 @@ __device__ __forceinline__ uint32_t clique_search(GateLds L, uint32_t m, uint32_
 }
 
 // stand-alone clique search on an explicit graph (the reference's test/test_maximum_clique.cpp shape):
-// adj = m x MW bit matrix in global memory. One block of 64 threads.
-template <bool kGate>
+// adj = m x MW bit matrix in global memory. One block of 64 threads. kWide as eval_kernel's: false is the search of the
+// instantiation that evaluates objects of up to 512 matches, and a graph of up to 512 vertices is run through that one.
+template <bool kGate, bool kWide = true>
 __global__ __launch_bounds__(128) void clique_test_kernel(const u64* adj, uint32_t m, uint32_t minimal_size,
                                                          uint16_t* stack, uint32_t stack_cap, uint32_t lds_bytes,
                                                          uint32_t* out) {
@@ -643,6 +635,6 @@ __global__ __launch_bounds__(128) void clique_test_kernel(const u64* adj, uint32
   __syncthreads();
   int err = 0;
   uint32_t steps = 0;
-  const uint32_t q = clique_search<true, kGate>(L, m, minimal_size, stack, stack_cap, &err, &steps);
+  const uint32_t q = clique_search<kWide, kGate>(L, m, minimal_size, stack, stack_cap, &err, &steps);
   if (l == 0) { out[0] = q; out[1] = (uint32_t)err; out[2] = steps; }
 }

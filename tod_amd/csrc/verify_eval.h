@@ -213,25 +213,40 @@ __device__ __forceinline__ int32_t gate_eval(const EvalArgs& A, const WaveBitsT<
   return result;
 }
 
+// The argument set of a block. By value in kernarg it is scalar already. Staged in device memory (written by the host before the
+// launch, constant for the kernel's lifetime) it is read once through the constant address space into scalar registers: read
+// through the plain pointer its fields and their addresses sat in 23 vector registers across the clique search.
+template <class A, uint32_t N>
+__device__ __forceinline__ const A& arg_set(const Slots<A, N>& S, uint32_t i) { return S.a[i]; }
+template <class A>
+__device__ __forceinline__ A arg_set(const SlotsPtr<A>& S, uint32_t i) {
+  A r;
+  __builtin_memcpy(&r, (const __attribute__((address_space(4))) A*)(S.a + i), sizeof(A));
+  return r;
+}
+
 // launched with 64 threads; the bound is deliberately larger so that hipcc keeps __syncthreads() as a real,
 // convergent s_barrier (with a 64-thread bound it drops the barrier and may split the lanes of the wave)
 // kWide = false: objects of up to 512 matches (job.W <= 8), the launch's every slot, so P and F are one slice of 64 words;
 // true: any size, eight slices
-template <bool kWide, class H = Slots<EvalArgs>>
+// kDeferred: the second pass over the hypotheses the first one deferred (A.from_deferred, big LDS). Only it can take the third tier
+// (adjacency in global scratch), so only its instantiations carry gate_eval<true>: with both tiers inlined side by side the
+// first pass held 10 registers more across the search, and it is the first pass that has to start beside the DB pass's waves.
+template <bool kWide, class H = Slots<EvalArgs>, bool kDeferred = false>
 __global__ __launch_bounds__(128) void eval_kernel(H SL) {
   TOD_LATENCY_PRIO();   // latency-bound: win issue arbitration against the VALU-saturating matcher
-  const EvalArgs& A = SL.a[blockIdx.y];
+  const EvalArgs& A = arg_set(SL, blockIdx.y);
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const uint32_t l = lane_id();
   const ObjJob& job = A.job;
   const uint32_t W = job.W;
   uint16_t* stack = A.stacks + (size_t)blockIdx.x * A.stack_cap;
-  uint32_t n_items = A.from_deferred ? A.n_deferred : (A.it_end - A.it_begin);
+  uint32_t n_items = kDeferred ? A.n_deferred : (A.it_end - A.it_begin);
   if (A.n_items_dev) n_items = min(n_items, uni(*A.n_items_dev));
   {                                                        // one block = one hypothesis
     const uint32_t item = blockIdx.x;
     if (item >= n_items) return;
-    const uint32_t it = uni(A.from_deferred ? A.deferred[item] : (A.it_begin + item));
+    const uint32_t it = uni(kDeferred ? A.deferred[item] : (A.it_begin + item));
     const uint32_t s0 = uni(A.iter_samples[3 * it]), s1 = uni(A.iter_samples[3 * it + 1]),
                    s2 = uni(A.iter_samples[3 * it + 2]);
     if (s0 >= job.n || s1 >= job.n || s2 >= job.n) {       // corrupt draw table: report, never dereference
@@ -259,19 +274,21 @@ __global__ __launch_bounds__(128) void eval_kernel(H SL) {
       if (m <= kGateMinimal) {
         result = 0;                                        // :214-218
       } else if (gate_lds_bytes(m) > A.lds_bytes &&
-                 !(A.from_deferred && A.adjc_scratch && gate_small_bytes(m) <= A.lds_bytes &&
+                 !(kDeferred && A.adjc_scratch && gate_small_bytes(m) <= A.lds_bytes &&
                    m * ((m + 63u) / 64u) <= kAdjcScratchWords)) {
-        if (A.from_deferred) {
+        if (kDeferred) {
           if (l == 0) atomicExch(&A.status->error, 2u);        // graph too large even with the adjacency in global memory
           result = INT_MIN;
         } else {
           if (l == 0) A.deferred[atomicAdd(&A.status->n_deferred, 1u)] = it;
           result = INT_MIN + 1;                            // filled in by the second pass
         }
-      } else {
+      } else if constexpr (kDeferred) {
         // third tier: adjacency matrix in global scratch
         result = gate_lds_bytes(m) > A.lds_bytes ? gate_eval<true, kWide>(A, F, m, it, cnt, lds_raw, stack)
                                                  : gate_eval<false, kWide>(A, F, m, it, cnt, lds_raw, stack);
+      } else {
+        result = gate_eval<false, kWide>(A, F, m, it, cnt, lds_raw, stack);
       }
     }
     if (l == 0) {

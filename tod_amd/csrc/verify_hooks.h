@@ -241,12 +241,12 @@ static int test_clique_impl(todhip_ctx* ctx, uint32_t m, const uint32_t* edges, 
   TOD_HIP(hipMemcpyAsync(ws->clique_adj.p, adj.data(), adj.size() * 8, hipMemcpyHostToDevice, ctx->stream));
   if (gate_lds_bytes(m) > kEvalLdsBig) return TODHIP_ESCRATCH;
   const uint32_t lds = gate_lds_bytes(m) <= kEvalLdsSmall ? kEvalLdsSmall : kEvalLdsBig;   // the two LDS tiers of eval_kernel
-  if (gate)
-    hipLaunchKernelGGL(clique_test_kernel<true>, dim3(1), dim3(64), lds, ctx->stream, ws->clique_adj.as<u64>(), m, minimal_size,
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(1), dim3(64), lds, ctx->stream, ws->clique_adj.as<u64>(), m, minimal_size,
                        ws->stacks.as<uint16_t>(), kStackCap, lds, ws->small.as<uint32_t>());
-  else
-    hipLaunchKernelGGL(clique_test_kernel<false>, dim3(1), dim3(64), lds, ctx->stream, ws->clique_adj.as<u64>(), m, minimal_size,
-                       ws->stacks.as<uint16_t>(), kStackCap, lds, ws->small.as<uint32_t>());
+  };
+  if (m <= 512u) { if (gate) launch(clique_test_kernel<true, false>); else launch(clique_test_kernel<false, false>); }   // the product's narrow search
+  else { if (gate) launch(clique_test_kernel<true, true>); else launch(clique_test_kernel<false, true>); }
   TOD_HIP(hipGetLastError());
   TOD_HIP(hipMemcpyAsync(out3, ws->small.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   TOD_HIP(hipStreamSynchronize(ctx->stream));
