@@ -465,6 +465,51 @@ int todhip_cross_check_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, ui
  * TODHIP_EINVAL, and the setting does not change: Q > 0 on a context whose DB is float or is one shard of several. */
 int todhip_set_cross_check(todhip_ctx*, uint32_t frame_queries /* 0 = off, the default */);
 
+/* The two filters of the float forms (a DB of desc_bytes == 512). todhip_set_ratio_test and todhip_set_cross_check do not apply to the
+ * float forms, whatever the comments above say about "every todhip_match* form": they keep their behaviour on every context (a host
+ * that set them on a shared context keeps its results), and the float forms have setters of their own -- todhip_set_l2_ratio_test,
+ * todhip_set_l2_cross_check -- and a filter of their own, todhip_cross_check_l2_device. With all of them off every float call leaves
+ * byte for byte what it left before they existed.
+ *
+ * Lowe's ratio test on L2 distances, the descriptors the criterion was defined for. ratio: 0 = off, the default; 0 < ratio <= 1 = on;
+ * anything else, NaN included, is TODHIP_EINVAL and leaves the setting unchanged. It may be called with any DB or none.
+ * Definition: while on, every query of todhip_match_l2, todhip_match_l2_device and todhip_merge_l2_shards_device[_on] is tested on its
+ *   two nearest rows over the whole DB (the union of the shards), whatever the radius: the two smallest keys in the library's order
+ *   (d2, row), d2 the exact defining sum. With dist = sqrtf(d2) in binary32 the query keeps its matches iff dist1 < ratio * dist2 --
+ *   one binary32 product, nothing fused -- and otherwise all of its matches are dropped (counts[q] = 0). A DB, or a union of shards,
+ *   with one row passes. Two rows at equal distance fail even at ratio 1, as they do for the Hamming forms. The radius cut applies
+ *   to the survivors. k == 1 searches two rows internally and returns one. todhip_match_l2_shard_device and the k-NN merge return
+ *   TODHIP_EINVAL for k < 2 while it is on (the merge needs every shard's second nearest row; it reads the setting of the context it
+ *   is called on). todhip_match_l2_radius* and their merges ignore it, as the Hamming radius forms ignore todhip_set_ratio_test.
+ *   The predicate is stated once, in tod_amd/csrc/l2_filters.h (l2_ratio_passes). It adds no launch. */
+int todhip_set_l2_ratio_test(todhip_ctx*, float ratio /* 0 = off, the default */);
+
+/* The cross-check over a float DB, cv::BFMatcher(NORM_L2, crossCheck = true): todhip_cross_check_device's definition word for word --
+ * frames, V(f), g(m), in place, survivors keep their order and move to the front with their xyz, slots in [new counts[q], old
+ * counts[q]) unspecified, nothing written at or behind the old counts[q], a query outside V(f) ends with counts[q] = 0, idempotent,
+ * frame_nq is copied before the call returns -- and only the distance differs:
+ *   d(q, g)      = the IEEE binary32 bits of d2(q, row g), the defining sequential sum of todhip_match_l2 without fused multiply-add,
+ *                  compared as unsigned integers (d2 >= 0, so the order of the bits is the order of the values). The query's own
+ *                  d(q, g) is computed again from the descriptors, not taken from DMatch.distance.
+ * d_q_desc: the nq query rows of 128 f32 that produced the output. It accepts any fixed-stride float output, stride 1 ... 1024: what
+ * todhip_match_l2_device, todhip_match_l2_radius_device, todhip_merge_l2_shards_device[_on] and
+ * todhip_merge_l2_radius_shards_device[_on] leave.
+ * Two kernels: the test (a lane per kept match holds its DB row in 128 registers; a frame's valid queries are cut into chunks over
+ * workgroups, pass through LDS, four at a time per lane; exact early exit on the partial sums) and todhip_cross_check_device's
+ * compaction.
+ * TODHIP_EINVAL: a null context, query or output pointer, nq == 0, frame_queries == 0, stride == 0 or > 1024 (or nq * stride >=
+ * 2^31), a DB that is not float, a context that does not hold the whole DB (filter a sharded DB's merged output on a context that
+ * does). TODHIP_ENODB without a DB. */
+int todhip_cross_check_l2_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t frame_queries,
+                                 const uint32_t* frame_nq /* host, [ceil(nq / frame_queries)], may be NULL */,
+                                 uint32_t stride, void* d_counts, void* d_matches, void* d_matches_xyz);
+/* Switches it on for todhip_match_l2 and todhip_match_l2_device: while frame_queries = Q > 0, those two calls run
+ * todhip_cross_check_l2_device(Q, frame_nq = NULL, stride = k) behind their finalize step, that is behind the ratio test and the
+ * radius cut (the host form packs its CSR from the filtered counts). 0 = off, the default: no launch is added. The shard, merge and
+ * radius entry points of the float forms ignore it.
+ * TODHIP_EINVAL, and the setting does not change: Q > 0 on a context whose resident DB is binary or is one shard of several. */
+int todhip_set_l2_cross_check(todhip_ctx*, uint32_t frame_queries /* 0 = off, the default */);
+
 /* ---- stage C: GuessGenerator ------------------------------------------------------------------- */
 void todhip_rng_seed(todhip_rng*, uint32_t seed);   /* srand(seed); the reference never seeds => seed 1 */
 /* Replaces GuessGenerator::process (GuessGenerator.cpp:127-250) and everything under src/common.

@@ -104,6 +104,7 @@ EXPORTS = [
     "todhip_cross_check_device", "todhip_set_cross_check", "todhip_pipeline_set_cross_check",
     "todhip_match_l2_shard_device", "todhip_merge_l2_shards_device", "todhip_merge_l2_shards_device_on",
     "todhip_match_l2_radius_shard_device", "todhip_merge_l2_radius_shards_device", "todhip_merge_l2_radius_shards_device_on",
+    "todhip_set_l2_ratio_test", "todhip_cross_check_l2_device", "todhip_set_l2_cross_check",
 ]
 
 MAX_TRAIN_BATCH_VIEWS = 64
@@ -224,6 +225,11 @@ def lib():
             L.todhip_cross_check_device.restype = C.c_int
             L.todhip_set_cross_check.argtypes, L.todhip_set_cross_check.restype = [C.c_void_p, C.c_uint32], C.c_int
             L.todhip_pipeline_set_cross_check.argtypes, L.todhip_pipeline_set_cross_check.restype = [C.c_void_p, C.c_int], C.c_int
+        if hasattr(L, "todhip_cross_check_l2_device"):                # (as above)
+            L.todhip_set_l2_ratio_test.argtypes, L.todhip_set_l2_ratio_test.restype = [C.c_void_p, C.c_float], C.c_int
+            L.todhip_cross_check_l2_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
+            L.todhip_cross_check_l2_device.restype = C.c_int
+            L.todhip_set_l2_cross_check.argtypes, L.todhip_set_l2_cross_check.restype = [C.c_void_p, C.c_uint32], C.c_int
         _lib = L
     return _lib
 
@@ -560,6 +566,30 @@ class Context:
         """match() and match_device() run the cross-check behind their finalize step, in frames of frame_queries query rows (0 = off,
         the default). The sharded and radius forms ignore it: filter their outputs with cross_check_device."""
         _check(lib().todhip_set_cross_check(self._h, frame_queries), "todhip_set_cross_check")
+
+    def set_l2_ratio_test(self, ratio):
+        """Lowe's ratio test of the float forms (todhip_set_l2_ratio_test; 0 = off, the default; 0 < ratio <= 1 = on): match_l2,
+        match_l2_device and merge_l2_shards_device drop every match of a query whose two nearest rows over the whole DB do not
+        satisfy sqrtf(d2_1) < ratio * sqrtf(d2_2) in binary32. k == 1 searches two rows and returns one; match_l2_shard_device and
+        the merge refuse k < 2 while it is on. The radius forms ignore it. set_ratio_test does not apply to the float forms."""
+        _check(lib().todhip_set_l2_ratio_test(self._h, C.c_float(ratio)), "todhip_set_l2_ratio_test")
+
+    def cross_check_l2_device(self, d_q, nq, frame_queries, stride, d_counts, d_matches, d_xyz, frame_nq=None):
+        """The cross-check filter over a float DB, in place on a fixed-stride device output of match_l2_device,
+        match_l2_radius_device or either float merge (todhip_cross_check_l2_device): cross_check_device's definition with the
+        binary32 bits of the exact d2 as the distance. d_q: the nq query rows of 128 f32. frame_nq: per frame, how many of its
+        first rows compete (None: all). Asynchronous on the context's stream."""
+        fn = None if frame_nq is None else np.ascontiguousarray(frame_nq, np.uint32)
+        if fn is not None and len(fn) != (nq + frame_queries - 1) // max(frame_queries, 1):
+            raise TodError(EINVAL, "todhip_cross_check_l2_device (frame_nq of %d entries for %d queries in frames of %d)" % (len(fn), nq, frame_queries))
+        _check(lib().todhip_cross_check_l2_device(self._h, d_q, nq, frame_queries, None if fn is None else _np_ptr(fn), stride, d_counts,
+                                                  d_matches, d_xyz), "todhip_cross_check_l2_device")
+
+    def set_l2_cross_check(self, frame_queries):
+        """match_l2() and match_l2_device() run the float cross-check behind their finalize step -- behind the ratio test and the
+        radius cut -- in frames of frame_queries query rows (0 = off, the default). The shard, merge and radius forms ignore it:
+        filter their outputs with cross_check_l2_device. set_cross_check does not apply to the float forms."""
+        _check(lib().todhip_set_l2_cross_check(self._h, frame_queries), "todhip_set_l2_cross_check")
 
     def match_shard_device(self, d_q, nq, k, radius, d_keys):
         rc = lib().todhip_match_shard_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius),

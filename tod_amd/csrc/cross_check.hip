@@ -4,7 +4,8 @@
 //
 // The reverse search runs over the frame's QUERIES, not over DB rows: (kept matches) x (queries of the frame) distances, a few
 // thousandths of the DB pass's count, so the vector ALU does it and no DB-pass kernel is involved. This file shares ctx.h, row_ops.h
-// and match_keys.h (the block size) with the matcher and nothing else.
+// and match_keys.h (the block size) with the matcher and nothing else. The float forms' test kernel is cross_check_l2.hip's; it shares
+// the frames' transport and X2 with this file through cross_check_frames.h.
 //
 // X1 cross_check_test_kernel     one lane = one slot of a frame's slot space (query-major, `stride` slots per query; a block is 256
 //                                consecutive slots of ONE frame, blocks behind the frame's valid queries return at once). A live lane
@@ -25,6 +26,7 @@
 
 #include "ctx.h"
 #include "cross_check.h"
+#include "cross_check_frames.h"
 #include "row_ops.h"
 
 namespace {
@@ -32,23 +34,12 @@ namespace {
 #include "match_keys.h"
 
 constexpr uint32_t kChunkQueries = 64;       // query descriptors per LDS image: 2 KB at 32 bytes, 4 KB at 64 (static LDS)
-constexpr uint32_t kArgFrames = 64;          // frame_nq of up to this many frames travels as a kernel argument (the pipeline's steps)
 constexpr uint32_t kTestEvery = 8;           // queries between two "is anybody of this wave still unbeaten" tests
-
-// frame_nq: none (every row of a frame is valid), by value, or in device memory (more than kArgFrames frames)
-enum LimitMode { kLimitNone = 0, kLimitArg = 1, kLimitDev = 2 };
-struct FrameLimits { uint32_t n[kArgFrames]; };
 
 struct CrossCheckWs : TodWs {
   static constexpr int kSlot = kWsCrossCheck;
   DevBuf frame_nq;
 };
-
-__device__ __forceinline__ tod::CrossCheckRange valid_range(uint32_t f, uint32_t nq, uint32_t Q, int mode, const FrameLimits& lim,
-                                                            const uint32_t* __restrict__ d_frame_nq) {
-  const uint32_t n = mode == kLimitArg ? lim.n[f] : mode == kLimitDev ? d_frame_nq[f] : 0u;
-  return tod::cross_check_valid(f, nq, Q, mode != kLimitNone, n);
-}
 
 template <int WORDS> struct RowRegs;
 template <> struct RowRegs<8> {
@@ -156,25 +147,34 @@ __global__ __launch_bounds__(kBlock) void cross_check_compact_kernel(uint32_t nq
 
 }  // namespace
 
-int tod_cross_check(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t Q, const uint32_t* frame_nq, uint32_t stride,
-                    uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz) {
-  if ((uint64_t)nq * stride > 0x7FFFFFFFull) return TODHIP_EINVAL;              // slots are counted in 32 bits
-  const bool wide = ctx->desc_bytes == 64;
-  const uint32_t n_frames = tod::cross_check_n_frames(nq, Q);
-  int mode = kLimitNone;
-  FrameLimits lim = {};
-  const uint32_t* d_frame_nq = nullptr;
+int tod_cross_check_frame_limits(todhip_ctx* ctx, const uint32_t* frame_nq, uint32_t n_frames, FrameLimitArgs* out) {
   if (frame_nq && n_frames <= kArgFrames) {
-    mode = kLimitArg;
-    for (uint32_t f = 0; f < n_frames; ++f) lim.n[f] = frame_nq[f];
+    out->mode = kLimitArg;
+    for (uint32_t f = 0; f < n_frames; ++f) out->lim.n[f] = frame_nq[f];
   } else if (frame_nq) {
     // pageable source: the runtime has taken the bytes when the call returns, and the copy runs behind the kernels of an earlier call
     CrossCheckWs* ws = tod_ws<CrossCheckWs>(ctx);
     TOD_HIP(ws->frame_nq.reserve((size_t)n_frames * sizeof(uint32_t)));
     TOD_HIP(hipMemcpyAsync(ws->frame_nq.p, frame_nq, (size_t)n_frames * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    mode = kLimitDev;
-    d_frame_nq = ws->frame_nq.as<uint32_t>();
+    out->mode = kLimitDev;
+    out->d_frame_nq = ws->frame_nq.as<uint32_t>();
   }
+  return TODHIP_OK;
+}
+
+void tod_cross_check_compact(todhip_ctx* ctx, uint32_t nq, uint32_t Q, const FrameLimitArgs& a, uint32_t stride, uint32_t* d_counts,
+                             todhip_dmatch* d_matches, float* d_xyz) {
+  hipLaunchKernelGGL(cross_check_compact_kernel, dim3((nq + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, ctx->stream, nq, Q, a.mode,
+                     a.lim, a.d_frame_nq, stride, d_counts, d_matches, d_xyz);
+}
+
+int tod_cross_check(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t Q, const uint32_t* frame_nq, uint32_t stride,
+                    uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz) {
+  if ((uint64_t)nq * stride > 0x7FFFFFFFull) return TODHIP_EINVAL;              // slots are counted in 32 bits
+  const bool wide = ctx->desc_bytes == 64;
+  const uint32_t n_frames = tod::cross_check_n_frames(nq, Q);
+  FrameLimitArgs a;
+  if (int rc = tod_cross_check_frame_limits(ctx, frame_nq, n_frames, &a)) return rc;
   if (!wide && ctx->bit_order_on) {            // the stored rows are permuted: the queries follow them, the distances do not change
     int rc = tod_bit_order_queries(ctx, d_q, nq, &d_q);
     if (rc != TODHIP_OK) return rc;
@@ -184,13 +184,12 @@ int tod_cross_check(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t Q, c
   const uint32_t bpf = (uint32_t)(((uint64_t)frame_rows * stride + kBlock - 1) / kBlock);   // (nq * stride < 2^31: checked by the caller)
   const dim3 grid(n_frames * bpf), block(kBlock);
   if (wide)
-    hipLaunchKernelGGL(cross_check_test_kernel<16>, grid, block, 0, ctx->stream, q, nq, Q, mode, lim, d_frame_nq, bpf, stride, d_counts,
+    hipLaunchKernelGGL(cross_check_test_kernel<16>, grid, block, 0, ctx->stream, q, nq, Q, a.mode, a.lim, a.d_frame_nq, bpf, stride, d_counts,
                        d_matches, ctx->db_desc.as<uint32_t>(), ctx->db_obj_off.as<uint32_t>(), ctx->n_objs);
   else
-    hipLaunchKernelGGL(cross_check_test_kernel<8>, grid, block, 0, ctx->stream, q, nq, Q, mode, lim, d_frame_nq, bpf, stride, d_counts,
+    hipLaunchKernelGGL(cross_check_test_kernel<8>, grid, block, 0, ctx->stream, q, nq, Q, a.mode, a.lim, a.d_frame_nq, bpf, stride, d_counts,
                        d_matches, ctx->db_desc.as<uint32_t>(), ctx->db_obj_off.as<uint32_t>(), ctx->n_objs);
-  hipLaunchKernelGGL(cross_check_compact_kernel, dim3((nq + kWavesPerBlock - 1) / kWavesPerBlock), block, 0, ctx->stream, nq, Q, mode, lim,
-                     d_frame_nq, stride, d_counts, d_matches, d_xyz);
+  tod_cross_check_compact(ctx, nq, Q, a, stride, d_counts, d_matches, d_xyz);
   TOD_HIP(hipGetLastError());
   return TODHIP_OK;
 }

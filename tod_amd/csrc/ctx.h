@@ -136,6 +136,8 @@ struct todhip_ctx {
   K4xSplit k4x;                              // k4x.force: todhip_set_matcher_block_split
   float ratio = 0.f;                         // todhip_set_ratio_test (0 = off)
   uint32_t cross_check_q = 0;                // todhip_set_cross_check: the frame size todhip_match[_device] filter with (0 = off)
+  float l2_ratio = 0.f;                      // todhip_set_l2_ratio_test (0 = off): the float forms' own ratio test
+  uint32_t l2_cross_check_q = 0;             // todhip_set_l2_cross_check: the frame size todhip_match_l2[_device] filter with (0 = off)
   // todhip_set_db_bit_order (db_bitorder.hip): the mode the next load uses; the order of the resident shard (stored position p holds
   // original bit bit_src_of[p]) and whether it differs from the identity; its device copy and the queries' workspace -- both stay
   // empty until a load computes an order
@@ -235,6 +237,10 @@ int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_s
 // cross_check.hip: todhip_cross_check_device behind its argument checks (what todhip_match[_device] run while todhip_set_cross_check is on)
 int tod_cross_check(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t frame_queries, const uint32_t* frame_nq, uint32_t stride,
                     uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz);
+// cross_check.hip: todhip_cross_check_l2_device behind its argument checks (what todhip_match_l2[_device] run while
+// todhip_set_l2_cross_check is on); d_q: nq rows of 128 f32
+int tod_cross_check_l2(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t frame_queries, const uint32_t* frame_nq, uint32_t stride,
+                       uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz);
 // verify.hip: ClusterPerObject of F frames on the device without a cloud (pnp.hip's 2D-only branch); d_err: 8 words per frame
 // (ClusterCtl of verify_kernels.h: word 0 = error, word 4 = matches kept)
 int tod_cluster_frames_nocloud(todhip_ctx* ctx, uint32_t F, const float* d_kp_xy, uint32_t nq, const uint32_t* d_counts,

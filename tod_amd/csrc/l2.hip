@@ -34,6 +34,8 @@
 //   l2_radius.h   the radius search's kernels (todhip_match_l2_radius*): LT, LR, LS, LE around the same DB pass
 //   l2_sharded.h  the sharded forms' kernels (todhip_match_l2[_radius]_shard_device, todhip_merge_l2[_radius]_shards_device[_on]): SK, SR, LK, LM
 //   l2_trace.h    host: the wave-trace report of TODHIP_L2_TRACE
+//   l2_d2.h       the defining distance d2_exact (shared with cross_check_l2.hip); l2_filters.h: the ratio test's predicate
+//                 (todhip_set_l2_ratio_test), evaluated by l2_finalize_kernel and l2_merge_knn_kernel<K>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -211,6 +213,7 @@ int l2_merge_shards(todhip_ctx* ctx, hipStream_t stream, const void* d_keys_all,
   if (!ctx || !d_keys_all || !d_counts || !d_matches || !d_xyz) return TODHIP_EINVAL;
   if (nq == 0 || width == 0 || width > (KNN ? kTop : kL2MaxPerQuery) || n_shards == 0 || n_shards > kMaxMergeShards) return TODHIP_EINVAL;
   if (KNN && !(radius > 0.f)) return TODHIP_EINVAL;
+  if (KNN && ctx->l2_ratio > 0.f && width < 2) return TODHIP_EINVAL;              // the test needs the second nearest row
   if (int rc = l2_db_check(ctx, true)) return rc;
   TOD_HIP(hipSetDevice(ctx->device));
   hipStream_t st = stream ? stream : ctx->stream;
@@ -221,7 +224,7 @@ int l2_merge_shards(todhip_ctx* ctx, hipStream_t stream, const void* d_keys_all,
   if (KNN) {
     dispatch_k(width, [&](auto kc) {
       hipLaunchKernelGGL(l2_merge_knn_kernel<decltype(kc)::value>, dim3((nq + kMergeBlock - 1u) / kMergeBlock), dim3(kMergeBlock), 0, st, keys,
-                         n_shards, nq, radius, ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), counts, matches, xyz);
+                         n_shards, nq, radius, ctx->l2_ratio, ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), counts, matches, xyz);
       return TODHIP_OK;
     });
   } else {
@@ -253,8 +256,15 @@ int tod_l2_db_prepare(todhip_ctx* ctx) {
 
 extern "C" {
 
+int todhip_set_l2_ratio_test(todhip_ctx* ctx, float ratio) {
+  if (!ctx || !tod::l2_ratio_valid(ratio)) return TODHIP_EINVAL;
+  ctx->l2_ratio = ratio;
+  return TODHIP_OK;
+}
+
 int todhip_match_l2_shard_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint32_t k, void* d_keys) {
   if (!ctx || !d_q_desc || !d_keys || nq == 0 || k == 0 || k > kTop) return TODHIP_EINVAL;
+  if (ctx->l2_ratio > 0.f && k < 2) return TODHIP_EINVAL;   // the merge's ratio test needs every shard's second nearest row
   int rc = l2_db_check(ctx, true);
   if (rc != TODHIP_OK) return rc;
   TOD_HIP(hipSetDevice(ctx->device));
@@ -375,14 +385,20 @@ int todhip_match_l2_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, u
   int rc = l2_db_check(ctx);
   if (rc != TODHIP_OK || nq == 0) return rc;
   TOD_HIP(hipSetDevice(ctx->device));
-  rc = l2_keys(ctx, reinterpret_cast<const float*>(d_q_desc), nq, k);
+  // the ratio test judges the two nearest rows: k == 1 searches two and returns one (todhip_match's k_in / k_out)
+  const uint32_t k_in = ctx->l2_ratio > 0.f ? std::max(k, 2u) : k;
+  rc = l2_keys(ctx, reinterpret_cast<const float*>(d_q_desc), nq, k_in);
   if (rc != TODHIP_OK) return rc;
   L2Ws* ws = tod_ws<L2Ws>(ctx);
-  hipLaunchKernelGGL(l2_finalize_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, ctx->stream, ws->keys.as<uint64_t>(), nq, k, radius,
-                     ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(), reinterpret_cast<uint32_t*>(d_counts),
-                     reinterpret_cast<todhip_dmatch*>(d_matches), reinterpret_cast<float*>(d_matches_xyz));
+  hipLaunchKernelGGL(l2_finalize_kernel, dim3((nq + 255u) / 256u), dim3(256), 0, ctx->stream, ws->keys.as<uint64_t>(), nq, k_in, k, radius,
+                     ctx->l2_ratio, ctx->db_obj_off.as<uint32_t>(), ctx->n_objs, ctx->db_pts.as<float>(),
+                     reinterpret_cast<uint32_t*>(d_counts), reinterpret_cast<todhip_dmatch*>(d_matches),
+                     reinterpret_cast<float*>(d_matches_xyz));
   TOD_HIP(hipGetLastError());
   ctx->counters.last_nq = nq; ctx->counters.last_k = k;
+  if (ctx->l2_cross_check_q)                                // todhip_set_l2_cross_check: behind the ratio test and the radius cut
+    return tod_cross_check_l2(ctx, d_q_desc, nq, ctx->l2_cross_check_q, nullptr, k, reinterpret_cast<uint32_t*>(d_counts),
+                              reinterpret_cast<todhip_dmatch*>(d_matches), reinterpret_cast<float*>(d_matches_xyz));
   return TODHIP_OK;
 }
 

@@ -3,6 +3,9 @@
 // (l2_radius.h) shares with them. Included by l2.hip.
 #pragma once
 
+#include "l2_d2.h"
+#include "l2_filters.h"
+
 namespace {
 
 // per query (one wave): k-th smallest score over the partitions' lists; scores at or above the seed were never
@@ -43,18 +46,8 @@ __global__ __launch_bounds__(256) void l2_threshold_kernel(const float* __restri
   if (l == 0) out[q] = ak + margin * eps[q];
 }
 
-// the defining distance (include/todhip.h): sequential f32, no fused multiply-add (-ffp-contract=off)
-__device__ __forceinline__ float d2_exact(const float* __restrict__ q, const float* __restrict__ r) {
-  float acc = 0.f;
-  for (uint32_t i = 0; i < kDim; i += 4) {
-    const float4 a = *reinterpret_cast<const float4*>(q + i), b = *reinterpret_cast<const float4*>(r + i);
-    float t = a.x - b.x; acc = acc + t * t;
-    t = a.y - b.y; acc = acc + t * t;
-    t = a.z - b.z; acc = acc + t * t;
-    t = a.w - b.w; acc = acc + t * t;
-  }
-  return acc;
-}
+// (the defining distance, d2_exact: l2_d2.h)
+static_assert(kDim == tod::kL2Dim, "l2_d2.h states the distance over kDim dimensions");
 
 __device__ __forceinline__ void keys_insert(uint64_t (&best)[kTop], uint64_t key) {
 #pragma unroll
@@ -172,21 +165,26 @@ __global__ __launch_bounds__(256) void l2_exact_scan_kernel(const float* __restr
   }
 }
 
-// radius cut (DescriptorMatcher.cpp:212-220 shape), object lookup (:60-129 load order), 3D gather (:231-244)
-__global__ __launch_bounds__(256) void l2_finalize_kernel(const uint64_t* __restrict__ keys, uint32_t nq, uint32_t k, float radius,
-                                                          const uint32_t* __restrict__ obj_off, uint32_t n_objs,
+// ratio test (todhip_set_l2_ratio_test; ratio 0: off), radius cut (DescriptorMatcher.cpp:212-220 shape), object lookup (:60-129 load
+// order), 3D gather (:231-244). keys: [nq][k_in]; the outputs have stride k_out <= k_in (k_in > k_out only for the ratio test with
+// k == 1, which needs the second nearest row: todhip_match's k_in / k_out). While the test is on k_in >= 2 (the host sees to it).
+__global__ __launch_bounds__(256) void l2_finalize_kernel(const uint64_t* __restrict__ keys, uint32_t nq, uint32_t k_in, uint32_t k_out,
+                                                          float radius, float ratio, const uint32_t* __restrict__ obj_off, uint32_t n_objs,
                                                           const float* __restrict__ pts, uint32_t* __restrict__ counts,
                                                           todhip_dmatch* __restrict__ matches, float* __restrict__ xyz) {
   const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
   if (qi >= nq) return;
+  const uint64_t* lst = keys + (size_t)qi * k_in;
   uint32_t kept = 0;
-  for (uint32_t j = 0; j < k; ++j) {
-    const uint64_t key = keys[(size_t)qi * k + j];
-    if (key == ~0ull) break;
-    const float dist = l2_key_distance(key);
-    if (dist > radius) break;
-    l2_write_match(key, dist, qi, (size_t)qi * k + kept, obj_off, n_objs, pts, matches, xyz);
-    ++kept;
+  if (!(ratio > 0.f) || tod::l2_ratio_keeps(lst[0], lst[1], ratio)) {
+    for (uint32_t j = 0; j < k_out; ++j) {
+      const uint64_t key = lst[j];
+      if (key == ~0ull) break;
+      const float dist = l2_key_distance(key);
+      if (dist > radius) break;
+      l2_write_match(key, dist, qi, (size_t)qi * k_out + kept, obj_off, n_objs, pts, matches, xyz);
+      ++kept;
+    }
   }
   counts[qi] = kept;
 }

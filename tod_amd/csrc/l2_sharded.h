@@ -50,9 +50,11 @@ __device__ __forceinline__ bool l2_key_stands(uint64_t key, float radius) { retu
 // shards and a padding key passes through it without moving anything), then l2_finalize_kernel's walk -- a match per key until the
 // first that does not stand. K is a template argument so that a shard's K keys are loaded before any is looked at and the list's
 // length is the call's k, not kTop. Neighbouring threads read neighbouring rows of a shard's keys.
+// ratio > 0 (todhip_set_l2_ratio_test; K >= 2 then, the host refuses K == 1): the two smallest keys of the union are the query's two
+// nearest rows of the full DB, and l2_finalize_kernel's test on them decides whether the walk starts at all.
 template <int K>
 __global__ __launch_bounds__(256) void l2_merge_knn_kernel(const uint64_t* __restrict__ keys_all, uint32_t n_shards, uint32_t nq, float radius,
-                                                           const uint32_t* __restrict__ obj_off, uint32_t n_objs,
+                                                           float ratio, const uint32_t* __restrict__ obj_off, uint32_t n_objs,
                                                            const float* __restrict__ pts, uint32_t* __restrict__ counts,
                                                            todhip_dmatch* __restrict__ matches, float* __restrict__ xyz) {
   TOD_LATENCY_PRIO();   // latency-bound, as the Hamming merges
@@ -76,6 +78,7 @@ __global__ __launch_bounds__(256) void l2_merge_knn_kernel(const uint64_t* __res
   }
   uint32_t kept = 0;
   bool open = true;
+  if (K >= 2 && ratio > 0.f) open = tod::l2_ratio_keeps(best[0], best[K >= 2 ? 1 : 0], ratio);
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     open = open && l2_key_stands(best[j], radius);

@@ -163,7 +163,8 @@ class GpuOps:
     max_per_query the two calls are the radius pair: matches and xyz have stride max_per_query instead of k and `out` also holds
     in_radius [n] i32 (todhip_match_radius_device's outputs). metric "l2": the context holds a shard of a float DB, the queries are
     128 x f32 rows, `radius` is a float and the two calls are the float pairs (todhip_match_l2_device's or
-    todhip_match_l2_radius_device's outputs)."""
+    todhip_match_l2_radius_device's outputs). The float ratio test needs no code here: the k-NN merge reads the setting of the context
+    it runs on (`ctx.set_l2_ratio_test`, the same on every rank; k >= 2 while it is on), the radius pair ignores it."""
 
     def __init__(self, ctx, compute_stream, comm_stream, backend, k, radius, max_per_query=None, metric="hamming"):
         import torch
