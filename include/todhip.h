@@ -126,7 +126,7 @@ int todhip_db_desc_bytes(const todhip_ctx*, uint32_t* desc_bytes);
 
 /* Descriptor widths. desc_bytes == 32: 256-bit binary rows (ORB / rBRIEF), Hamming. desc_bytes == 512: 128 x f32, L2
  * (todhip_match_l2*, one device). desc_bytes == 64: 512-bit binary rows -- BRISK, FREAK, BRIEF-64 -- Hamming, any shard_count, host
- * or device source. Anything else: TODHIP_EINVAL. A narrower binary descriptor (AKAZE's 61 bytes) is used by zero-padding rows AND
+ * or device source. desc_bytes == 256: 64 x f32, L2, the second float width (see todhip_match_l2). Anything else: TODHIP_EINVAL. A narrower binary descriptor (AKAZE's 61 bytes) is used by zero-padding rows AND
  * queries to 64 bytes: the padding adds nothing to any distance.
  * On a DB loaded with desc_bytes == 64, todhip_match, todhip_match_device and todhip_match_shard_device with
  * todhip_merge_shards_device[_on] perform the same exact search as on a 32-byte DB, definition unchanged: Hamming distance over all
@@ -245,7 +245,14 @@ int todhip_match_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t
  * queryIdx): they share ONE pass over the DB, and every query's matches are those of a call that carried its frame alone
  * (16 frames of 1000 queries against 500k rows under the first, too narrow eps: 0.12 ms per frame instead of 0.19; under the
  * corrected one a 16-frame call has too few private candidate slots per query and is slower per frame than single calls, 0.75 ms
- * against 0.24: DESIGN 6b, "The bound"). */
+ * against 0.24: DESIGN 6b, "The bound").
+ * Two widths: dim = desc_bytes / 4 ∈ {64, 128}. A DB loaded with desc_bytes == 256 is a float DB of 64 x f32 rows
+ * (SURF's and KAZE's default width) and every float call of this header serves it -- todhip_db_load[_device] with any shard_count,
+ * todhip_match_l2[_device], todhip_match_l2_radius[_device], the shard and merge pairs, todhip_set_l2_ratio_test,
+ * todhip_cross_check_l2_device and todhip_set_l2_cross_check -- with the definitions given for desc_bytes == 512 and 127 read as
+ * dim - 1: d2 = sum over i = 0..dim-1 in index order, distance = sqrtf(d2), order (d2, row), key = bits(d2) << 32 | row; queries are
+ * nq x dim f32; the same eps(q) bounds the filter (tests/l2_dim64_bound_host_test.cpp). What a float DB refuses (the Hamming calls,
+ * selections, LSH, the pipeline) it refuses at either width; any other desc_bytes is TODHIP_EINVAL at the load. */
 int todhip_match_l2(todhip_ctx*, const float* q_desc, uint32_t nq, uint32_t k, float radius, uint32_t* row_ptr,
                     todhip_dmatch* matches, float* matches_xyz);
 int todhip_match_l2_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, uint32_t k, float radius, void* d_counts,

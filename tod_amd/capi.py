@@ -367,6 +367,7 @@ class Context:
     def db_load(self, desc, pts, obj_off, shard_rank=0, shard_count=1):
         """desc u8[N,32] (256-bit binary: ORB) or u8[N,64] (512-bit binary: BRISK, FREAK; AKAZE's 61 bytes zero-padded to 64), both
         Hamming, or f32[N,128] (float, L2); pts f32[N,3], obj_off u32[n_obj+1] (rows of object o are obj_off[o]:obj_off[o+1]).
+        f32[N,64] (SURF, KAZE) is the narrower float DB, desc_bytes 256: every float call serves it as it serves 128.
         The width of desc is the DB's desc_bytes: the match calls take queries of that width."""
         desc = np.ascontiguousarray(desc, np.float32 if np.asarray(desc).dtype == np.float32 else np.uint8)
         pts = np.ascontiguousarray(pts, np.float32)
@@ -406,7 +407,8 @@ class Context:
         return dict(total_rows=tot.value, shard_first=first.value, shard_rows=rows.value, n_objs=nobj.value)
 
     def desc_bytes(self):
-        """Bytes per row of the resident DB (32, 64 or 512; 0 before the first load): todhip_db_desc_bytes"""
+        """Bytes per row of the resident DB (32, 64 or 512; 0 before the first load): todhip_db_desc_bytes. 256: the float DB of
+        64 x f32 rows."""
         b = C.c_uint32()
         _check(lib().todhip_db_desc_bytes(self._h, C.byref(b)), "todhip_db_desc_bytes")
         return b.value
@@ -418,6 +420,15 @@ class Context:
         B = self.desc_bytes() if hasattr(lib(), "todhip_db_desc_bytes") else 0
         if B in (32, 64) and q.ndim == 2 and q.shape[1] != B:
             raise TodError(EINVAL, "%s (queries of shape %s against a DB of %d-byte descriptors)" % (what, q.shape, B))
+        return q
+
+    def _query_rows_l2(self, q_desc, what):
+        """q_desc as contiguous f32[nq, dim]. A query matrix of another width than a float DB's (64 or 128) is refused here with
+        TodError(EINVAL), as _query_rows refuses it for a binary DB."""
+        q = np.ascontiguousarray(q_desc, np.float32)
+        B = self.desc_bytes() if hasattr(lib(), "todhip_db_desc_bytes") else 0
+        if B in (256, 512) and q.ndim == 2 and q.shape[1] * 4 != B:
+            raise TodError(EINVAL, "%s (queries of shape %s against a DB of %d x f32 descriptors)" % (what, q.shape, B // 4))
         return q
 
     def select_objects(self, ids):
@@ -481,8 +492,9 @@ class Context:
                                                           d_xyz, d_in_radius), "todhip_merge_radius_shards_device_on")
 
     def match_l2(self, q_desc, k, radius):
-        """Float descriptors, host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
-        return self._match_host(lib().todhip_match_l2, "todhip_match_l2", np.ascontiguousarray(q_desc, np.float32), k, C.c_float(radius))
+        """Float descriptors, host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3]). q_desc f32[nq, 64] or
+        f32[nq, 128]: the query width must equal the DB's (desc_bytes() / 4; TodError(EINVAL) otherwise)."""
+        return self._match_host(lib().todhip_match_l2, "todhip_match_l2", self._query_rows_l2(q_desc, "todhip_match_l2"), k, C.c_float(radius))
 
     def match_l2_device(self, d_q, nq, k, radius, d_counts, d_matches, d_xyz):
         rc = lib().todhip_match_l2_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_float(radius),
@@ -492,8 +504,9 @@ class Context:
     def match_l2_radius(self, q_desc, radius, max_per_query):
         """The true L2 radius search over a float DB, host-buffer form (todhip_match_l2_radius): every row whose distance is not
         > radius, the nearest max_per_query of them per query. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3],
-        in_radius u32[nq]). The output buffers start at 16 matches per query and grow to the count the library asks for."""
-        q = np.ascontiguousarray(q_desc, np.float32)
+        in_radius u32[nq]). The output buffers start at 16 matches per query and grow to the count the library asks for. The query
+        width must equal the DB's, as in match_l2."""
+        q = self._query_rows_l2(q_desc, "todhip_match_l2_radius")
         nq = q.shape[0]
         row_ptr, in_radius = np.zeros(nq + 1, np.uint32), np.zeros(nq, np.uint32)
         cap = max(nq * min(max_per_query, 16), 1)
@@ -578,7 +591,14 @@ class Context:
         """The cross-check filter over a float DB, in place on a fixed-stride device output of match_l2_device,
         match_l2_radius_device or either float merge (todhip_cross_check_l2_device): cross_check_device's definition with the
         binary32 bits of the exact d2 as the distance. d_q: the nq query rows of 128 f32. frame_nq: per frame, how many of its
-        first rows compete (None: all). Asynchronous on the context's stream."""
+        first rows compete (None: all). Asynchronous on the context's stream. On a DB of 64 x f32 rows the query rows are 64 f32.
+        d_q may also be the device tensor itself (anything with .shape and .data_ptr()): its width is then checked against the DB's
+        (TodError(EINVAL)) before the library reads it -- a bare pointer carries no shape and the caller answers for it."""
+        if hasattr(d_q, "data_ptr"):
+            B = self.desc_bytes()
+            if B in (256, 512) and (len(d_q.shape) != 2 or d_q.shape[1] * 4 != B or d_q.shape[0] < nq):
+                raise TodError(EINVAL, "todhip_cross_check_l2_device (queries of shape %s against a DB of %d x f32 descriptors)" % (tuple(d_q.shape), B // 4))
+            d_q = d_q.data_ptr()
         fn = None if frame_nq is None else np.ascontiguousarray(frame_nq, np.uint32)
         if fn is not None and len(fn) != (nq + frame_queries - 1) // max(frame_queries, 1):
             raise TodError(EINVAL, "todhip_cross_check_l2_device (frame_nq of %d entries for %d queries in frames of %d)" % (len(fn), nq, frame_queries))

@@ -195,8 +195,8 @@ static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_o
                         uint32_t shard_rank, uint32_t shard_count, float* spans_out, bool device_src) {
   if (!ctx || (!objs && n_objs) || shard_count == 0 || shard_rank >= shard_count) return TODHIP_EINVAL;
   // 32: 256-bit binary descriptors (ORB), 64: 512-bit ones (BRISK, FREAK; match_wide.hip), Hamming; 512: 128 x f32 (SIFT-like), L2
-  // (a shard of several is searched by the sharded forms alone, l2_sharded.h)
-  if (desc_bytes != 32 && desc_bytes != 64 && desc_bytes != 512) return TODHIP_EINVAL;
+  // (a shard of several is searched by the sharded forms alone, l2_sharded.h); 256: 64 x f32 (SURF, KAZE), the same calls
+  if (desc_bytes != 32 && desc_bytes != 64 && desc_bytes != 512 && desc_bytes != 256) return TODHIP_EINVAL;
   TOD_HIP(hipSetDevice(ctx->device));
   tod_view_reset(ctx);                                      // todhip_db_select_objects: a load selects all objects
   tod_db_rows_written(ctx);                                 // the fp4 copy of the old rows is stale (match_launch.h builds the next)
@@ -266,7 +266,7 @@ static int db_load_impl(todhip_ctx* ctx, const todhip_object* objs, uint32_t n_o
       if (spans_out) spans_out[o] = ctx->h_spans[o];
     }
   }
-  if (desc_bytes == 512) {
+  if (desc_bytes == 512 || desc_bytes == 256) {
     int rc = tod_l2_db_prepare(ctx);
     if (rc != TODHIP_OK) return rc;
   }

@@ -210,7 +210,7 @@ extern "C" int todhip_cross_check_device(todhip_ctx* ctx, const void* d_q_desc, 
 extern "C" int todhip_set_cross_check(todhip_ctx* ctx, uint32_t frame_queries) {
   if (!ctx) return TODHIP_EINVAL;
   // a float DB has no Hamming rows to test against, a shard of a DB does not hold every row a match names (switching off always works)
-  if (frame_queries && ctx->total_rows && (ctx->desc_bytes == 512 || ctx->shard_rows != ctx->total_rows)) return TODHIP_EINVAL;
+  if (frame_queries && ctx->total_rows && (ctx->desc_bytes == 512 || ctx->desc_bytes == 256 || ctx->shard_rows != ctx->total_rows)) return TODHIP_EINVAL;
   ctx->cross_check_q = frame_queries;
   return TODHIP_OK;
 }

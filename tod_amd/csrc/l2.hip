@@ -36,6 +36,8 @@
 //   l2_trace.h    host: the wave-trace report of TODHIP_L2_TRACE
 //   l2_d2.h       the defining distance d2_exact (shared with cross_check_l2.hip); l2_filters.h: the ratio test's predicate
 //                 (todhip_set_l2_ratio_test), evaluated by l2_finalize_kernel and l2_merge_knn_kernel<K>
+// Two row widths: desc_bytes 512 = 128 x f32 and desc_bytes 256 = 64 x f32 (SURF, KAZE). The kernels that touch a row take the
+// width as a template argument (l2_prepare_kernel has a sibling); l2_kernels(ctx) below is the one place that picks between them.
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -75,6 +77,32 @@ const L2Knobs& l2_knobs() {                                 // the environment, 
   return knobs;
 }
 
+// The one dispatcher on the row width: every kernel that touches a row of D floats, for D = kDim or kDimNarrow. The signatures do not
+// depend on D, so a launch site reads the resident DB's table (l2_kernels(ctx)) and is otherwise what it was; the kernels that see
+// keys, scores or counters only (threshold, finalize, emit, the shard and merge kernels) are not in it.
+using L2Gemm = decltype(&l2_gemm_kernel<2, 4, kDim>);
+struct L2Kernels {
+  uint32_t dim;
+  decltype(&l2_prepare_kernel) prepare;
+  L2Gemm pass1_kt1, pass1_kt4, pass1_kt8, pass2;
+  decltype(&l2_rerank_kernel<kDim>) rerank;
+  decltype(&l2_exact_scan_kernel<kDim>) exact_scan;
+  decltype(&l2_radius_threshold_kernel<kDim>) radius_threshold;
+  decltype(&l2_radius_refine_kernel<kDim>) radius_refine;
+  decltype(&l2_radius_scan_kernel<kDim>) radius_scan;
+  L2Gemm pass1(uint32_t kt) const { return kt == 1u ? pass1_kt1 : kt == 4u ? pass1_kt4 : pass1_kt8; }
+};
+template <uint32_t D>
+constexpr L2Kernels l2_kernels_of(decltype(&l2_prepare_kernel) prepare) {
+  return {D, prepare, l2_gemm_kernel<1, 1, D>, l2_gemm_kernel<1, 4, D>, l2_gemm_kernel<1, 8, D>, l2_gemm_kernel<2, 4, D>, l2_rerank_kernel<D>,
+          l2_exact_scan_kernel<D>, l2_radius_threshold_kernel<D>, l2_radius_refine_kernel<D>, l2_radius_scan_kernel<D>};
+}
+// (a context that holds no float DB never gets here: l2_db_check stands before every call)
+const L2Kernels& l2_kernels(const todhip_ctx* ctx) {
+  static const L2Kernels wide = l2_kernels_of<kDim>(l2_prepare_kernel), narrow = l2_kernels_of<kDimNarrow>(l2_prepare_narrow_kernel);
+  return l2_dim_of(ctx->desc_bytes) == kDimNarrow ? narrow : wide;
+}
+
 // What every call that runs the DB pass (l2_gemm_kernel<2, 4>) over nq queries starts with: the buffers the pass reads and writes,
 // and the queries' bf16 image pre-scaled by -2 (a power of two: no extra rounding), |q|^2, eps and zeroed shared counters.
 int l2_pass_begin(todhip_ctx* ctx, L2Ws* ws, const L2Plan& P, const float* d_q, uint32_t nq) {
@@ -82,7 +110,7 @@ int l2_pass_begin(todhip_ctx* ctx, L2Ws* ws, const L2Plan& P, const float* d_q, 
                                              {&ws->q_eps, P.q_eps_bytes}, {&ws->q_norm, P.q_norm_bytes}, {&ws->thr, P.thr_bytes},
                                              {&ws->cand, P.cand_bytes}, {&ws->slots, P.slots_bytes}, {&ws->slot_cnt, P.slot_cnt_bytes}};
   for (const auto& b : bufs) TOD_HIP(b.first->reserve(b.second));
-  hipLaunchKernelGGL(l2_prepare_kernel, dim3((P.nq_pad + 3u) / 4u), dim3(256), 0, ctx->stream, d_q, nq, P.nq_pad, -2.0f,
+  hipLaunchKernelGGL(l2_kernels(ctx).prepare, dim3((P.nq_pad + 3u) / 4u), dim3(256), 0, ctx->stream, d_q, nq, P.nq_pad, -2.0f,
                      ws->q_bf16.as<uint16_t>(), ws->q_norm.as<float>(), (uint32_t*)nullptr, 0, (const uint32_t*)ws->scal.as<uint32_t>(),
                      ws->q_eps.as<float>(), ws->cand_cnt.as<uint32_t>());
   return TODHIP_OK;
@@ -92,10 +120,8 @@ int l2_pass_begin(todhip_ctx* ctx, L2Ws* ws, const L2Plan& P, const float* d_q, 
 // a sample (n tiles, every stride-th of the DB's, in grid_x chunks of per_chunk), the other passes over the plan's chunks of the
 // whole DB. part: where passes 0 and 1 leave their lists (pass 2: the wave trace, or null); thr: the seed that limits pass 1
 // (or null), pass 2's candidate threshold; sink: pass 2's candidate containers.
-using L2Gemm = decltype(&l2_gemm_kernel<2, 4>);
 struct L2Tiles { uint32_t n, per_chunk, stride, grid_x; };
 L2Tiles l2_all_tiles(const L2Plan& P) { return {P.n_tiles, P.tiles_per_chunk, 1u, P.n_chunks}; }
-L2Gemm l2_pass1_kernel(uint32_t kt) { return kt == 1u ? l2_gemm_kernel<1, 1> : kt == 4u ? l2_gemm_kernel<1, 4> : l2_gemm_kernel<1, 8>; }
 
 void l2_launch_gemm(L2Gemm kernel, todhip_ctx* ctx, const L2Ws* ws, const L2Plan& P, L2Tiles tiles, float* part, const float* thr,
                     bool sink) {
@@ -112,10 +138,11 @@ int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k) {
   hipStream_t st = ctx->stream;
   const uint32_t n = (uint32_t)ctx->shard_rows;
   const L2Knobs& knobs = l2_knobs();
-  const L2Plan P = l2_plan(n, nq, k, (uint32_t)ctx->n_cu, knobs);
+  const L2Kernels& K = l2_kernels(ctx);
+  const L2Plan P = l2_plan(n, nq, k, (uint32_t)ctx->n_cu, knobs, K.dim);
   TOD_HIP(ws->keys.reserve(P.keys_bytes));
   if (knobs.exact_scan) {
-    hipLaunchKernelGGL(l2_exact_scan_kernel, dim3(nq), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(), n, k,
+    hipLaunchKernelGGL(K.exact_scan, dim3(nq), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(), n, k,
                        (const uint32_t*)nullptr, ws->keys.as<uint64_t>());
     TOD_HIP(hipGetLastError());
     return TODHIP_OK;
@@ -130,24 +157,24 @@ int l2_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, uint32_t k) {
   };
   const float* seed = nullptr;
   if (P.seed_pass) {
-    l2_launch_gemm(l2_pass1_kernel(P.kt0), ctx, ws, P, {P.sample_tiles, P.s_tpc, P.sample_stride, P.s_used}, ws->part.as<float>(), nullptr, false);
+    l2_launch_gemm(K.pass1(P.kt0), ctx, ws, P, {P.sample_tiles, P.s_tpc, P.sample_stride, P.s_used}, ws->part.as<float>(), nullptr, false);
     if (P.fast) threshold(2u * P.s_used, nq, nullptr, P.margin, ws->thr.as<float>());
     else { threshold(2u * P.s_used, P.nq_pad, nullptr, 0.f, ws->seed.as<float>()); seed = ws->seed.as<float>(); }
   }
   KernelTimer timer{ctx};
   if (int rc = timer.begin()) return rc;
   if (!P.one_gemm()) {
-    l2_launch_gemm(l2_pass1_kernel(P.kt1), ctx, ws, P, l2_all_tiles(P), ws->part.as<float>(), seed, false);
+    l2_launch_gemm(K.pass1(P.kt1), ctx, ws, P, l2_all_tiles(P), ws->part.as<float>(), seed, false);
     if (int rc = timer.end()) return rc;
     threshold(P.n_parts, nq, seed, P.margin, ws->thr.as<float>());
   }
-  l2_launch_gemm(l2_gemm_kernel<2, 4>, ctx, ws, P, l2_all_tiles(P), knobs.trace ? ws->part.as<float>() : nullptr, ws->thr.as<float>(), true);
+  l2_launch_gemm(K.pass2, ctx, ws, P, l2_all_tiles(P), knobs.trace ? ws->part.as<float>() : nullptr, ws->thr.as<float>(), true);
   if (P.one_gemm()) { if (int rc = timer.end()) return rc; }
   if (knobs.trace) { if (int rc = l2_trace_report(ctx, ws->part.p, P.q_blocks, P.n_chunks)) return rc; }
-  hipLaunchKernelGGL(l2_rerank_kernel, dim3((nq + 3u) / 4u), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(),
+  hipLaunchKernelGGL(K.rerank, dim3((nq + 3u) / 4u), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(),
                      ws->slots.as<uint32_t>(), ws->slot_cnt.as<uint32_t>(), P.n_parts, ws->cand.as<uint32_t>(),
                      ws->cand_cnt.as<uint32_t>(), k, ws->keys.as<uint64_t>(), ws->flags.as<uint32_t>());
-  hipLaunchKernelGGL(l2_exact_scan_kernel, dim3(nq), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(), n, k,
+  hipLaunchKernelGGL(K.exact_scan, dim3(nq), dim3(256), 0, st, d_q, nq, ctx->db_desc.as<float>(), n, k,
                      (const uint32_t*)ws->flags.as<uint32_t>(), ws->keys.as<uint64_t>());
   TOD_HIP(hipGetLastError());
   return TODHIP_OK;
@@ -161,20 +188,21 @@ int l2_radius_keys(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radius,
   L2Ws* ws = tod_ws<L2Ws>(ctx);
   hipStream_t st = ctx->stream;
   const float* db = ctx->db_desc.as<float>();
-  const L2Plan P = l2_plan((uint32_t)ctx->shard_rows, nq, mpq, (uint32_t)ctx->n_cu, l2_knobs());
+  const L2Kernels& K = l2_kernels(ctx);
+  const L2Plan P = l2_plan((uint32_t)ctx->shard_rows, nq, mpq, (uint32_t)ctx->n_cu, l2_knobs(), K.dim);
   TOD_HIP(ws->keys.reserve(P.keys_bytes));
   if (int rc = l2_pass_begin(ctx, ws, P, d_q, nq)) return rc;
   TOD_HIP(ws->scan_marks.reserve(P.scan_marks_bytes));
-  hipLaunchKernelGGL(l2_radius_threshold_kernel, dim3((P.nq_pad + 255u) / 256u), dim3(256), 0, st, d_q, nq, P.nq_pad, radius,
+  hipLaunchKernelGGL(K.radius_threshold, dim3((P.nq_pad + 255u) / 256u), dim3(256), 0, st, d_q, nq, P.nq_pad, radius,
                      ws->q_eps.as<float>(), ws->thr.as<float>(), ws->scan_marks.as<uint32_t>());
   KernelTimer timer{ctx};
   if (int rc = timer.begin()) return rc;
-  l2_launch_gemm(l2_gemm_kernel<2, 4>, ctx, ws, P, l2_all_tiles(P), nullptr, ws->thr.as<float>(), true);
+  l2_launch_gemm(K.pass2, ctx, ws, P, l2_all_tiles(P), nullptr, ws->thr.as<float>(), true);
   if (int rc = timer.end()) return rc;
-  hipLaunchKernelGGL(l2_radius_refine_kernel, dim3(nq), dim3(256), 0, st, d_q, db, ws->slots.as<uint32_t>(), ws->slot_cnt.as<uint32_t>(),
+  hipLaunchKernelGGL(K.radius_refine, dim3(nq), dim3(256), 0, st, d_q, db, ws->slots.as<uint32_t>(), ws->slot_cnt.as<uint32_t>(),
                      P.n_parts, ws->cand.as<uint32_t>(), ws->cand_cnt.as<uint32_t>(), ws->scan_marks.as<uint32_t>(), radius, mpq,
                      ws->keys.as<uint64_t>(), d_counts, d_in_radius, ws->flags.as<uint32_t>());
-  hipLaunchKernelGGL(l2_radius_scan_kernel, dim3(nq), dim3(256), 0, st, d_q, db, (uint32_t)ctx->shard_rows, ws->flags.as<uint32_t>(), radius,
+  hipLaunchKernelGGL(K.radius_scan, dim3(nq), dim3(256), 0, st, d_q, db, (uint32_t)ctx->shard_rows, ws->flags.as<uint32_t>(), radius,
                      mpq, ws->keys.as<uint64_t>(), d_counts, d_in_radius);
   TOD_HIP(hipGetLastError());
   return TODHIP_OK;
@@ -194,10 +222,10 @@ int l2_radius_search(todhip_ctx* ctx, const float* d_q, uint32_t nq, float radiu
   return TODHIP_OK;
 }
 
-// the DB every float call needs: not empty, 128 x f32; the unsharded calls: the whole of it resident
+// the DB every float call needs: not empty, 128 or 64 x f32; the unsharded calls: the whole of it resident
 int l2_db_check(const todhip_ctx* ctx, bool sharded = false) {
   if (ctx->total_rows == 0) return TODHIP_ENODB;
-  return ctx->desc_bytes != kDim * 4u || (!sharded && ctx->shard_rows != ctx->total_rows) ? TODHIP_EINVAL : TODHIP_OK;
+  return l2_dim_of(ctx->desc_bytes) == 0u || (!sharded && ctx->shard_rows != ctx->total_rows) ? TODHIP_EINVAL : TODHIP_OK;
 }
 
 int l2_radius_args(const todhip_ctx* ctx, uint32_t nq, float radius, uint32_t mpq, bool sharded = false) {
@@ -239,17 +267,18 @@ int l2_merge_shards(todhip_ctx* ctx, hipStream_t stream, const void* d_keys_all,
 
 }  // namespace
 
-// called by todhip_db_load for 128 x f32 rows (already resident in ctx->db_desc): bf16 image, norms, Rmax
+// called by todhip_db_load for 128 or 64 x f32 rows (already resident in ctx->db_desc): bf16 image, norms, Rmax
 int tod_l2_db_prepare(todhip_ctx* ctx) {
   L2Ws* ws = tod_ws<L2Ws>(ctx);
   const uint32_t n = (uint32_t)ctx->shard_rows, n_pad = l2_pad_rows(n);
-  TOD_HIP(ws->db_bf16.reserve((size_t)std::max(n_pad, kTileRows) * kDim * 2));
+  TOD_HIP(ws->db_bf16.reserve((size_t)std::max(n_pad, kTileRows) * l2_dim_of(ctx->desc_bytes) * 2));
   TOD_HIP(ws->db_norm.reserve((size_t)std::max(n_pad, kTileRows) * 4));
   TOD_HIP(ws->scal.reserve(64));
   TOD_HIP(hipMemsetAsync(ws->scal.p, 0, 64, ctx->stream));
   if (n_pad)
-    hipLaunchKernelGGL(l2_prepare_kernel, dim3((n_pad + 3u) / 4u), dim3(256), 0, ctx->stream, ctx->db_desc.as<float>(), n,
-                       n_pad, 1.0f, ws->db_bf16.as<uint16_t>(), ws->db_norm.as<float>(), ws->scal.as<uint32_t>(), 1);
+    hipLaunchKernelGGL(l2_kernels(ctx).prepare, dim3((n_pad + 3u) / 4u), dim3(256), 0, ctx->stream, ctx->db_desc.as<float>(), n,
+                       n_pad, 1.0f, ws->db_bf16.as<uint16_t>(), ws->db_norm.as<float>(), ws->scal.as<uint32_t>(), 1,
+                       (const uint32_t*)nullptr, (float*)nullptr, (uint32_t*)nullptr);
   TOD_HIP(hipGetLastError());
   return TODHIP_OK;
 }
@@ -349,7 +378,7 @@ int todhip_match_l2_radius(todhip_ctx* ctx, const float* q_desc, uint32_t nq, fl
   if (rc != TODHIP_OK) return rc;
   TOD_HIP(hipSetDevice(ctx->device));
   const size_t nm = (size_t)nq * max_per_query;
-  TOD_HIP(ctx->m_q.reserve((size_t)nq * kDim * 4));
+  TOD_HIP(ctx->m_q.reserve((size_t)nq * ctx->desc_bytes));
   TOD_HIP(ctx->m_counts.reserve(2u * (size_t)nq * sizeof(uint32_t)));
   uint32_t* d_counts = ctx->m_counts.as<uint32_t>();
   uint32_t* d_in = d_counts + nq;
@@ -360,7 +389,7 @@ int todhip_match_l2_radius(todhip_ctx* ctx, const float* q_desc, uint32_t nq, fl
   uint32_t* h_in = h_counts + nq;
   todhip_dmatch* h_m = reinterpret_cast<todhip_dmatch*>(h_in + nq);
   float* h_xyz = reinterpret_cast<float*>(h_m + nm);
-  TOD_HIP(hipMemcpyAsync(ctx->m_q.p, q_desc, (size_t)nq * kDim * 4, hipMemcpyHostToDevice, ctx->stream));
+  TOD_HIP(hipMemcpyAsync(ctx->m_q.p, q_desc, (size_t)nq * ctx->desc_bytes, hipMemcpyHostToDevice, ctx->stream));
   rc = l2_radius_search(ctx, ctx->m_q.as<float>(), nq, radius, max_per_query, d_counts, h_m, h_xyz, d_in);
   if (rc != TODHIP_OK) return rc;
   TOD_HIP(hipMemcpyAsync(h_counts, d_counts, 2u * (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -413,11 +442,11 @@ int todhip_match_l2(todhip_ctx* ctx, const float* q_desc, uint32_t nq, uint32_t 
   if (db != TODHIP_OK) return db;
   TOD_HIP(hipSetDevice(ctx->device));
   const size_t cap = (size_t)nq * k;
-  TOD_HIP(ctx->m_q.reserve((size_t)nq * kDim * 4));
+  TOD_HIP(ctx->m_q.reserve((size_t)nq * ctx->desc_bytes));
   TOD_HIP(ctx->m_counts.reserve((size_t)nq * 4));
   TOD_HIP(ctx->m_matches.reserve(cap * sizeof(todhip_dmatch)));
   TOD_HIP(ctx->m_xyz.reserve(cap * 12));
-  TOD_HIP(hipMemcpyAsync(ctx->m_q.p, q_desc, (size_t)nq * kDim * 4, hipMemcpyHostToDevice, ctx->stream));
+  TOD_HIP(hipMemcpyAsync(ctx->m_q.p, q_desc, (size_t)nq * ctx->desc_bytes, hipMemcpyHostToDevice, ctx->stream));
   int rc = todhip_match_l2_device(ctx, ctx->m_q.p, nq, k, radius, ctx->m_counts.p, ctx->m_matches.p, ctx->m_xyz.p);
   if (rc != TODHIP_OK) return rc;
   std::vector<uint32_t> counts(nq);

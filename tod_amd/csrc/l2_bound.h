@@ -22,6 +22,10 @@
 //   the matrix cores' f32 accumulation of the 128 exact bf16 x bf16 products onto |r|^2 (136 additions of at most one ulp each, 2^-23,
 //   of a partial sum below |r|^2 + 2 |q^| |r^|: < 2^-15.9 (|q| + Rmax)^2);
 //   together below 2^-15 (|q| + Rmax)^2 -- half of the term. The other half covers the f32 rounding of the threshold A_k + 2 eps.
+// Rows of 64 floats (desc_bytes 256) use the same two constants. No term grows when the width shrinks: the bf16 term is
+// Cauchy-Schwarz and does not know the dimension; the defining sum has 63 rounded additions instead of 127, the matrix cores accumulate
+// 72 times instead of 136, and the narrow prepare kernel's norm is one product and the six shuffle steps without the addition in front.
+// tests/l2_dim64_bound_host_test.cpp holds the inequality at 64 dimensions against binary64 (worst-case families: 0.97 of eps).
 // Domain: finite components, |q|^2 and every |r|^2 normal f32 numbers (no overflow, no underflow). The bound is relative and says
 // nothing once a norm has underflowed.
 #pragma once

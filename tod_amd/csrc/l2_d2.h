@@ -1,4 +1,4 @@
-// The defining distance of the float matcher (include/todhip.h): d2 = sum over i = 0..127 in index order of (q[i] - r[i])^2, every
+// The defining distance of the float matcher (include/todhip.h): d2 = sum over i = 0..dim-1 in index order of (q[i] - r[i])^2, every
 // operation in binary32, rounded once, no fused multiply-add (-ffp-contract=off). Stated once, in steps of four dimensions, for the
 // two translation units that evaluate it: l2.hip (pass 3, the exact scans, the radius search) walks both rows through d2_exact,
 // cross_check.hip's float kernel holds one row in registers and walks the other through d2_step4 -- the same operations in the same
@@ -8,6 +8,7 @@
 
 namespace tod {
 constexpr uint32_t kL2Dim = 128;   // floats per row (l2_plan.h's kDim)
+constexpr uint32_t kL2DimNarrow = 64;   // ... of the narrower float DB (l2_plan.h's kDimNarrow): d2_exact<64>, the same loop body
 }
 
 // d2_exact's loop body for a caller that holds one of the rows in registers: four more dimensions onto a partial sum. (d2_exact does
@@ -21,9 +22,10 @@ __device__ __forceinline__ float d2_step4(float acc, const float4 a, const float
   return acc;
 }
 
+template <uint32_t D = tod::kL2Dim>
 __device__ __forceinline__ float d2_exact(const float* __restrict__ q, const float* __restrict__ r) {
   float acc = 0.f;
-  for (uint32_t i = 0; i < tod::kL2Dim; i += 4) {
+  for (uint32_t i = 0; i < D; i += 4) {
     const float4 a = *reinterpret_cast<const float4*>(q + i), b = *reinterpret_cast<const float4*>(r + i);
     float t = a.x - b.x; acc = acc + t * t;
     t = a.y - b.y; acc = acc + t * t;

@@ -96,7 +96,10 @@ __device__ __forceinline__ void l2_epilogue(const f32x16& sc, float& limit, floa
 // three of four loads hit the CU's L1). The row norms enter as the C operand of a tile's first MFMA, so the accumulator IS
 // the score; the epilogue of query tile t sits behind the MFMAs of tile t + 1 (two accumulators).
 // KT: per-lane list length of pass 1 (1: minimum only, the seed pass; 4 when k <= 4: 16 VGPRs less), unused in pass 2
-template <int PASS, uint32_t KT>
+// D: floats per row, kDim or kDimNarrow. The comments below give kDim's numbers; what depends on the width is taken from l2_plan.h's
+// l2_k_steps (8 or 4 segments, loads and MFMAs per tile), l2_tile_loads (9 or 5: what the vmcnt waits count in) and
+// l2_ring_slot_bytes. At 64 the query fragments are 64 VGPRs and a tile is 4 KB; the geometry, the sink and the epilogues are the same.
+template <int PASS, uint32_t KT, uint32_t D = kDim>
 __global__ __launch_bounds__(256, 2) void l2_gemm_kernel(const uint16_t* __restrict__ db, const float* __restrict__ dbn,
                                                          uint32_t n_tiles, uint32_t tiles_per_chunk, uint32_t tile_stride,
                                                          const uint16_t* __restrict__ qh, uint32_t nq_pad,
@@ -113,12 +116,13 @@ __global__ __launch_bounds__(256, 2) void l2_gemm_kernel(const uint16_t* __restr
   const uint64_t t_start = (PASS == 2 && part) ? __builtin_amdgcn_s_memrealtime() : 0ull;
 
   // this wave's query fragments: B[k = 16 s + 8 h + j][col r] = q^[q_base + 32 t + r][16 s + 8 h + j]
-  bf16x8 bq[kQTilesPerWave][8];
+  constexpr uint32_t kSteps = l2_k_steps(D), kNormOff = kTileRows * D * 2u, kSlotBytes = l2_ring_slot_bytes(D);
+  bf16x8 bq[kQTilesPerWave][kSteps];
 #pragma unroll
   for (uint32_t t = 0; t < kQTilesPerWave; ++t) {
-    const uint16_t* qp = qh + (size_t)(q_base + 32u * t + r) * kDim + 8u * h;
+    const uint16_t* qp = qh + (size_t)(q_base + 32u * t + r) * D + 8u * h;
 #pragma unroll
-    for (uint32_t s = 0; s < 8; ++s) bq[t][s] = *reinterpret_cast<const bf16x8*>(qp + 16u * s);
+    for (uint32_t s = 0; s < kSteps; ++s) bq[t][s] = *reinterpret_cast<const bf16x8*>(qp + 16u * s);
   }
   float best[kQTilesPerWave][KT];
   float limit[kQTilesPerWave];
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void l2_gemm_kernel(const uint16_t* __restr
 #pragma unroll
   for (uint32_t t = 0; t < kQTilesPerWave; ++t) {
 #pragma unroll
-    for (uint32_t s = 0; s < 8; ++s) asm volatile("" :: "v"(bq[t][s]));
+    for (uint32_t s = 0; s < kSteps; ++s) asm volatile("" :: "v"(bq[t][s]));
     asm volatile("" :: "v"(limit[t]));
   }
   // The wave's private ring in LDS: two slots of one DB tile (8 KB of fragments, already in register order) + its 32 row norms
@@ -145,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void l2_gemm_kernel(const uint16_t* __restr
   // gets exactly the 16 bytes lane l loaded. Written as asm, with the vmcnt waits counted by hand: loads retire in order, each
   // tile is exactly 9 of them, and "at most 9 outstanding" therefore means the older of the two tiles in flight has landed
   // (the compiler would wait for everything before any LDS read, which is the depth this ring exists for).
-  __shared__ __attribute__((aligned(16))) uint8_t ring[kWaves][2][kRingSlotBytes];
+  __shared__ __attribute__((aligned(16))) uint8_t ring[kWaves][2][kSlotBytes];
   typedef __attribute__((address_space(3))) void* lptr_t;
   const uint32_t ring_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(size_t)(lptr_t)(&ring[wave][0][0]));
   const uint32_t frag_off = l * 16u, norm_off = r * 4u;
@@ -160,24 +164,26 @@ __global__ __launch_bounds__(256, 2) void l2_gemm_kernel(const uint16_t* __restr
       return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
              (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
     };
-    const uint64_t g = uniform64((uint64_t)(db + (size_t)tile * tile_stride * (kTileRows * kDim)));
+    const uint64_t g = uniform64((uint64_t)(db + (size_t)tile * tile_stride * (kTileRows * D)));
     const uint64_t gn = uniform64((uint64_t)(dbn + (size_t)tile * tile_stride * kTileRows));
-    const uint32_t lds = ring_lds + slot * kRingSlotBytes;
+    const uint32_t lds = ring_lds + slot * kSlotBytes;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the slot's previous tile has been read out
 #pragma unroll
-    for (uint32_t s = 0; s < 8; ++s) L2_DMA("dwordx4", frag_off, g + s * 1024u, lds + s * 1024u);
-    L2_DMA("dword", norm_off, gn, lds + 8192u);
+    for (uint32_t s = 0; s < kSteps; ++s) L2_DMA("dwordx4", frag_off, g + s * 1024u, lds + s * 1024u);
+    L2_DMA("dword", norm_off, gn, lds + kNormOff);
   };
+  // "at most one tile's loads outstanding": the older of the two tiles in flight has landed
+#define L2_WAIT_OLDER_TILE() asm volatile("s_waitcnt vmcnt(%0)" :: "n"(l2_tile_loads(D)) : "memory")
   // One DB tile against the wave's 4 query tiles. The tile's fragments live in ONE register set: the last query tile's
   // MFMA of k-step s is the last reader of a[s], and the next tile's a[s] is read from the ring right behind it (a second
   // set would not fit beside the 128 query registers at two waves per SIMD; LDS latency is what that distance covers).
-  bf16x8 a[8];
+  bf16x8 a[kSteps];
   // |row|^2 of the rows this lane's accumulators belong to (register 4 g + i <-> row 8 g + 4 h + i): the C operand of a query
   // tile's first MFMA. Like a[], ONE register set, reloaded behind its last reader.
   f32x16 nrm;
   auto read_frag = [&](uint32_t slot, uint32_t s) { return *reinterpret_cast<const bf16x8*>(&ring[wave][slot][s * 1024u + frag_off]); };
   auto read_norms = [&](uint32_t slot) {
-    const float* np = reinterpret_cast<const float*>(&ring[wave][slot][8192u]) + 4u * h;
+    const float* np = reinterpret_cast<const float*>(&ring[wave][slot][kNormOff]) + 4u * h;
 #pragma unroll
     for (uint32_t gg = 0; gg < 4; ++gg) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(np + 8u * gg);
@@ -186,20 +192,20 @@ __global__ __launch_bounds__(256, 2) void l2_gemm_kernel(const uint16_t* __restr
   };
   issue(t_begin, 0u);
   issue(t_begin + 1u, 1u);
-  asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+  L2_WAIT_OLDER_TILE();
 #pragma unroll
-  for (uint32_t s = 0; s < 8; ++s) a[s] = read_frag(0u, s);
+  for (uint32_t s = 0; s < kSteps; ++s) a[s] = read_frag(0u, s);
   read_norms(0u);
   uint32_t cur = 0;
   for (uint32_t tile = t_begin; tile < t_end; ++tile, cur ^= 1u) {
     if (!kAblateDma) issue(tile + 2u, cur);                 // in flight now: tile + 1 (the other slot) and tile + 2
     f32x16 acc[2];
     auto mfma_tile = [&](uint32_t t) {
-      if (!kAblateDma && t + 1 == kQTilesPerWave) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");     // tile + 1 has landed
+      if (!kAblateDma && t + 1 == kQTilesPerWave) L2_WAIT_OLDER_TILE();                                // tile + 1 has landed
       f32x16 c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[t][0], nrm, 0, 0, 0);
       if (!kAblateLdsReads && t + 1 == kQTilesPerWave) { a[0] = read_frag(cur ^ 1u, 0u); read_norms(cur ^ 1u); }
 #pragma unroll
-      for (uint32_t s = 1; s < 8; ++s) {
+      for (uint32_t s = 1; s < kSteps; ++s) {
         c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[s], bq[t][s], c, 0, 0, 0);
         if (!kAblateLdsReads && t + 1 == kQTilesPerWave) a[s] = read_frag(cur ^ 1u, s);
       }
@@ -213,6 +219,7 @@ __global__ __launch_bounds__(256, 2) void l2_gemm_kernel(const uint16_t* __restr
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // nothing may still be on its way into this block's LDS when it is handed on
+#undef L2_WAIT_OLDER_TILE
 #undef L2_DMA
 #pragma clang diagnostic pop
   if (PASS == 2) {

@@ -6,9 +6,18 @@
 #include <cstddef>
 #include <cstdint>
 
-constexpr uint32_t kDim = 128;
+constexpr uint32_t kDim = 128;                            // floats per row of the wider of the two float DBs (desc_bytes 512)
+constexpr uint32_t kDimNarrow = 64;                       // ... and of the narrower (desc_bytes 256: SURF, KAZE); DESIGN 6p
 constexpr uint32_t kTileRows = 32;                        // DB rows of one MFMA A tile (8 KB of bf16)
-constexpr uint32_t kRingSlotBytes = kTileRows * kDim * 2u + 256u;   // a wave's ring slot in LDS: one tile's fragments + its 32 norms, twice
+// what of the DB pass depends on the width, each stated once: k-steps of 16 dimensions per tile (one 1 KB wave-load and one MFMA per
+// query tile each), loads per tile (the k-steps' and the norms': what a hand-counted vmcnt counts in), a wave's ring slot in LDS (one
+// tile's fragments + its 32 norms, twice)
+constexpr uint32_t l2_k_steps(uint32_t dim) { return dim / 16u; }
+constexpr uint32_t l2_tile_loads(uint32_t dim) { return l2_k_steps(dim) + 1u; }
+constexpr uint32_t l2_ring_slot_bytes(uint32_t dim) { return kTileRows * dim * 2u + 256u; }
+constexpr uint32_t kRingSlotBytes = l2_ring_slot_bytes(kDim);
+// floats per row of a DB of desc_bytes bytes a row; 0: not a float DB
+constexpr uint32_t l2_dim_of(uint32_t desc_bytes) { return desc_bytes == kDim * 4u ? kDim : desc_bytes == kDimNarrow * 4u ? kDimNarrow : 0u; }
 constexpr uint32_t kQTilesPerWave = 4;
 constexpr uint32_t kWaves = 4;
 constexpr uint32_t kBlockQueries = kWaves * kQTilesPerWave * 32u;   // 512
@@ -53,7 +62,9 @@ struct L2Plan {
 };
 
 // k: the list length per query (the radius search passes max_per_query; it uses the DB pass's geometry and the sizes, not the seed pass)
-inline L2Plan l2_plan(uint32_t n_rows, uint32_t nq, uint32_t k, uint32_t n_cu, const L2Knobs& knobs) {
+// dim: floats per row, kDim or kDimNarrow. The geometry does not depend on it (a wave is 4 query tiles at either width); the queries'
+// bf16 image does
+inline L2Plan l2_plan(uint32_t n_rows, uint32_t nq, uint32_t k, uint32_t n_cu, const L2Knobs& knobs, uint32_t dim = kDim) {
   L2Plan P{};
   P.nq_pad = ((nq + kBlockQueries - 1u) / kBlockQueries) * kBlockQueries;
   P.q_blocks = P.nq_pad / kBlockQueries;
@@ -80,7 +91,7 @@ inline L2Plan l2_plan(uint32_t n_rows, uint32_t nq, uint32_t k, uint32_t n_cu, c
   P.keys_bytes = (size_t)nq * k * 8;
   // a word per padded query; the counters among them: l2_prepare_kernel zeroes one for every row < nq_pad
   P.cand_cnt_bytes = P.flags_bytes = P.q_eps_bytes = P.q_norm_bytes = P.thr_bytes = P.seed_bytes = P.scan_marks_bytes = (size_t)P.nq_pad * 4;
-  P.q_bf16_bytes = (size_t)P.nq_pad * kDim * 2;
+  P.q_bf16_bytes = (size_t)P.nq_pad * dim * 2;
   P.cand_bytes = (size_t)P.nq_pad * kCandCap * 4;
   P.slots_bytes = (size_t)P.nq_pad * P.n_parts * kSlot * 4;        // 2 x 512 partitions x 8 rows x 4 B x 512 queries per query block: 16 MB whatever nq
   P.slot_cnt_bytes = (size_t)P.nq_pad * P.n_parts * 4;

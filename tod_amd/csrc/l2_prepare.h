@@ -39,4 +39,33 @@ __global__ __launch_bounds__(256) void l2_prepare_kernel(const float* __restrict
   }
 }
 
+// The same for rows of kDimNarrow = 64 floats (a sibling, so that the kernel above stays what it is): one wave per row, a lane takes
+// ONE dimension k = l. frag != 0: a 32-row tile is 4 segments (k-steps) of 64 lanes x 16 bytes, 4 KB, in the order stated above.
+// |row|^2: lane l holds v[l]^2, then s += shfl_xor(s, 32 ... 1) -- one product and six shuffle steps, no addition before the tree
+// (tests/l2_dim64_bound_host_test.cpp sums in this order).
+__global__ __launch_bounds__(256) void l2_prepare_narrow_kernel(const float* __restrict__ src, uint32_t n, uint32_t n_pad, float scale,
+                                                                uint16_t* __restrict__ dst, float* __restrict__ norm2,
+                                                                uint32_t* __restrict__ max_norm2_bits, int frag,
+                                                                const uint32_t* __restrict__ rmax2_bits = nullptr,
+                                                                float* __restrict__ eps = nullptr, uint32_t* __restrict__ zero_cnt = nullptr) {
+  const uint32_t row = blockIdx.x * 4u + (threadIdx.x >> 6), l = threadIdx.x & 63u;
+  if (row >= n_pad) return;
+  const float a = row < n ? src[(size_t)row * kDimNarrow + l] : 0.f;
+  const size_t at = frag ? (size_t)(row >> 5) * (kTileRows * kDimNarrow) + (l >> 4) * 512u + (((l >> 3) & 1u) * 32u + (row & 31u)) * 8u + (l & 7u)
+                         : (size_t)row * kDimNarrow + l;
+  dst[at] = tod::l2_bf16_rne(a * scale);
+  float s = a * a;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if (l == 0) {
+    const float n2 = row < n ? s : 3.0e38f;                 // a padding row can never be a candidate
+    norm2[row] = n2;
+    if (row < n && max_norm2_bits) atomicMax(max_norm2_bits, __float_as_uint(s));
+    if (rmax2_bits) {
+      eps[row] = tod::l2_eps(n2, __uint_as_float(*rmax2_bits));
+      zero_cnt[row] = 0u;
+    }
+  }
+}
+
 }  // namespace

@@ -44,7 +44,8 @@ namespace {
 static_assert(kL2SortKeys >= kListCap, "LR sorts every candidate of a query that did not overflow");
 constexpr float kThrMax = 1.0e38f;                        // below the padding rows' score (3e38)
 
-// LT. force[q] = 1: the query is answered by LS (see the head comment)
+// LT. force[q] = 1: the query is answered by LS (see the head comment). D here and below: floats per row (kDim or kDimNarrow)
+template <uint32_t D>
 __global__ __launch_bounds__(256) void l2_radius_threshold_kernel(const float* __restrict__ q, uint32_t nq, uint32_t nq_pad, float radius,
                                                                   const float* __restrict__ eps, float* __restrict__ thr,
                                                                   uint32_t* __restrict__ force) {
@@ -52,8 +53,8 @@ __global__ __launch_bounds__(256) void l2_radius_threshold_kernel(const float* _
   if (qi >= nq_pad) return;
   if (qi >= nq) { thr[qi] = -FLT_MAX; return; }             // padding queries collect nothing
   double n2 = 0.0;
-  for (uint32_t i = 0; i < kDim; i += 4) {
-    const float4 v = *reinterpret_cast<const float4*>(q + (size_t)qi * kDim + i);
+  for (uint32_t i = 0; i < D; i += 4) {
+    const float4 v = *reinterpret_cast<const float4*>(q + (size_t)qi * D + i);
     n2 += (double)v.x * v.x; n2 += (double)v.y * v.y; n2 += (double)v.z * v.z; n2 += (double)v.w * v.w;
   }
   const double r2_up = (double)radius * (double)radius * (1.0 + 0x1p-21);
@@ -80,8 +81,9 @@ __device__ __forceinline__ void l2_block_sort(uint64_t* s, uint32_t n2) {
 }
 
 // the key of (query, row) when the row is inside the radius, the fill value otherwise
+template <uint32_t D>
 __device__ __forceinline__ uint64_t l2_radius_key(const float* __restrict__ q, const float* __restrict__ db, uint32_t row, float radius) {
-  const float d2 = d2_exact(q, db + (size_t)row * kDim);
+  const float d2 = d2_exact<D>(q, db + (size_t)row * D);
   return sqrtf(d2) > radius ? ~0ull : ((uint64_t)__float_as_uint(d2) << 32) | row;
 }
 
@@ -96,6 +98,7 @@ __device__ __forceinline__ void l2_radius_store(const uint64_t* s, uint32_t coun
 // LR. One workgroup per query: its candidate rows (the lanes' slots, then the shared list) into LDS, flagged under
 // l2_rerank_kernel's two conditions; otherwise the exact key of every candidate, the count of real keys, a sort, the cut. Keys are
 // unique (a row is one lane's in one chunk), so the result does not depend on the order in which the slots were appended.
+template <uint32_t D>
 __global__ __launch_bounds__(256) void l2_radius_refine_kernel(const float* __restrict__ q, const float* __restrict__ db,
                                                                const uint32_t* __restrict__ slots, const uint32_t* __restrict__ slot_cnt,
                                                                uint32_t n_parts, const uint32_t* __restrict__ cand,
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256) void l2_radius_refine_kernel(const float* __re
   while (n2 < total) n2 <<= 1;
   uint32_t mine = 0;
   for (uint32_t c = tid; c < n2; c += 256u) {
-    const uint64_t key = c < total ? l2_radius_key(q + (size_t)qi * kDim, db, s_rows[c], radius) : ~0ull;
+    const uint64_t key = c < total ? l2_radius_key<D>(q + (size_t)qi * D, db, s_rows[c], radius) : ~0ull;
     s_keys[c] = key;
     mine += key != ~0ull ? 1u : 0u;
   }
@@ -142,6 +145,7 @@ __global__ __launch_bounds__(256) void l2_radius_refine_kernel(const float* __re
 // `worst`, the max_per_query-th best at that sort (later keys at or above it can never be among the first max_per_query). A slice's
 // keys are appended in row order (ballot, prefix over the four waves), so the buffer's content is the same on every run; when the
 // next slice might not fit, all 2048 keys are sorted and the lower half is the new best.
+template <uint32_t D>
 __global__ __launch_bounds__(256) void l2_radius_scan_kernel(const float* __restrict__ q, const float* __restrict__ db, uint32_t n,
                                                              const uint32_t* __restrict__ flagged, float radius, uint32_t mpq,
                                                              uint64_t* __restrict__ keys, uint32_t* __restrict__ counts,
@@ -166,7 +170,7 @@ __global__ __launch_bounds__(256) void l2_radius_scan_kernel(const float* __rest
       __syncthreads();
     }
     const uint32_t row = row0 + tid;
-    const uint64_t key = row < n ? l2_radius_key(q + (size_t)qi * kDim, db, row, radius) : ~0ull;
+    const uint64_t key = row < n ? l2_radius_key<D>(q + (size_t)qi * D, db, row, radius) : ~0ull;
     mine += key != ~0ull ? 1u : 0u;
     const bool take = key < worst;                          // ~0 is never below worst
     const unsigned long long b = __builtin_amdgcn_ballot_w64(take);

@@ -48,6 +48,7 @@ __global__ __launch_bounds__(256) void l2_threshold_kernel(const float* __restri
 
 // (the defining distance, d2_exact: l2_d2.h)
 static_assert(kDim == tod::kL2Dim, "l2_d2.h states the distance over kDim dimensions");
+static_assert(kDimNarrow == tod::kL2DimNarrow, "... and over kDimNarrow dimensions");
 
 __device__ __forceinline__ void keys_insert(uint64_t (&best)[kTop], uint64_t key) {
 #pragma unroll
@@ -100,7 +101,8 @@ __device__ __forceinline__ void l2_write_match(uint64_t key, float dist, uint32_
   o[0] = pts[(size_t)row * 3 + 0]; o[1] = pts[(size_t)row * 3 + 1]; o[2] = pts[(size_t)row * 3 + 2];
 }
 
-// pass 3: one wave per query. keys[q][k] = (f32 bits of d2) << 32 | row, ascending, ~0 padded
+// pass 3: one wave per query. keys[q][k] = (f32 bits of d2) << 32 | row, ascending, ~0 padded. D: floats per row (kDim or kDimNarrow)
+template <uint32_t D>
 __global__ __launch_bounds__(256) void l2_rerank_kernel(const float* __restrict__ q, uint32_t nq, const float* __restrict__ db,
                                                         const uint32_t* __restrict__ slots, const uint32_t* __restrict__ slot_cnt,
                                                         uint32_t n_parts, const uint32_t* __restrict__ cand,
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(256) void l2_rerank_kernel(const float* __restrict_
   for (uint32_t j = 0; j < kTop; ++j) best[j] = ~0ull;
   for (uint32_t c = l; c < total; c += 64u) {
     const uint32_t row = s_rows[w][c];
-    const float d2 = d2_exact(q + (size_t)qi * kDim, db + (size_t)row * kDim);
+    const float d2 = d2_exact<D>(q + (size_t)qi * D, db + (size_t)row * D);
     keys_insert(best, ((uint64_t)__float_as_uint(d2) << 32) | row);
   }
   wave_select(best, k, keys + (size_t)qi * k);
@@ -142,6 +144,7 @@ __global__ __launch_bounds__(256) void l2_rerank_kernel(const float* __restrict_
 
 // fallback for queries whose candidate list overflowed (and the test hook's exact GPU reference): one block per
 // query scans every DB row with the defining distance
+template <uint32_t D>
 __global__ __launch_bounds__(256) void l2_exact_scan_kernel(const float* __restrict__ q, uint32_t nq, const float* __restrict__ db,
                                                             uint32_t n, uint32_t k, const uint32_t* __restrict__ only_flagged,
                                                             uint64_t* __restrict__ keys) {
@@ -152,7 +155,7 @@ __global__ __launch_bounds__(256) void l2_exact_scan_kernel(const float* __restr
 #pragma unroll
   for (uint32_t j = 0; j < kTop; ++j) best[j] = ~0ull;
   for (uint32_t row = tid; row < n; row += 256u) {
-    const float d2 = d2_exact(q + (size_t)qi * kDim, db + (size_t)row * kDim);
+    const float d2 = d2_exact<D>(q + (size_t)qi * D, db + (size_t)row * D);
     keys_insert(best, ((uint64_t)__float_as_uint(d2) << 32) | row);
   }
   wave_select(best, kTop, s_keys[w]);

@@ -13,6 +13,8 @@
 // carry (row + shard_first < 2^32). Why the merged result is the unsharded one whatever each shard's Rmax, eps and path: every shard
 // call ends in the EXACT keys of its rows (pass 3, the exact scan, LR or LS: the defining d2 in the defining order), the filter
 // before it only decides how they are found. The union of exact per-shard answers is searched with integer comparisons alone.
+// The row width (128 or 64 floats) is the context's: the searches these kernels continue pick their instantiations from
+// ctx->desc_bytes (l2_kernels, l2.hip), and nothing here looks inside a row -- a key is a key at either width.
 #pragma once
 
 #include "shard_merge.h"

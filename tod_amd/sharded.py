@@ -23,6 +23,8 @@ A float DB (128 x f32 rows, L2) goes through the same steps: `Sharded
 as bytes, `GpuOps(metric="l2")` calls todhip_match_l2_shard_device + todhip_merge_l2_shards_device[_on], or with `max_per_query`
 todhip_match_l2_radius_shard_device + todhip_merge_l2_radius_shards_device[_on]. A key is then binary32 bits of d2 << 32 | global row,
 the radius is a float, and the merged result is that of todhip_match_l2_device / todhip_match_l2_radius_device on the whole DB.
+The narrower float DB (64 x f32 rows: SURF, KAZE) is `ShardedMatcher(desc_bytes=256)` with the same `GpuOps(metric="l2")`:
+the gathered query rows are 256 bytes, and `GpuOps.match_shard` refuses rows of another width than the resident shard's.
 
 `ShardedMatcher` is the ONE implementation of steps 1-4's choreography: bench.py runs it on the GPU (GpuOps: torch
 streams/events, RCCL through torch.distributed, libtodhip for the compute) and tests/test_sharded_cpu.py runs the same
@@ -208,6 +210,8 @@ class GpuOps:
             out.view(-1).copy_(o.to(out.device))
 
     def match_shard(self, q_all, n, keys_out):
+        if self.metric == "l2" and q_all.shape[-1] * q_all.element_size() != self.ctx.desc_bytes():   # ShardedMatcher(desc_bytes=256 or 512)
+            raise ValueError("query rows of %d bytes against a float DB of %d-byte rows" % (q_all.shape[-1] * q_all.element_size(), self.ctx.desc_bytes()))
         if self.metric == "l2" and self.max_per_query is not None:
             self.ctx.match_l2_radius_shard_device(q_all.data_ptr(), n, self.radius, self.max_per_query, keys_out.data_ptr())
         elif self.metric == "l2":
