@@ -3,14 +3,21 @@
 The shared library is the product; this module only loads it and marshals numpy / torch
 buffers to plain pointers. There is no CPU fallback: if the library or the GPU is missing,
 loading or context creation raises.
+
+Every prototype comes from include/todhip.h: the header is parsed when this module is imported (the import fails without it, or on a
+declaration it cannot read) and lib() sets argtypes and restype of each function it declares, so a signature is written once, there. An argument of the wrong kind -- a ctypes wrapper of another type than the header's, a float for an
+integer, a numpy scalar for a pointer -- therefore raises ctypes.ArgumentError at the call; it is never truncated or reinterpreted.
+Plain Python and numpy integers, bool, None (NULL), byref(...), ctypes arrays and instances of the header's own type pass.
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "todhip.h")
 # TODHIP_LIB_PATH: another build of the same library (the diagnostics builds of tools/*_ablate.sh, an A/B against HEAD) -- loaded
 # instead of, never copied over, the product file
 LIB_PATH = os.environ.get("TODHIP_LIB_PATH") or os.path.join(_PKG, "libtodhip.so")
@@ -73,46 +80,42 @@ class PatternStats(C.Structure):
     _fields_ = [("n_keypoints", C.c_uint32), ("n_candidates", C.c_uint32), ("accepted_in_round", C.c_uint32 * 6)]
 
 
-# every symbol include/todhip.h declares (checked by tests/test_abi.py against the header text)
-EXPORTS = [
-    "todhip_version", "todhip_create", "todhip_destroy", "todhip_stream", "todhip_last_hip_error",
-    "todhip_synchronize", "todhip_get_counters", "todhip_set_cu_partition", "todhip_stream_create", "todhip_stream_destroy", "todhip_set_kernel_timing", "todhip_set_matcher_engine", "todhip_set_matcher_block_split", "todhip_set_ratio_test", "todhip_db_load", "todhip_db_load_device", "todhip_db_info",
-    "todhip_match", "todhip_match_device", "todhip_match_shard_device", "todhip_merge_shards_device", "todhip_merge_shards_device_on",
-    "todhip_rng_seed", "todhip_verify", "todhip_orb", "todhip_orb_masked", "todhip_test_clique", "todhip_test_clique_gate",
-    "todhip_verify_trace", "todhip_test_adjacency", "todhip_test_consensus", "todhip_verify_device",
-    "todhip_orb_device", "todhip_verify_device_depth", "todhip_orb_batch_device",
-    "todhip_verify_batch_device", "todhip_verify_batch_device_depth",
-    "todhip_match_l2", "todhip_match_l2_device",
-    "todhip_model_begin", "todhip_model_add_observation", "todhip_model_finish", "todhip_model_device", "todhip_model_free",
-    "todhip_model_add_rows", "todhip_model_compact",
-    "todhip_rescale_depth", "todhip_rescale_depth_device", "todhip_verify_2d", "todhip_verify_2d_device", "todhip_verify_2d_batch_device", "todhip_set_lsh",
-    "todhip_set_db_bit_order", "todhip_db_bit_order",
-    "todhip_pipeline_default_params", "todhip_pipeline_create", "todhip_pipeline_destroy", "todhip_pipeline_matcher",
-    "todhip_pipeline_db_load", "todhip_pipeline_db_load_device", "todhip_pipeline_submit", "todhip_pipeline_submit_device",
-    "todhip_pipeline_wait", "todhip_pipeline_get_stats", "todhip_bgr_to_gray_device",
-    "todhip_pattern_learn_begin", "todhip_pattern_learn_add_view", "todhip_pattern_learn_add_view_device", "todhip_pattern_learn_finish",
-    "todhip_pattern_learn_responses", "todhip_pattern_learn_free", "todhip_pipeline_set_pattern",
-    "todhip_db_select_objects", "todhip_db_selection", "todhip_pipeline_select_objects",
-    "todhip_match_radius", "todhip_match_radius_device",
-    "todhip_match_radius_shard_device", "todhip_merge_radius_shards_device", "todhip_merge_radius_shards_device_on",
-    "todhip_db_desc_bytes",
-    "todhip_orb_batch_device_masked", "todhip_verify_device_depth_rescaled", "todhip_verify_batch_device_depth_rescaled",
-    "todhip_test_depth_lookup", "todhip_pipeline_set_depth_size", "todhip_pipeline_submit_masked", "todhip_pipeline_submit_masked_device",
-    "todhip_model_add_observations_device",
-    "todhip_match_l2_radius", "todhip_match_l2_radius_device",
-    "todhip_test_draw_table", "todhip_test_kabsch",
-    "todhip_cross_check_device", "todhip_set_cross_check", "todhip_pipeline_set_cross_check",
-    "todhip_match_l2_shard_device", "todhip_merge_l2_shards_device", "todhip_merge_l2_shards_device_on",
-    "todhip_match_l2_radius_shard_device", "todhip_merge_l2_radius_shards_device", "todhip_merge_l2_radius_shards_device_on",
-    "todhip_set_l2_ratio_test", "todhip_cross_check_l2_device", "todhip_set_l2_cross_check",
-]
+_SCALARS = {"uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "int": C.c_int, "float": C.c_float}
+_DECLARATION = re.compile(r"\b(\w+\s*\**)\s*\b(todhip_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _prototypes(path):
+    """{name: (restype, argtypes)} of every function the header at `path` declares, in its order. A pointer or an array is c_void_p,
+    the scalars are _SCALARS; a parameter of any other type raises (it would have to be guessed)."""
+    with open(path) as f:
+        code = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    protos = {}
+    for ret, name, params in _DECLARATION.findall(code):
+        argtypes = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = [w for w in p.split() if w != "const"]
+            if "*" in p or "[" in p:
+                argtypes.append(C.c_void_p)
+            elif words and words[0] in _SCALARS:
+                argtypes.append(_SCALARS[words[0]])
+            else:
+                raise RuntimeError("%s: %s declares a parameter '%s' of a type the binding does not know" % (path, name, " ".join(p.split())))
+        protos[name] = (C.c_void_p if "*" in ret else None if ret.strip() == "void" else C.c_int, argtypes)
+    unread = set(re.findall(r"\b(todhip_\w+)\s*\(", code)) - set(protos)      # e.g. a parameter list with parentheses of its own
+    if unread:
+        raise RuntimeError("%s: the binding cannot read the declaration of %s" % (path, ", ".join(sorted(unread))))
+    return protos
+
+
+# the header is read once, when this module is imported (the tree carries it beside the package; without it the import fails)
+_PROTOTYPES = _prototypes(HEADER_PATH)
+# every symbol include/todhip.h declares, in its order (tests/test_abi.py checks them and their prototypes against the header text)
+EXPORTS = list(_PROTOTYPES)
 
 MAX_TRAIN_BATCH_VIEWS = 64
 
-# todhip_model_add_observations_device's arguments in the header's order (tests/test_train_batch_cpu.py compares them with its text)
-_u32, _vp, _ci = C.c_uint32, C.c_void_p, C.c_int
-ADD_OBSERVATIONS_DEVICE_ARGTYPES = [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _ci, _u32, _u32, _ci, _u32, _u32, _u32, _vp, _vp, _vp,
-                                    _u32, _u32, C.c_float, _vp, _vp]
+# todhip_model_add_observations_device's arguments in the header's order: kept as a name for callers of earlier versions, read from the header
+ADD_OBSERVATIONS_DEVICE_ARGTYPES = _PROTOTYPES["todhip_model_add_observations_device"][1]
 
 MAX_PER_QUERY_LIMIT = 1024
 
@@ -151,85 +154,10 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        L.todhip_stream.restype = C.c_void_p
-        L.todhip_destroy.restype = None
-        L.todhip_rng_seed.restype = None
-        L.todhip_model_free.restype = None
-        L.todhip_pipeline_destroy.restype = None
-        L.todhip_pattern_learn_free.restype = None
-        L.todhip_pipeline_matcher.restype = C.c_void_p
-        L.todhip_set_db_bit_order.argtypes, L.todhip_set_db_bit_order.restype = [C.c_void_p, C.c_int], C.c_int
-        L.todhip_db_bit_order.argtypes, L.todhip_db_bit_order.restype = [C.c_void_p, C.c_void_p], C.c_int
-        if hasattr(L, "todhip_db_select_objects"):                    # (TODHIP_LIB_PATH may name a build from before the selection)
-            L.todhip_db_select_objects.argtypes, L.todhip_db_select_objects.restype = [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int
-            L.todhip_db_selection.argtypes, L.todhip_db_selection.restype = [C.c_void_p] * 4, C.c_int
-            L.todhip_pipeline_select_objects.argtypes, L.todhip_pipeline_select_objects.restype = [C.c_void_p, C.c_void_p, C.c_uint32], C.c_int
-        if hasattr(L, "todhip_model_compact"):                        # (as above)
-            L.todhip_model_add_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-            L.todhip_model_add_rows.restype = C.c_int
-            L.todhip_model_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_uint32] + [C.c_void_p] * 4
-            L.todhip_model_compact.restype = C.c_int
-        if hasattr(L, "todhip_match_radius"):                         # (as above)
-            L.todhip_match_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
-            L.todhip_match_radius.restype = C.c_int
-            L.todhip_match_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
-            L.todhip_match_radius_device.restype = C.c_int
-        if hasattr(L, "todhip_match_radius_shard_device"):            # (as above)
-            L.todhip_match_radius_shard_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-            L.todhip_match_radius_shard_device.restype = C.c_int
-            L.todhip_merge_radius_shards_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
-            L.todhip_merge_radius_shards_device.restype = C.c_int
-            L.todhip_merge_radius_shards_device_on.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
-            L.todhip_merge_radius_shards_device_on.restype = C.c_int
-        if hasattr(L, "todhip_db_desc_bytes"):                        # (as above)
-            L.todhip_db_desc_bytes.argtypes, L.todhip_db_desc_bytes.restype = [C.c_void_p, C.c_void_p], C.c_int
-        if hasattr(L, "todhip_verify_device_depth_rescaled"):        # (as above)
-            u32, vp, ci = C.c_uint32, C.c_void_p, C.c_int
-            L.todhip_orb_batch_device_masked.argtypes = [vp, vp, vp, u32, C.c_uint64, u32, u32, u32, u32, u32, C.c_float, vp, vp, vp, vp, u32, vp]
-            L.todhip_orb_batch_device_masked.restype = ci
-            tail = [vp, vp, vp, u32, vp, u32, vp, vp, vp, vp]        # counts, matches, xyz, k, spans, n_objs, params, rng, poses, n_poses
-            L.todhip_verify_device_depth_rescaled.argtypes = [vp, vp, u32, vp, ci, u32, u32, ci, u32, u32, vp] + tail + [vp, vp]
-            L.todhip_verify_device_depth_rescaled.restype = ci
-            L.todhip_verify_batch_device_depth_rescaled.argtypes = [vp, u32, vp, u32, vp, ci, u32, u32, ci, u32, u32, vp] + tail + [vp, vp, vp]
-            L.todhip_verify_batch_device_depth_rescaled.restype = ci
-            L.todhip_test_depth_lookup.argtypes, L.todhip_test_depth_lookup.restype = [vp, vp, ci, u32, u32, ci, u32, u32, vp, u32, vp], ci
-            L.todhip_pipeline_set_depth_size.argtypes, L.todhip_pipeline_set_depth_size.restype = [vp, u32, u32, ci], ci
-            L.todhip_pipeline_submit_masked.argtypes, L.todhip_pipeline_submit_masked.restype = [vp, vp, vp, vp, u32, vp], ci
-            L.todhip_pipeline_submit_masked_device.argtypes, L.todhip_pipeline_submit_masked_device.restype = [vp, vp, vp, vp, u32, vp], ci
-        if hasattr(L, "todhip_model_add_observations_device"):       # (as above)
-            L.todhip_model_add_observations_device.argtypes = ADD_OBSERVATIONS_DEVICE_ARGTYPES
-            L.todhip_model_add_observations_device.restype = C.c_int
-        if hasattr(L, "todhip_match_l2_radius"):                      # (as above)
-            L.todhip_match_l2_radius.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 5
-            L.todhip_match_l2_radius.restype = C.c_int
-            L.todhip_match_l2_radius_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_uint32] + [C.c_void_p] * 4
-            L.todhip_match_l2_radius_device.restype = C.c_int
-        if hasattr(L, "todhip_match_l2_shard_device"):                # (as above)
-            u32, vp, f32 = C.c_uint32, C.c_void_p, C.c_float
-            L.todhip_match_l2_shard_device.argtypes, L.todhip_match_l2_shard_device.restype = [vp, vp, u32, u32, vp], C.c_int
-            L.todhip_merge_l2_shards_device.argtypes, L.todhip_merge_l2_shards_device.restype = [vp, vp, u32, u32, u32, f32, vp, vp, vp], C.c_int
-            L.todhip_merge_l2_shards_device_on.argtypes = [vp, vp, vp, u32, u32, u32, f32, vp, vp, vp]
-            L.todhip_merge_l2_shards_device_on.restype = C.c_int
-            L.todhip_match_l2_radius_shard_device.argtypes, L.todhip_match_l2_radius_shard_device.restype = [vp, vp, u32, f32, u32, vp], C.c_int
-            L.todhip_merge_l2_radius_shards_device.argtypes = [vp, vp, u32, u32, u32, vp, vp, vp, vp]
-            L.todhip_merge_l2_radius_shards_device.restype = C.c_int
-            L.todhip_merge_l2_radius_shards_device_on.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp, vp, vp]
-            L.todhip_merge_l2_radius_shards_device_on.restype = C.c_int
-        if hasattr(L, "todhip_test_draw_table"):                      # (as above)
-            L.todhip_test_draw_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-            L.todhip_test_draw_table.restype = C.c_int
-        if hasattr(L, "todhip_test_kabsch"):                          # (as above)
-            L.todhip_test_kabsch.argtypes, L.todhip_test_kabsch.restype = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4, C.c_int
-        if hasattr(L, "todhip_cross_check_device"):                   # (as above)
-            L.todhip_cross_check_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
-            L.todhip_cross_check_device.restype = C.c_int
-            L.todhip_set_cross_check.argtypes, L.todhip_set_cross_check.restype = [C.c_void_p, C.c_uint32], C.c_int
-            L.todhip_pipeline_set_cross_check.argtypes, L.todhip_pipeline_set_cross_check.restype = [C.c_void_p, C.c_int], C.c_int
-        if hasattr(L, "todhip_cross_check_l2_device"):                # (as above)
-            L.todhip_set_l2_ratio_test.argtypes, L.todhip_set_l2_ratio_test.restype = [C.c_void_p, C.c_float], C.c_int
-            L.todhip_cross_check_l2_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 3
-            L.todhip_cross_check_l2_device.restype = C.c_int
-            L.todhip_set_l2_cross_check.argtypes, L.todhip_set_l2_cross_check.restype = [C.c_void_p, C.c_uint32], C.c_int
+        for name, (restype, argtypes) in _PROTOTYPES.items():
+            f = getattr(L, name, None)            # TODHIP_LIB_PATH may name a build of an older commit: what it lacks stays an AttributeError
+            if f is not None:
+                f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -240,13 +168,52 @@ class TodError(RuntimeError):
         self.status = status
 
 
-def _check(rc, what):
+def _call(name, *args):
+    """The library's function `name` on args; a status other than OK raises TodError(status, name)."""
+    rc = getattr(lib(), name)(*args)
     if rc != OK:
-        raise TodError(rc, what)
+        raise TodError(rc, name)
 
 
 def _np_ptr(a):
-    return C.c_void_p(a.ctypes.data)
+    """The pointer of a numpy array; None (an optional array that is absent) stays None: NULL"""
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
+def _opt(a, dtype):
+    """An optional array (pattern, mask) as a contiguous one of dtype, or None"""
+    return None if a is None else np.ascontiguousarray(a, dtype)
+
+
+def _objects(desc, pts, obj_off):
+    """(TodObject[n_obj], n_obj, bytes per row) of DB rows in host memory: desc [N, width], pts f32[N, 3], both contiguous and held
+    by the caller during the call; rows of object o are obj_off[o]:obj_off[o+1]"""
+    obj_off = np.asarray(obj_off, np.int64)
+    n_obj = len(obj_off) - 1
+    B = (desc.shape[1] if desc.ndim == 2 else 32) * desc.itemsize
+    objs = (TodObject * max(n_obj, 1))()
+    for o in range(n_obj):
+        lo, hi = int(obj_off[o]), int(obj_off[o + 1])
+        objs[o].desc, objs[o].pts_xyz, objs[o].n = desc.ctypes.data + lo * B, pts.ctypes.data + lo * 12, hi - lo
+    return objs, n_obj, B
+
+
+def _model_objects(models):
+    """(TodObject[len(models)], obj_off u32[len(models) + 1]) of trained models (capi.Model) in device memory"""
+    objs = (TodObject * len(models))()
+    off = [0]
+    for i, m in enumerate(models):
+        objs[i].desc, objs[i].pts_xyz, objs[i].n = m.device()
+        off.append(off[-1] + objs[i].n)
+    return objs, np.asarray(off, np.uint32)
+
+
+def _frame_limits(frame_nq, nq, frame_queries, what):
+    """frame_nq of a cross-check as u32[ceil(nq / frame_queries)] (None stays None); another length is TodError(EINVAL)"""
+    fn = _opt(frame_nq, np.uint32)
+    if fn is not None and len(fn) != (nq + frame_queries - 1) // max(frame_queries, 1):
+        raise TodError(EINVAL, "%s (frame_nq of %d entries for %d queries in frames of %d)" % (what, len(fn), nq, frame_queries))
+    return fn
 
 
 def _ids_in(ids):
@@ -272,11 +239,6 @@ def _strided_rows(a, stride, W=None):
 
 def _k9(K):
     return np.ascontiguousarray(K, np.float32).reshape(9)
-
-
-def _verify_in(spans, min_inliers, n_iter, err):
-    """What every verify* call passes in besides its frame: (spans f32[n_objs], VerifyParams). The caller holds both during the call."""
-    return np.ascontiguousarray(spans, np.float32), VerifyParams(min_inliers, n_iter, err)
 
 
 def _pose_out(max_poses, n_kp, n_frames=None, cache=None):
@@ -305,8 +267,7 @@ class Context:
 
     def __init__(self, device=0, stream=None):
         self._h = C.c_void_p()
-        _check(lib().todhip_create(C.c_int(device), C.c_void_p(stream), C.byref(self._h)), "todhip_create")
-        self._keep = None
+        _call("todhip_create", device, stream, C.byref(self._h))
 
     def close(self):
         if self._h:
@@ -324,44 +285,43 @@ class Context:
         return lib().todhip_stream(self._h)
 
     def synchronize(self):
-        _check(lib().todhip_synchronize(self._h), "todhip_synchronize")
+        _call("todhip_synchronize", self._h)
 
     def counters(self):
         c = Counters()
-        _check(lib().todhip_get_counters(self._h, C.byref(c)), "todhip_get_counters")
+        _call("todhip_get_counters", self._h, C.byref(c))
         return c
 
     def set_matcher_engine(self, engine):
         """0 auto, 1 vector ALU (K4), 2 matrix cores (K4x): identical results"""
-        _check(lib().todhip_set_matcher_engine(self._h, C.c_int({"auto": 0, "valu": 1, "mfma": 2}.get(engine, engine))),
-               "todhip_set_matcher_engine")
+        _call("todhip_set_matcher_engine", self._h, {"auto": 0, "valu": 1, "mfma": 2}.get(engine, engine))
 
     def set_matcher_block_split(self, split):
         """-1 adaptive (default), 0 whole blocks, 2 / 3: the matrix-core engine's blocks stop after that many of their 4 matrix
         instructions when no partial sum can still reach a threshold: identical results"""
-        _check(lib().todhip_set_matcher_block_split(self._h, C.c_int(split)), "todhip_set_matcher_block_split")
+        _call("todhip_set_matcher_block_split", self._h, split)
 
     def set_ratio_test(self, ratio):
         """Lowe's ratio test on the two nearest neighbours (0 = off, the reference's effective setting)"""
-        _check(lib().todhip_set_ratio_test(self._h, C.c_float(ratio)), "todhip_set_ratio_test")
+        _call("todhip_set_ratio_test", self._h, ratio)
 
     def set_lsh(self, n_tables, key_size=16, multi_probe_level=1):
         """LSH-approximate mode of the Hamming matcher (0 tables = the exact search, the default)."""
-        _check(lib().todhip_set_lsh(self._h, C.c_uint32(n_tables), C.c_uint32(key_size), C.c_uint32(multi_probe_level)), "todhip_set_lsh")
+        _call("todhip_set_lsh", self._h, n_tables, key_size, multi_probe_level)
 
     def set_db_bit_order(self, mode):
         """0 off (default), 1 informative bits first: the db_load calls that follow store the rows' bit positions in that order and the
         match calls permute their queries alike -- identical results (todhip_set_db_bit_order)"""
-        _check(lib().todhip_set_db_bit_order(self._h, C.c_int(mode)), "todhip_set_db_bit_order")
+        _call("todhip_set_db_bit_order", self._h, mode)
 
     def db_bit_order(self):
         """u8[256]: stored position p of the resident DB holds original bit src_of[p] (the identity when off / nothing loaded)"""
         src_of = np.zeros(256, np.uint8)
-        _check(lib().todhip_db_bit_order(self._h, _np_ptr(src_of)), "todhip_db_bit_order")
+        _call("todhip_db_bit_order", self._h, _np_ptr(src_of))
         return src_of
 
     def set_kernel_timing(self, enable):
-        _check(lib().todhip_set_kernel_timing(self._h, C.c_int(1 if enable else 0)), "todhip_set_kernel_timing")
+        _call("todhip_set_kernel_timing", self._h, 1 if enable else 0)
 
     # ---------------------------------------------------------------- stage B
     def db_load(self, desc, pts, obj_off, shard_rank=0, shard_count=1):
@@ -371,84 +331,60 @@ class Context:
         The width of desc is the DB's desc_bytes: the match calls take queries of that width."""
         desc = np.ascontiguousarray(desc, np.float32 if np.asarray(desc).dtype == np.float32 else np.uint8)
         pts = np.ascontiguousarray(pts, np.float32)
-        obj_off = np.asarray(obj_off, np.int64)
-        n_obj = len(obj_off) - 1
-        objs = (TodObject * max(n_obj, 1))()
-        B = (desc.shape[1] if desc.ndim == 2 else 32) * desc.itemsize
-        for o in range(n_obj):
-            lo, hi = int(obj_off[o]), int(obj_off[o + 1])
-            objs[o].desc = desc.ctypes.data + lo * B
-            objs[o].pts_xyz = pts.ctypes.data + lo * 12
-            objs[o].n = hi - lo
+        objs, n_obj, B = _objects(desc, pts, obj_off)
         spans = np.zeros(max(n_obj, 1), np.float32)
-        rc = lib().todhip_db_load(self._h, objs, C.c_uint32(n_obj), C.c_uint32(B), C.c_uint32(shard_rank),
-                                  C.c_uint32(shard_count), _np_ptr(spans))
-        _check(rc, "todhip_db_load")
+        _call("todhip_db_load", self._h, objs, n_obj, B, shard_rank, shard_count, _np_ptr(spans))
         return spans[:n_obj]
 
     def db_load_models(self, models, shard_rank=0, shard_count=1):
         """Object DB straight from trained models (capi.Model) in this device's memory: no host copy of descriptors or points
         (todhip_model_device + todhip_db_load_device). Returns (spans, obj_off)."""
-        objs = (TodObject * len(models))()
-        off = [0]
-        for i, m in enumerate(models):
-            d, p, n = m.device()
-            objs[i].desc, objs[i].pts_xyz, objs[i].n = d, p, n
-            off.append(off[-1] + n)
+        objs, off = _model_objects(models)
         spans = np.zeros(len(models), np.float32)
-        _check(lib().todhip_db_load_device(self._h, objs, C.c_uint32(len(models)), C.c_uint32(32), C.c_uint32(shard_rank),
-                                           C.c_uint32(shard_count), _np_ptr(spans)), "todhip_db_load_device")
-        return spans, np.asarray(off, np.uint32)
+        _call("todhip_db_load_device", self._h, objs, len(models), 32, shard_rank, shard_count, _np_ptr(spans))
+        return spans, off
 
     def db_info(self):
         tot, first, rows, nobj = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32()
-        _check(lib().todhip_db_info(self._h, C.byref(tot), C.byref(first), C.byref(rows), C.byref(nobj)),
-               "todhip_db_info")
+        _call("todhip_db_info", self._h, C.byref(tot), C.byref(first), C.byref(rows), C.byref(nobj))
         return dict(total_rows=tot.value, shard_first=first.value, shard_rows=rows.value, n_objs=nobj.value)
 
     def desc_bytes(self):
         """Bytes per row of the resident DB (32, 64 or 512; 0 before the first load): todhip_db_desc_bytes. 256: the float DB of
         64 x f32 rows."""
         b = C.c_uint32()
-        _check(lib().todhip_db_desc_bytes(self._h, C.byref(b)), "todhip_db_desc_bytes")
+        _call("todhip_db_desc_bytes", self._h, C.byref(b))
         return b.value
 
-    def _query_rows(self, q_desc, what):
-        """q_desc as contiguous u8[nq, desc_bytes]. A query matrix of another width than a binary DB's is refused here with
-        TodError(EINVAL): the library sees a pointer and would read it at the DB's stride."""
-        q = np.ascontiguousarray(q_desc, np.uint8)
-        B = self.desc_bytes() if hasattr(lib(), "todhip_db_desc_bytes") else 0
-        if B in (32, 64) and q.ndim == 2 and q.shape[1] != B:
-            raise TodError(EINVAL, "%s (queries of shape %s against a DB of %d-byte descriptors)" % (what, q.shape, B))
-        return q
-
-    def _query_rows_l2(self, q_desc, what):
-        """q_desc as contiguous f32[nq, dim]. A query matrix of another width than a float DB's (64 or 128) is refused here with
-        TodError(EINVAL), as _query_rows refuses it for a binary DB."""
-        q = np.ascontiguousarray(q_desc, np.float32)
-        B = self.desc_bytes() if hasattr(lib(), "todhip_db_desc_bytes") else 0
-        if B in (256, 512) and q.ndim == 2 and q.shape[1] * 4 != B:
-            raise TodError(EINVAL, "%s (queries of shape %s against a DB of %d x f32 descriptors)" % (what, q.shape, B // 4))
+    def _query_rows(self, q_desc, dtype, what):
+        """q_desc as contiguous dtype[nq, width]: u8 for a binary DB (32 or 64 bytes a row), f32 for a float DB (64 or 128 a row). A
+        query matrix of another width than such a DB's is refused here with TodError(EINVAL): the library sees a pointer and would
+        read it at the DB's stride."""
+        q = np.ascontiguousarray(q_desc, dtype)
+        B, is_float = self.desc_bytes(), q.itemsize == 4
+        if B in ((256, 512) if is_float else (32, 64)) and q.ndim == 2 and q.shape[1] * q.itemsize != B:
+            raise TodError(EINVAL, "%s (queries of shape %s against a DB of %s descriptors)"
+                           % (what, q.shape, "%d x f32" % (B // 4) if is_float else "%d-byte" % B))
         return q
 
     def select_objects(self, ids):
         """Search only the rows of the listed objects (indices of the last db_load, any order, repeats allowed) from now on; None:
         all objects again, []: nothing. imgIdx and the sharded keys keep the numbering of the full DB (todhip_db_select_objects)."""
         p, n, keep = _ids_in(ids)
-        _check(lib().todhip_db_select_objects(self._h, p, C.c_uint32(n)), "todhip_db_select_objects")
+        _call("todhip_db_select_objects", self._h, p, n)
 
     def selection(self):
         """dict(n_objs, rows, shard_rows): the distinct selected objects, their rows in the whole DB and in this context's shard"""
         n, rows, srows = C.c_uint32(), C.c_uint64(), C.c_uint64()
-        _check(lib().todhip_db_selection(self._h, C.byref(n), C.byref(rows), C.byref(srows)), "todhip_db_selection")
+        _call("todhip_db_selection", self._h, C.byref(n), C.byref(rows), C.byref(srows))
         return dict(n_objs=n.value, rows=rows.value, shard_rows=srows.value)
 
-    def _match_host(self, fn, what, q, k, radius):
+    def _match_host(self, name, q, k, radius):
         nq = q.shape[0]
         row_ptr = np.zeros(nq + 1, np.uint32)
         m = np.zeros(max(nq * k, 1), DMATCH_DTYPE)
         xyz = np.zeros((max(nq * k, 1), 3), np.float32)
-        _check(fn(self._h, _np_ptr(q), C.c_uint32(nq), C.c_uint32(k), radius, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz)), what)
+        _call(name, self._h, _np_ptr(q), nq, k, radius, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz))
         n = int(row_ptr[nq])
         return row_ptr, m[:n].copy(), xyz[:n].copy()
 
@@ -456,7 +392,7 @@ class Context:
         """Host-buffer form: q_desc u8[nq, 32] or u8[nq, 64] -- the query width must equal the DB's (desc_bytes(); TodError(EINVAL)
         otherwise). On a 64-byte DB distances run 0 ... 512 and a radius >= 512 cuts nothing.
         Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3])."""
-        return self._match_host(lib().todhip_match, "todhip_match", self._query_rows(q_desc, "todhip_match"), k, C.c_uint32(radius))
+        return self._match_host("todhip_match", self._query_rows(q_desc, np.uint8, "todhip_match"), k, radius)
 
     def match_radius(self, q_desc, radius, max_per_query):
         """The true radius search, host-buffer form (todhip_match_radius): every searched row within `radius` bits, the nearest
@@ -467,46 +403,50 @@ class Context:
         row_ptr, in_radius = np.zeros(nq + 1, np.uint32), np.zeros(nq, np.uint32)
         m, xyz = np.empty(cap, DMATCH_DTYPE), np.empty((cap, 3), np.float32)
         n = C.c_uint32(cap)
-        _check(lib().todhip_match_radius(self._h, _np_ptr(q), nq, radius, max_per_query, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz),
-                                         C.addressof(n), _np_ptr(in_radius)), "todhip_match_radius")
+        _call("todhip_match_radius", self._h, _np_ptr(q), nq, radius, max_per_query, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz),
+              C.byref(n), _np_ptr(in_radius))
         return row_ptr, m[:n.value].copy(), xyz[:n.value].copy(), in_radius
 
     def match_radius_device(self, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
         """Device-pointer form (ints from tensor.data_ptr()), fixed stride max_per_query; d_in_radius may be None."""
-        _check(lib().todhip_match_radius_device(self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius),
-               "todhip_match_radius_device")
+        _call("todhip_match_radius_device", self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius)
 
     def match_radius_shard_device(self, d_q, nq, radius, max_per_query, d_keys):
         """The sharded radius search, step 1: this context's shard -> d_keys u64[nq, max_per_query + 1] (ascending keys
         distance << 32 | row of the full DB, UINT64_MAX padding, the shard's exact count in the last slot; every slot written)."""
-        _check(lib().todhip_match_radius_shard_device(self._h, d_q, nq, radius, max_per_query, d_keys), "todhip_match_radius_shard_device")
+        _call("todhip_match_radius_shard_device", self._h, d_q, nq, radius, max_per_query, d_keys)
 
-    def merge_radius_shards_device(self, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
-        """Step 2: d_keys_all u64[n_shards, nq, max_per_query + 1] -> what match_radius_device leaves on the unsharded DB."""
-        _check(lib().todhip_merge_radius_shards_device(self._h, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz,
-                                                       d_in_radius), "todhip_merge_radius_shards_device")
+    def _merge(self, name, stream, *args):
+        """A merge of shard keys on the context's stream, or (its _on form) on a HIP stream of the caller's: the merges only read the
+        context's immutable tables"""
+        if stream is None:
+            _call(name, self._h, *args)
+        else:
+            _call(name + "_on", self._h, stream, *args)
+
+    def merge_radius_shards_device(self, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None, stream=None):
+        """Step 2: d_keys_all u64[n_shards, nq, max_per_query + 1] -> what match_radius_device leaves on the unsharded DB.
+        stream: as merge_shards_device."""
+        self._merge("todhip_merge_radius_shards_device", stream, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius)
 
     def merge_radius_shards_device_on(self, stream, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
         """The same merge on a stream of the caller's (it only reads the context's immutable tables)."""
-        _check(lib().todhip_merge_radius_shards_device_on(self._h, stream, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches,
-                                                          d_xyz, d_in_radius), "todhip_merge_radius_shards_device_on")
+        self.merge_radius_shards_device(d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius, stream=stream)
 
     def match_l2(self, q_desc, k, radius):
         """Float descriptors, host-buffer form. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3]). q_desc f32[nq, 64] or
         f32[nq, 128]: the query width must equal the DB's (desc_bytes() / 4; TodError(EINVAL) otherwise)."""
-        return self._match_host(lib().todhip_match_l2, "todhip_match_l2", self._query_rows_l2(q_desc, "todhip_match_l2"), k, C.c_float(radius))
+        return self._match_host("todhip_match_l2", self._query_rows(q_desc, np.float32, "todhip_match_l2"), k, radius)
 
     def match_l2_device(self, d_q, nq, k, radius, d_counts, d_matches, d_xyz):
-        rc = lib().todhip_match_l2_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_float(radius),
-                                          C.c_void_p(d_counts), C.c_void_p(d_matches), C.c_void_p(d_xyz))
-        _check(rc, "todhip_match_l2_device")
+        _call("todhip_match_l2_device", self._h, d_q, nq, k, radius, d_counts, d_matches, d_xyz)
 
     def match_l2_radius(self, q_desc, radius, max_per_query):
         """The true L2 radius search over a float DB, host-buffer form (todhip_match_l2_radius): every row whose distance is not
         > radius, the nearest max_per_query of them per query. Returns (row_ptr u32[nq+1], matches DMATCH[n], xyz f32[n,3],
         in_radius u32[nq]). The output buffers start at 16 matches per query and grow to the count the library asks for. The query
         width must equal the DB's, as in match_l2."""
-        q = self._query_rows_l2(q_desc, "todhip_match_l2_radius")
+        q = self._query_rows(q_desc, np.float32, "todhip_match_l2_radius")
         nq = q.shape[0]
         row_ptr, in_radius = np.zeros(nq + 1, np.uint32), np.zeros(nq, np.uint32)
         cap = max(nq * min(max_per_query, 16), 1)
@@ -514,78 +454,62 @@ class Context:
             m, xyz = np.empty(cap, DMATCH_DTYPE), np.empty((cap, 3), np.float32)
             n = C.c_uint32(cap)
             rc = lib().todhip_match_l2_radius(self._h, _np_ptr(q), nq, radius, max_per_query, _np_ptr(row_ptr), _np_ptr(m), _np_ptr(xyz),
-                                              C.addressof(n), _np_ptr(in_radius))
+                                              C.byref(n), _np_ptr(in_radius))
             if rc != ECAPACITY or n.value <= cap:
                 break
             cap = n.value                                                 # the needed count: the same call fits now
-        _check(rc, "todhip_match_l2_radius")
+        if rc != OK:
+            raise TodError(rc, "todhip_match_l2_radius")
         return row_ptr, m[:n.value].copy(), xyz[:n.value].copy(), in_radius
 
     def match_l2_radius_device(self, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None):
         """Device-pointer form (ints from tensor.data_ptr()), fixed stride max_per_query; d_in_radius may be None."""
-        _check(lib().todhip_match_l2_radius_device(self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius),
-               "todhip_match_l2_radius_device")
+        _call("todhip_match_l2_radius_device", self._h, d_q, nq, radius, max_per_query, d_counts, d_matches, d_xyz, d_in_radius)
 
     def match_l2_shard_device(self, d_q, nq, k, d_keys):
         """The sharded float k-NN search, step 1: this context's shard -> d_keys u64[nq, k] (ascending keys
         binary32 bits of d2 << 32 | row of the full DB, UINT64_MAX padding; the plain top-k, every slot written)."""
-        _check(lib().todhip_match_l2_shard_device(self._h, d_q, nq, k, d_keys), "todhip_match_l2_shard_device")
+        _call("todhip_match_l2_shard_device", self._h, d_q, nq, k, d_keys)
 
     def merge_l2_shards_device(self, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz, stream=None):
-        """Step 2: d_keys_all u64[n_shards, nq, k] -> what match_l2_device leaves on the unsharded DB. stream: a HIP stream of the
-        caller's instead of the context's (the merge only reads the context's immutable tables)."""
-        if stream is None:
-            _check(lib().todhip_merge_l2_shards_device(self._h, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz),
-                   "todhip_merge_l2_shards_device")
-        else:
-            _check(lib().todhip_merge_l2_shards_device_on(self._h, stream, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz),
-                   "todhip_merge_l2_shards_device_on")
+        """Step 2: d_keys_all u64[n_shards, nq, k] -> what match_l2_device leaves on the unsharded DB. stream: as merge_shards_device."""
+        self._merge("todhip_merge_l2_shards_device", stream, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz)
 
     def match_l2_radius_shard_device(self, d_q, nq, radius, max_per_query, d_keys):
         """The sharded float radius search, step 1: this context's shard -> d_keys u64[nq, max_per_query + 1] (ascending keys,
         UINT64_MAX padding, the shard's exact count in the last slot; every slot written)."""
-        _check(lib().todhip_match_l2_radius_shard_device(self._h, d_q, nq, radius, max_per_query, d_keys),
-               "todhip_match_l2_radius_shard_device")
+        _call("todhip_match_l2_radius_shard_device", self._h, d_q, nq, radius, max_per_query, d_keys)
 
     def merge_l2_radius_shards_device(self, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz, d_in_radius=None,
                                       stream=None):
         """Step 2: d_keys_all u64[n_shards, nq, max_per_query + 1] -> what match_l2_radius_device leaves on the unsharded DB.
-        stream: as merge_l2_shards_device."""
-        if stream is None:
-            _check(lib().todhip_merge_l2_radius_shards_device(self._h, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz,
-                                                              d_in_radius), "todhip_merge_l2_radius_shards_device")
-        else:
-            _check(lib().todhip_merge_l2_radius_shards_device_on(self._h, stream, d_keys_all, n_shards, nq, max_per_query, d_counts,
-                                                                 d_matches, d_xyz, d_in_radius), "todhip_merge_l2_radius_shards_device_on")
+        stream: as merge_shards_device."""
+        self._merge("todhip_merge_l2_radius_shards_device", stream, d_keys_all, n_shards, nq, max_per_query, d_counts, d_matches, d_xyz,
+                    d_in_radius)
 
     def match_device(self, d_q, nq, k, radius, d_counts, d_matches, d_xyz):
         """Device-pointer form (ints from tensor.data_ptr()). d_q: nq rows of the DB's width, 32 or 64 bytes (desc_bytes()) -- the
         query width must equal the DB's, and a pointer carries no shape: the caller answers for it."""
-        rc = lib().todhip_match_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius),
-                                       C.c_void_p(d_counts), C.c_void_p(d_matches), C.c_void_p(d_xyz))
-        _check(rc, "todhip_match_device")
+        _call("todhip_match_device", self._h, d_q, nq, k, radius, d_counts, d_matches, d_xyz)
 
     def cross_check_device(self, d_q, nq, frame_queries, stride, d_counts, d_matches, d_xyz, frame_nq=None):
         """The cross-check filter in place on a fixed-stride device output (todhip_cross_check_device): a match stays only where its
         query is the nearest valid query of its frame (frame_queries rows each) to the DB row it names, ties to the lower query
         index. frame_nq: per frame, how many of its first rows compete (None: all). Asynchronous on the context's stream."""
-        fn = None if frame_nq is None else np.ascontiguousarray(frame_nq, np.uint32)
-        if fn is not None and len(fn) != (nq + frame_queries - 1) // max(frame_queries, 1):
-            raise TodError(EINVAL, "todhip_cross_check_device (frame_nq of %d entries for %d queries in frames of %d)" % (len(fn), nq, frame_queries))
-        _check(lib().todhip_cross_check_device(self._h, d_q, nq, frame_queries, None if fn is None else _np_ptr(fn), stride, d_counts,
-                                               d_matches, d_xyz), "todhip_cross_check_device")
+        fn = _frame_limits(frame_nq, nq, frame_queries, "todhip_cross_check_device")
+        _call("todhip_cross_check_device", self._h, d_q, nq, frame_queries, _np_ptr(fn), stride, d_counts, d_matches, d_xyz)
 
     def set_cross_check(self, frame_queries):
         """match() and match_device() run the cross-check behind their finalize step, in frames of frame_queries query rows (0 = off,
         the default). The sharded and radius forms ignore it: filter their outputs with cross_check_device."""
-        _check(lib().todhip_set_cross_check(self._h, frame_queries), "todhip_set_cross_check")
+        _call("todhip_set_cross_check", self._h, frame_queries)
 
     def set_l2_ratio_test(self, ratio):
         """Lowe's ratio test of the float forms (todhip_set_l2_ratio_test; 0 = off, the default; 0 < ratio <= 1 = on): match_l2,
         match_l2_device and merge_l2_shards_device drop every match of a query whose two nearest rows over the whole DB do not
         satisfy sqrtf(d2_1) < ratio * sqrtf(d2_2) in binary32. k == 1 searches two rows and returns one; match_l2_shard_device and
         the merge refuse k < 2 while it is on. The radius forms ignore it. set_ratio_test does not apply to the float forms."""
-        _check(lib().todhip_set_l2_ratio_test(self._h, C.c_float(ratio)), "todhip_set_l2_ratio_test")
+        _call("todhip_set_l2_ratio_test", self._h, ratio)
 
     def cross_check_l2_device(self, d_q, nq, frame_queries, stride, d_counts, d_matches, d_xyz, frame_nq=None):
         """The cross-check filter over a float DB, in place on a fixed-stride device output of match_l2_device,
@@ -599,167 +523,104 @@ class Context:
             if B in (256, 512) and (len(d_q.shape) != 2 or d_q.shape[1] * 4 != B or d_q.shape[0] < nq):
                 raise TodError(EINVAL, "todhip_cross_check_l2_device (queries of shape %s against a DB of %d x f32 descriptors)" % (tuple(d_q.shape), B // 4))
             d_q = d_q.data_ptr()
-        fn = None if frame_nq is None else np.ascontiguousarray(frame_nq, np.uint32)
-        if fn is not None and len(fn) != (nq + frame_queries - 1) // max(frame_queries, 1):
-            raise TodError(EINVAL, "todhip_cross_check_l2_device (frame_nq of %d entries for %d queries in frames of %d)" % (len(fn), nq, frame_queries))
-        _check(lib().todhip_cross_check_l2_device(self._h, d_q, nq, frame_queries, None if fn is None else _np_ptr(fn), stride, d_counts,
-                                                  d_matches, d_xyz), "todhip_cross_check_l2_device")
+        fn = _frame_limits(frame_nq, nq, frame_queries, "todhip_cross_check_l2_device")
+        _call("todhip_cross_check_l2_device", self._h, d_q, nq, frame_queries, _np_ptr(fn), stride, d_counts, d_matches, d_xyz)
 
     def set_l2_cross_check(self, frame_queries):
         """match_l2() and match_l2_device() run the float cross-check behind their finalize step -- behind the ratio test and the
         radius cut -- in frames of frame_queries query rows (0 = off, the default). The shard, merge and radius forms ignore it:
         filter their outputs with cross_check_l2_device. set_cross_check does not apply to the float forms."""
-        _check(lib().todhip_set_l2_cross_check(self._h, frame_queries), "todhip_set_l2_cross_check")
+        _call("todhip_set_l2_cross_check", self._h, frame_queries)
 
     def match_shard_device(self, d_q, nq, k, radius, d_keys):
-        rc = lib().todhip_match_shard_device(self._h, C.c_void_p(d_q), C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius),
-                                             C.c_void_p(d_keys))
-        _check(rc, "todhip_match_shard_device")
+        _call("todhip_match_shard_device", self._h, d_q, nq, k, radius, d_keys)
 
-    def merge_shards_device(self, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz):
-        rc = lib().todhip_merge_shards_device(self._h, C.c_void_p(d_keys_all), C.c_uint32(n_shards), C.c_uint32(nq),
-                                              C.c_uint32(k), C.c_uint32(radius), C.c_void_p(d_counts),
-                                              C.c_void_p(d_matches), C.c_void_p(d_xyz))
-        _check(rc, "todhip_merge_shards_device")
+    def merge_shards_device(self, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz, stream=None):
+        """stream: a HIP stream of the caller's instead of the context's (the merge only reads the context's immutable tables)."""
+        self._merge("todhip_merge_shards_device", stream, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz)
 
     def merge_shards_device_on(self, stream, d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz):
         """The merge on a stream of the caller's (it only reads the context's immutable tables)."""
-        rc = lib().todhip_merge_shards_device_on(self._h, C.c_void_p(stream), C.c_void_p(d_keys_all), C.c_uint32(n_shards),
-                                                 C.c_uint32(nq), C.c_uint32(k), C.c_uint32(radius), C.c_void_p(d_counts),
-                                                 C.c_void_p(d_matches), C.c_void_p(d_xyz))
-        _check(rc, "todhip_merge_shards_device_on")
+        self.merge_shards_device(d_keys_all, n_shards, nq, k, radius, d_counts, d_matches, d_xyz, stream=stream)
 
     # ---------------------------------------------------------------- stage C
+    def _verify(self, name, front, n_kp, spans, min_inliers, n_iter, err, rng, max_poses, n_frames=None, cache=False):
+        """Every verify* call: `front` are the function's arguments between the context and spans, n_kp the keypoints of a frame. The
+        numpy arrays in `front` go over as their pointers (`ptrs`); the parameter `front` stays bound to the tuple until this
+        function returns, and the tuple holds the arrays, so a temporary such as _k9(K) in a caller's tuple lives through the call.
+        n_frames None: one frame, rng one Rng, -> list of pose dicts. n_frames given: the batch form, rng a ctypes array
+        Rng * n_frames, -> that list per frame. cache: keep the inlier array in the context between calls."""
+        ptrs = [_np_ptr(a) if isinstance(a, np.ndarray) else a for a in front]
+        sp, prm = np.ascontiguousarray(spans, np.float32), VerifyParams(min_inliers, n_iter, err)
+        poses, n_poses, inl, n_inl, pose_ptr = _pose_out(max_poses, n_kp, n_frames, self if cache else None)
+        if n_frames is None:
+            _call(name, self._h, *ptrs, _np_ptr(sp), len(sp), C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
+            return _pose_list(poses, 0, n_poses.value, inl)
+        _call(name, self._h, *ptrs, _np_ptr(sp), len(sp), C.byref(prm), rng, poses, C.byref(n_poses), pose_ptr, _np_ptr(inl), C.byref(n_inl))
+        return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
+
     def verify(self, kp_xy, cloud, row_ptr, matches, matches_xyz, spans, min_inliers, n_iter, err, rng,
                max_poses=64):
         kp = np.ascontiguousarray(kp_xy, np.float32)
         cloud = np.ascontiguousarray(cloud, np.float32)
         H, W = (cloud.shape[0], cloud.shape[1]) if cloud.ndim == 3 else (0, 0)
-        row_ptr = np.ascontiguousarray(row_ptr, np.uint32)
-        matches = np.ascontiguousarray(matches, DMATCH_DTYPE)
-        mxyz = np.ascontiguousarray(matches_xyz, np.float32)
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
-        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, len(kp))
-        rc = lib().todhip_verify(self._h, _np_ptr(kp), C.c_uint32(len(kp)), _np_ptr(cloud), C.c_uint32(H),
-                                 C.c_uint32(W), _np_ptr(row_ptr), _np_ptr(matches), _np_ptr(mxyz), _np_ptr(sp), C.c_uint32(len(sp)),
-                                 C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
-        _check(rc, "todhip_verify")
-        return _pose_list(poses, 0, n_poses.value, inl)
+        front = (kp, len(kp), cloud, H, W, np.ascontiguousarray(row_ptr, np.uint32), np.ascontiguousarray(matches, DMATCH_DTYPE),
+                 np.ascontiguousarray(matches_xyz, np.float32))
+        return self._verify("todhip_verify", front, len(kp), spans, min_inliers, n_iter, err, rng, max_poses)
 
     def verify_2d(self, kp_xy, K, row_ptr, matches, matches_xyz, spans, min_inliers, n_iter, err_px, rng, max_poses=64):
         """The 2D-only branch (no cloud): todhip_verify_2d. err_px: reprojection threshold in pixels."""
         kp = np.ascontiguousarray(kp_xy, np.float32)
-        row_ptr = np.ascontiguousarray(row_ptr, np.uint32)
-        matches = np.ascontiguousarray(matches, DMATCH_DTYPE)
-        mxyz = np.ascontiguousarray(matches_xyz, np.float32)
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err_px)
-        K9 = _k9(K)
-        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, len(kp))
-        rc = lib().todhip_verify_2d(self._h, _np_ptr(kp), C.c_uint32(len(kp)), _np_ptr(K9), _np_ptr(row_ptr),
-                                    matches.ctypes.data_as(C.c_void_p), _np_ptr(mxyz), _np_ptr(sp), C.c_uint32(len(sp)),
-                                    C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
-        _check(rc, "todhip_verify_2d")
-        return _pose_list(poses, 0, n_poses.value, inl)
+        front = (kp, len(kp), _k9(K), np.ascontiguousarray(row_ptr, np.uint32), np.ascontiguousarray(matches, DMATCH_DTYPE),
+                 np.ascontiguousarray(matches_xyz, np.float32))
+        return self._verify("todhip_verify_2d", front, len(kp), spans, min_inliers, n_iter, err_px, rng, max_poses)
 
     def verify_2d_device(self, d_kp_xy, nq, K, d_counts, d_matches, d_xyz, k, spans, min_inliers, n_iter, err_px, rng, max_poses=64):
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err_px)
-        K9 = _k9(K)
-        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq)
-        rc = lib().todhip_verify_2d_device(self._h, C.c_void_p(d_kp_xy), C.c_uint32(nq), _np_ptr(K9), C.c_void_p(d_counts),
-                                           C.c_void_p(d_matches), C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp), C.c_uint32(len(sp)),
-                                           C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
-        _check(rc, "todhip_verify_2d_device")
-        return _pose_list(poses, 0, n_poses.value, inl)
+        return self._verify("todhip_verify_2d_device", (d_kp_xy, nq, _k9(K), d_counts, d_matches, d_xyz, k), nq, spans, min_inliers, n_iter,
+                            err_px, rng, max_poses)
 
     def verify_2d_batch_device(self, n_frames, d_kp_xy, nq, K, d_counts, d_matches, d_xyz, k, spans, min_inliers, n_iter, err_px, rngs,
                                max_poses=16):
         """rngs: ctypes array (Rng * n_frames). Returns a list (per frame) of lists of pose dicts."""
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err_px)
-        K9 = _k9(K)
-        poses, n_poses, inl, n_inl, pose_ptr = _pose_out(max_poses, nq, n_frames)
-        rc = lib().todhip_verify_2d_batch_device(self._h, C.c_uint32(n_frames), C.c_void_p(d_kp_xy), C.c_uint32(nq), _np_ptr(K9),
-                                                 C.c_void_p(d_counts), C.c_void_p(d_matches), C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp),
-                                                 C.c_uint32(len(sp)), C.byref(prm), rngs, poses, C.byref(n_poses), pose_ptr, _np_ptr(inl),
-                                                 C.byref(n_inl))
-        _check(rc, "todhip_verify_2d_batch_device")
-        return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
+        return self._verify("todhip_verify_2d_batch_device", (n_frames, d_kp_xy, nq, _k9(K), d_counts, d_matches, d_xyz, k), nq, spans,
+                            min_inliers, n_iter, err_px, rngs, max_poses, n_frames)
 
     def verify_device(self, d_kp_xy, nq, d_cloud, H, W, d_counts, d_matches, d_xyz, k, spans, min_inliers, n_iter,
                       err, rng, max_poses=64):
         """Device-pointer form (ints from tensor.data_ptr()); poses are returned on the host."""
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
-        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq, cache=self)
-        rc = lib().todhip_verify_device(self._h, C.c_void_p(d_kp_xy), C.c_uint32(nq), C.c_void_p(d_cloud),
-                                        C.c_uint32(H), C.c_uint32(W), C.c_void_p(d_counts), C.c_void_p(d_matches),
-                                        C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp), C.c_uint32(len(sp)),
-                                        C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl),
-                                        C.byref(n_inl))
-        _check(rc, "todhip_verify_device")
-        return _pose_list(poses, 0, n_poses.value, inl)
+        return self._verify("todhip_verify_device", (d_kp_xy, nq, d_cloud, H, W, d_counts, d_matches, d_xyz, k), nq, spans, min_inliers,
+                            n_iter, err, rng, max_poses, cache=True)
 
     def verify_device_depth(self, d_kp_xy, nq, d_depth, depth_is_u16, H, W, K, d_counts, d_matches, d_xyz, k, spans,
                             min_inliers, n_iter, err, rng, max_poses=64):
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
-        K9 = _k9(K)
-        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq)
-        rc = lib().todhip_verify_device_depth(self._h, C.c_void_p(d_kp_xy), C.c_uint32(nq), C.c_void_p(d_depth),
-                                              C.c_int(1 if depth_is_u16 else 0), C.c_uint32(H), C.c_uint32(W),
-                                              _np_ptr(K9), C.c_void_p(d_counts), C.c_void_p(d_matches),
-                                              C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp), C.c_uint32(len(sp)),
-                                              C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl),
-                                              C.byref(n_inl))
-        _check(rc, "todhip_verify_device_depth")
-        return _pose_list(poses, 0, n_poses.value, inl)
+        return self._verify("todhip_verify_device_depth", (d_kp_xy, nq, d_depth, 1 if depth_is_u16 else 0, H, W, _k9(K), d_counts, d_matches,
+                                                           d_xyz, k), nq, spans, min_inliers, n_iter, err, rng, max_poses)
 
     def verify_batch_device(self, n_frames, d_kp_xy, nq, d_cloud, H, W, d_counts, d_matches, d_xyz, k, spans, min_inliers,
                             n_iter, err, rngs, max_poses=16, depth=None):
         """rngs: ctypes array (Rng * n_frames). depth = (d_depth, is_u16, K) selects the depth form (d_cloud ignored).
         Returns a list (per frame) of lists of pose dicts."""
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
-        poses, n_poses, inl, n_inl, pose_ptr = _pose_out(max_poses, nq, n_frames, cache=self)
         if depth is None:
-            rc = lib().todhip_verify_batch_device(self._h, C.c_uint32(n_frames), C.c_void_p(d_kp_xy), C.c_uint32(nq),
-                                                  C.c_void_p(d_cloud), C.c_uint32(H), C.c_uint32(W), C.c_void_p(d_counts),
-                                                  C.c_void_p(d_matches), C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp),
-                                                  C.c_uint32(len(sp)), C.byref(prm), rngs, poses, C.byref(n_poses), pose_ptr,
-                                                  _np_ptr(inl), C.byref(n_inl))
+            name, image = "todhip_verify_batch_device", (d_cloud, H, W)
         else:
-            d_depth, is_u16, K = depth
-            K9 = _k9(K)
-            rc = lib().todhip_verify_batch_device_depth(self._h, C.c_uint32(n_frames), C.c_void_p(d_kp_xy), C.c_uint32(nq),
-                                                        C.c_void_p(d_depth), C.c_int(1 if is_u16 else 0), C.c_uint32(H),
-                                                        C.c_uint32(W), _np_ptr(K9), C.c_void_p(d_counts), C.c_void_p(d_matches),
-                                                        C.c_void_p(d_xyz), C.c_uint32(k), _np_ptr(sp), C.c_uint32(len(sp)),
-                                                        C.byref(prm), rngs, poses, C.byref(n_poses), pose_ptr, _np_ptr(inl),
-                                                        C.byref(n_inl))
-        _check(rc, "todhip_verify_batch_device")
-        return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
+            name, image = "todhip_verify_batch_device_depth", (depth[0], 1 if depth[1] else 0, H, W, _k9(depth[2]))
+        return self._verify(name, (n_frames, d_kp_xy, nq) + image + (d_counts, d_matches, d_xyz, k), nq, spans, min_inliers, n_iter, err,
+                            rngs, max_poses, n_frames, cache=True)
 
     def verify_device_depth_rescaled(self, d_kp_xy, nq, d_depth, depth_is_u16, dH, dW, nearest, H, W, K, d_counts, d_matches, d_xyz, k,
                                      spans, min_inliers, n_iter, err, rng, max_poses=64):
         """verify_device_depth on a dH x dW depth image: the result of rescale_depth_device followed by verify_device_depth, without
         the H x W intermediate (H, W, K: the image's)."""
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
-        K9 = _k9(K)
-        poses, n_poses, inl, n_inl, _ = _pose_out(max_poses, nq)
-        rc = lib().todhip_verify_device_depth_rescaled(self._h, d_kp_xy, nq, d_depth, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0,
-                                                       H, W, _np_ptr(K9), d_counts, d_matches, d_xyz, k, _np_ptr(sp), len(sp),
-                                                       C.byref(prm), C.byref(rng), poses, C.byref(n_poses), _np_ptr(inl), C.byref(n_inl))
-        _check(rc, "todhip_verify_device_depth_rescaled")
-        return _pose_list(poses, 0, n_poses.value, inl)
+        front = (d_kp_xy, nq, d_depth, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0, H, W, _k9(K), d_counts, d_matches, d_xyz, k)
+        return self._verify("todhip_verify_device_depth_rescaled", front, nq, spans, min_inliers, n_iter, err, rng, max_poses)
 
     def verify_batch_device_depth_rescaled(self, n_frames, d_kp_xy, nq, d_depth, depth_is_u16, dH, dW, nearest, H, W, K, d_counts,
                                            d_matches, d_xyz, k, spans, min_inliers, n_iter, err, rngs, max_poses=16):
         """The batch form (d_depth: n_frames x dH x dW, rngs: ctypes array Rng * n_frames); a list per frame of lists of pose dicts."""
-        sp, prm = _verify_in(spans, min_inliers, n_iter, err)
-        K9 = _k9(K)
-        poses, n_poses, inl, n_inl, pose_ptr = _pose_out(max_poses, nq, n_frames, cache=self)
-        rc = lib().todhip_verify_batch_device_depth_rescaled(self._h, n_frames, d_kp_xy, nq, d_depth, 1 if depth_is_u16 else 0, dH, dW,
-                                                             1 if nearest else 0, H, W, _np_ptr(K9), d_counts, d_matches, d_xyz, k,
-                                                             _np_ptr(sp), len(sp), C.byref(prm), rngs, poses, C.byref(n_poses), pose_ptr,
-                                                             _np_ptr(inl), C.byref(n_inl))
-        _check(rc, "todhip_verify_batch_device_depth_rescaled")
-        return [_pose_list(poses, pose_ptr[f], pose_ptr[f + 1], inl) for f in range(n_frames)]
+        front = (n_frames, d_kp_xy, nq, d_depth, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0, H, W, _k9(K), d_counts, d_matches,
+                 d_xyz, k)
+        return self._verify("todhip_verify_batch_device_depth_rescaled", front, nq, spans, min_inliers, n_iter, err, rngs, max_poses,
+                            n_frames, cache=True)
 
     def test_depth_lookup(self, d_depth, depth_is_u16, dH, dW, nearest, H, W, kp_xy, fill=0.0):
         """z (f32 [n]) of the verifier's depth lookup at the pixel positions kp_xy [n, 2]. Returns (status, z): OK, or ERANGE when a
@@ -775,7 +636,7 @@ class Context:
     def verify_trace(self, cap=4096):
         arr = (RoundTrace * cap)()
         n = C.c_uint32(cap)
-        _check(lib().todhip_verify_trace(self._h, arr, C.byref(n)), "todhip_verify_trace")
+        _call("todhip_verify_trace", self._h, arr, C.byref(n))
         return [arr[i] for i in range(n.value)]
 
     def test_adjacency(self, train, query, kp_per_match, span, err):
@@ -786,9 +647,7 @@ class Context:
         W = (n + 63) // 64
         phys = np.zeros((n, W), np.uint64)
         samp = np.zeros((n, W), np.uint64)
-        rc = lib().todhip_test_adjacency(self._h, _np_ptr(t), _np_ptr(q), _np_ptr(kp), C.c_uint32(n), C.c_float(span),
-                                         C.c_float(err), _np_ptr(phys), _np_ptr(samp))
-        _check(rc, "todhip_test_adjacency")
+        _call("todhip_test_adjacency", self._h, _np_ptr(t), _np_ptr(q), _np_ptr(kp), n, span, err, _np_ptr(phys), _np_ptr(samp))
         return phys, samp
 
     def test_consensus(self, train, query, kp_per_match, span, err, triples, stop_level=0, dbg_stride=0):
@@ -798,11 +657,8 @@ class Context:
         tr = np.ascontiguousarray(triples, np.uint32).reshape(-1, 3)
         counts = np.zeros(len(tr), np.int32)
         dbg = np.zeros((len(tr), dbg_stride), np.uint32) if dbg_stride else None
-        rc = lib().todhip_test_consensus(self._h, _np_ptr(t), _np_ptr(q), _np_ptr(kp), C.c_uint32(len(t)),
-                                         C.c_float(span), C.c_float(err), _np_ptr(tr), C.c_uint32(len(tr)),
-                                         C.c_uint32(stop_level), _np_ptr(counts),
-                                         None if dbg is None else _np_ptr(dbg), C.c_uint32(dbg_stride))
-        _check(rc, "todhip_test_consensus")
+        _call("todhip_test_consensus", self._h, _np_ptr(t), _np_ptr(q), _np_ptr(kp), len(t), span, err, _np_ptr(tr), len(tr), stop_level,
+              _np_ptr(counts), _np_ptr(dbg), dbg_stride)
         return counts, dbg
 
     def test_draw_table(self, samp, valid, n, rnd, S, form=0):
@@ -827,15 +683,13 @@ class Context:
         assert len(Hd) == len(Cc)
         R = np.zeros((len(Hd), 9), np.float32)
         T = np.zeros((len(Hd), 3), np.float32)
-        _check(lib().todhip_test_kabsch(self._h, len(Hd), _np_ptr(Hd), _np_ptr(Cc), _np_ptr(R), _np_ptr(T)), "todhip_test_kabsch")
+        _call("todhip_test_kabsch", self._h, len(Hd), _np_ptr(Hd), _np_ptr(Cc), _np_ptr(R), _np_ptr(T))
         return R.reshape(-1, 3, 3), T
 
     def test_clique(self, m, edges, minimal_size=0xFFFFFFFF, gate=False):
         e = np.ascontiguousarray(np.asarray(edges, np.uint32).reshape(-1, 2))
         out = np.zeros(3, np.uint32)
-        fn = lib().todhip_test_clique_gate if gate else lib().todhip_test_clique
-        rc = fn(self._h, C.c_uint32(m), _np_ptr(e), C.c_uint32(len(e)), C.c_uint32(minimal_size), _np_ptr(out))
-        _check(rc, "todhip_test_clique")
+        _call("todhip_test_clique_gate" if gate else "todhip_test_clique", self._h, m, _np_ptr(e), len(e), minimal_size, _np_ptr(out))
         return int(out[0]), int(out[1]), int(out[2])
 
     # ---------------------------------------------------------------- stage A
@@ -845,7 +699,7 @@ class Context:
         the last row's W pixels is what the library gets."""
         if stride is None:
             g = np.ascontiguousarray(gray, np.uint8)
-            mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+            mk = _opt(mask, np.uint8)
             H, W = g.shape
             stride = W
         else:
@@ -856,46 +710,34 @@ class Context:
         aux = np.zeros((max(cap, 1), 4), np.float32)
         desc = np.zeros((max(cap, 1), 32), np.uint8)
         n_out = C.c_uint32(cap)
-        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
-        rc = lib().todhip_orb_masked(self._h, _np_ptr(g), None if mk is None else _np_ptr(mk), C.c_uint32(H), C.c_uint32(W),
-                                     C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor),
-                                     None if pat is None else _np_ptr(pat), _np_ptr(kp), _np_ptr(aux), _np_ptr(desc),
-                                     C.byref(n_out))
-        _check(rc, "todhip_orb_masked")
+        pat = _opt(pattern, np.int8)
+        _call("todhip_orb_masked", self._h, _np_ptr(g), _np_ptr(mk), H, W, stride, n_features, n_levels, scale_factor, _np_ptr(pat),
+              _np_ptr(kp), _np_ptr(aux), _np_ptr(desc), C.byref(n_out))
         n = n_out.value
         return kp[:n].copy(), aux[:n].copy(), desc[:n].copy()
 
     def orb_device(self, d_gray, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux, d_desc, cap, pattern=None):
         n_out = C.c_uint32(cap)
-        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
-        rc = lib().todhip_orb_device(self._h, C.c_void_p(d_gray), C.c_uint32(H), C.c_uint32(W), C.c_uint32(stride),
-                                     C.c_uint32(n_features), C.c_uint32(n_levels), C.c_float(scale_factor),
-                                     None if pat is None else _np_ptr(pat),
-                                     C.c_void_p(d_kp_xy), C.c_void_p(d_kp_aux), C.c_void_p(d_desc), C.byref(n_out))
-        _check(rc, "todhip_orb_device")
+        pat = _opt(pattern, np.int8)
+        _call("todhip_orb_device", self._h, d_gray, H, W, stride, n_features, n_levels, scale_factor, _np_ptr(pat), d_kp_xy, d_kp_aux,
+              d_desc, C.byref(n_out))
         return n_out.value
 
     def orb_batch_device(self, d_gray, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy, d_kp_aux,
                          d_desc, cap, pattern=None):
         n = (C.c_uint32 * n_frames)()
-        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
-        rc = lib().todhip_orb_batch_device(self._h, C.c_void_p(d_gray), C.c_uint32(n_frames), C.c_uint64(frame_stride), C.c_uint32(H),
-                                           C.c_uint32(W), C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels),
-                                           C.c_float(scale_factor), None if pat is None else _np_ptr(pat), C.c_void_p(d_kp_xy),
-                                           C.c_void_p(d_kp_aux),
-                                           C.c_void_p(d_desc), C.c_uint32(cap), n)
-        _check(rc, "todhip_orb_batch_device")
+        pat = _opt(pattern, np.int8)
+        _call("todhip_orb_batch_device", self._h, d_gray, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor,
+              _np_ptr(pat), d_kp_xy, d_kp_aux, d_desc, cap, n)
         return list(n)
 
     def orb_batch_device_masked(self, d_gray, d_mask, n_frames, frame_stride, H, W, stride, n_features, n_levels, scale_factor, d_kp_xy,
                                 d_kp_aux, d_desc, cap, pattern=None):
         """orb_batch_device with a packed mask per frame (d_mask: n_frames x H x W u8 in HBM; None / 0: no masks)."""
         n = (C.c_uint32 * n_frames)()
-        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
-        rc = lib().todhip_orb_batch_device_masked(self._h, d_gray, d_mask or None, n_frames, frame_stride, H, W, stride, n_features,
-                                                  n_levels, scale_factor, None if pat is None else _np_ptr(pat), d_kp_xy, d_kp_aux,
-                                                  d_desc, cap, n)
-        _check(rc, "todhip_orb_batch_device_masked")
+        pat = _opt(pattern, np.int8)
+        _call("todhip_orb_batch_device_masked", self._h, d_gray, d_mask or None, n_frames, frame_stride, H, W, stride, n_features, n_levels,
+              scale_factor, _np_ptr(pat), d_kp_xy, d_kp_aux, d_desc, cap, n)
         return list(n)
 
     def rescale_depth(self, depth, H, W, nearest=False):
@@ -903,15 +745,11 @@ class Context:
         u16 = depth.dtype == np.uint16
         d = np.ascontiguousarray(depth, np.uint16 if u16 else np.float32)
         out = np.empty((H, W), np.float32)
-        rc = lib().todhip_rescale_depth(self._h, _np_ptr(d), C.c_int(1 if u16 else 0), C.c_uint32(d.shape[0]), C.c_uint32(d.shape[1]),
-                                        _np_ptr(out), C.c_uint32(H), C.c_uint32(W), C.c_int(1 if nearest else 0))
-        _check(rc, "todhip_rescale_depth")
+        _call("todhip_rescale_depth", self._h, _np_ptr(d), 1 if u16 else 0, d.shape[0], d.shape[1], _np_ptr(out), H, W, 1 if nearest else 0)
         return out
 
     def rescale_depth_device(self, d_depth_in, is_u16, dH, dW, d_depth_out, H, W, nearest=False):
-        rc = lib().todhip_rescale_depth_device(self._h, C.c_void_p(d_depth_in), C.c_int(1 if is_u16 else 0), C.c_uint32(dH),
-                                               C.c_uint32(dW), C.c_void_p(d_depth_out), C.c_uint32(H), C.c_uint32(W), C.c_int(1 if nearest else 0))
-        _check(rc, "todhip_rescale_depth_device")
+        _call("todhip_rescale_depth_device", self._h, d_depth_in, 1 if is_u16 else 0, dH, dW, d_depth_out, H, W, 1 if nearest else 0)
 
 
 class Model:
@@ -921,7 +759,7 @@ class Model:
         self._ctx = ctx
         self._h = C.c_void_p()
         self._cap = capacity_rows
-        _check(lib().todhip_model_begin(ctx._h, C.c_uint32(capacity_rows), C.byref(self._h)), "todhip_model_begin")
+        _call("todhip_model_begin", ctx._h, capacity_rows, C.byref(self._h))
 
     def add_observation(self, gray, mask, depth, K, R, T, n_features=500, n_levels=8, scale_factor=1.2, pattern=None):
         g = np.ascontiguousarray(gray, np.uint8)
@@ -935,12 +773,9 @@ class Model:
         R9 = np.ascontiguousarray(R, np.float32).reshape(9)
         T3 = np.ascontiguousarray(T, np.float32).reshape(3)
         n = C.c_uint32(0)
-        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
-        rc = lib().todhip_model_add_observation(self._ctx._h, self._h, _np_ptr(g), _np_ptr(mk), _np_ptr(d),
-                                                C.c_int(1 if u16 else 0), C.c_uint32(H), C.c_uint32(W), _np_ptr(K9),
-                                                _np_ptr(R9), _np_ptr(T3), C.c_uint32(n_features), C.c_uint32(n_levels),
-                                                C.c_float(scale_factor), None if pat is None else _np_ptr(pat), C.byref(n))
-        _check(rc, "todhip_model_add_observation")
+        pat = _opt(pattern, np.int8)
+        _call("todhip_model_add_observation", self._ctx._h, self._h, _np_ptr(g), _np_ptr(mk), _np_ptr(d), 1 if u16 else 0, H, W, _np_ptr(K9),
+              _np_ptr(R9), _np_ptr(T3), n_features, n_levels, scale_factor, _np_ptr(pat), C.byref(n))
         return n.value
 
     def add_observations_device(self, d_gray, d_mask, d_depth, n_views, H, W, K, R, T, *, stride=None, frame_stride=None,
@@ -962,12 +797,10 @@ class Model:
         if n_views and (K9.size != 9 * n_views or R9.size != 9 * n_views or T3.size != 3 * n_views):
             raise ValueError("K, R, T do not hold n_views cameras")
         n = np.zeros(max(n_views, 1), np.uint32)
-        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
-        rc = lib().todhip_model_add_observations_device(self._ctx._h, self._h, d_gray or None, frame_stride, stride, d_mask or None,
-                                                        d_depth or None, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0, n_views,
-                                                        H, W, _np_ptr(K9), _np_ptr(R9), _np_ptr(T3), n_features, n_levels, scale_factor,
-                                                        None if pat is None else _np_ptr(pat), _np_ptr(n))
-        _check(rc, "todhip_model_add_observations_device")
+        pat = _opt(pattern, np.int8)
+        _call("todhip_model_add_observations_device", self._ctx._h, self._h, d_gray or None, frame_stride, stride, d_mask or None,
+              d_depth or None, 1 if depth_is_u16 else 0, dH, dW, 1 if nearest else 0, n_views, H, W, _np_ptr(K9), _np_ptr(R9), _np_ptr(T3),
+              n_features, n_levels, scale_factor, _np_ptr(pat), _np_ptr(n))
         return n[:n_views].copy()
 
     def add_rows(self, desc, pts):
@@ -977,8 +810,8 @@ class Model:
         if len(d) != len(p):
             raise ValueError("desc and pts differ in rows")
         n = C.c_uint32(0)
-        _check(lib().todhip_model_add_rows(self._ctx._h, self._h, _np_ptr(d) if len(d) else None, _np_ptr(p) if len(d) else None, len(d), C.byref(n)),
-               "todhip_model_add_rows")
+        _call("todhip_model_add_rows", self._ctx._h, self._h, _np_ptr(d) if len(d) else None, _np_ptr(p) if len(d) else None, len(d),
+              C.byref(n))
         return n.value
 
     def compact(self, merge_dist, max_hamming=DEFAULT_COMPACT_HAMMING, want_support=False):
@@ -986,8 +819,8 @@ class Model:
         point and within max_hamming bits of its descriptor) -> (rows_before, rows_after[, support u32[rows_after]])."""
         before, after, ns = C.c_uint32(0), C.c_uint32(0), C.c_uint32(self._cap if want_support else 0)
         sup = np.zeros(max(self._cap, 1), np.uint32) if want_support else None
-        _check(lib().todhip_model_compact(self._ctx._h, self._h, merge_dist, max_hamming, C.byref(before), C.byref(after),
-                                          _np_ptr(sup) if want_support else None, C.byref(ns)), "todhip_model_compact")
+        _call("todhip_model_compact", self._ctx._h, self._h, merge_dist, max_hamming, C.byref(before), C.byref(after), _np_ptr(sup),
+              C.byref(ns))
         if want_support:
             return before.value, after.value, sup[:ns.value].copy()
         return before.value, after.value
@@ -995,14 +828,14 @@ class Model:
     def device(self):
         """(device pointer of the descriptors, device pointer of the points, rows) -- valid until close()."""
         d, p, n = C.c_void_p(), C.c_void_p(), C.c_uint32()
-        _check(lib().todhip_model_device(self._ctx._h, self._h, C.byref(d), C.byref(p), C.byref(n)), "todhip_model_device")
+        _call("todhip_model_device", self._ctx._h, self._h, C.byref(d), C.byref(p), C.byref(n))
         return d.value, p.value, n.value
 
     def finish(self):
         desc = np.zeros((self._cap, 32), np.uint8)
         pts = np.zeros((self._cap, 3), np.float32)
         n = C.c_uint32(self._cap)
-        _check(lib().todhip_model_finish(self._ctx._h, self._h, _np_ptr(desc), _np_ptr(pts), C.byref(n)), "todhip_model_finish")
+        _call("todhip_model_finish", self._ctx._h, self._h, _np_ptr(desc), _np_ptr(pts), C.byref(n))
         return desc[:n.value].copy(), pts[:n.value].copy()
 
     def close(self):
@@ -1021,29 +854,22 @@ class PatternLearner:
         self._h = C.c_void_p()
         self.n_keypoints = 0
         cand = None if candidates is None else np.ascontiguousarray(candidates, np.int8).reshape(-1, 4)
-        _check(lib().todhip_pattern_learn_begin(ctx._h, None if cand is None else _np_ptr(cand), C.c_uint32(0 if cand is None else len(cand)),
-                                                C.c_uint32(capacity_keypoints), C.byref(self._h)), "todhip_pattern_learn_begin")
+        _call("todhip_pattern_learn_begin", ctx._h, _np_ptr(cand), 0 if cand is None else len(cand), capacity_keypoints, C.byref(self._h))
 
     def add_view(self, gray, mask=None, n_features=500, n_levels=8, scale_factor=1.2):
         """The keypoints todhip_orb_masked finds in the view, as many as still fit; returns their number."""
         g = np.ascontiguousarray(gray, np.uint8)
-        mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        mk = _opt(mask, np.uint8)
         H, W = g.shape
-        n = C.c_uint32(0)
-        rc = lib().todhip_pattern_learn_add_view(self._ctx._h, self._h, _np_ptr(g), None if mk is None else _np_ptr(mk), C.c_uint32(H),
-                                                 C.c_uint32(W), C.c_uint32(W), C.c_uint32(n_features), C.c_uint32(n_levels),
-                                                 C.c_float(scale_factor), C.byref(n))
-        _check(rc, "todhip_pattern_learn_add_view")
-        self.n_keypoints += n.value
-        return n.value
+        return self._add_view("todhip_pattern_learn_add_view", _np_ptr(g), _np_ptr(mk), H, W, W, n_features, n_levels, scale_factor)
 
     def add_view_device(self, d_gray, d_mask, H, W, stride, n_features=500, n_levels=8, scale_factor=1.2):
         """Device-pointer form (ints from tensor.data_ptr(); d_mask: row stride W, or None)."""
+        return self._add_view("todhip_pattern_learn_add_view_device", d_gray, d_mask, H, W, stride, n_features, n_levels, scale_factor)
+
+    def _add_view(self, name, *view):
         n = C.c_uint32(0)
-        rc = lib().todhip_pattern_learn_add_view_device(self._ctx._h, self._h, C.c_void_p(d_gray), C.c_void_p(d_mask), C.c_uint32(H),
-                                                        C.c_uint32(W), C.c_uint32(stride), C.c_uint32(n_features), C.c_uint32(n_levels),
-                                                        C.c_float(scale_factor), C.byref(n))
-        _check(rc, "todhip_pattern_learn_add_view_device")
+        _call(name, self._ctx._h, self._h, *view, C.byref(n))
         self.n_keypoints += n.value
         return n.value
 
@@ -1051,16 +877,14 @@ class PatternLearner:
         """-> dict(pattern i8[256, 4], chosen u32[256], round_of u8[256], n_keypoints, n_candidates, accepted_in_round [6])"""
         pattern, chosen, round_of = np.zeros((256, 4), np.int8), np.zeros(256, np.uint32), np.zeros(256, np.uint8)
         st = PatternStats()
-        _check(lib().todhip_pattern_learn_finish(self._ctx._h, self._h, C.c_int(order), _np_ptr(pattern), _np_ptr(chosen), _np_ptr(round_of),
-                                                 C.byref(st)), "todhip_pattern_learn_finish")
+        _call("todhip_pattern_learn_finish", self._ctx._h, self._h, order, _np_ptr(pattern), _np_ptr(chosen), _np_ptr(round_of), C.byref(st))
         return dict(pattern=pattern, chosen=chosen, round_of=round_of, n_keypoints=int(st.n_keypoints), n_candidates=int(st.n_candidates),
                     accepted_in_round=[int(x) for x in st.accepted_in_round])
 
     def responses(self, first, count):
         """Rows first .. first + count - 1 of the response matrix: u32 [count, ceil(n_keypoints / 32)] (test hook)."""
         words = np.zeros((count, (self.n_keypoints + 31) // 32), np.uint32)
-        _check(lib().todhip_pattern_learn_responses(self._ctx._h, self._h, C.c_uint32(first), C.c_uint32(count), _np_ptr(words)),
-               "todhip_pattern_learn_responses")
+        _call("todhip_pattern_learn_responses", self._ctx._h, self._h, first, count, _np_ptr(words))
         return words
 
     def close(self):
@@ -1074,7 +898,6 @@ class _Borrowed(Context):
 
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
-        self._keep = None
 
     def close(self):
         self._h = C.c_void_p()
@@ -1083,7 +906,7 @@ class _Borrowed(Context):
 def pipeline_params(**kw):
     """todhip_pipeline_default_params with the given fields replaced (K: 3x3 camera matrix, verify: (min_inliers, n_iter, err))."""
     p = PipelineParams()
-    _check(lib().todhip_pipeline_default_params(C.byref(p)), "todhip_pipeline_default_params")
+    _call("todhip_pipeline_default_params", C.byref(p))
     for key, v in kw.items():
         if key == "K":
             p.K9[:] = [float(x) for x in _k9(v)]
@@ -1101,7 +924,7 @@ class Pipeline:
     def __init__(self, device=0, params=None, **kw):
         self.params = params if params is not None else pipeline_params(**kw)
         self._h = C.c_void_p()
-        _check(lib().todhip_pipeline_create(C.c_int(device), C.byref(self.params), C.byref(self._h)), "todhip_pipeline_create")
+        _call("todhip_pipeline_create", device, C.byref(self.params), C.byref(self._h))
         self._n = {}                                                  # ticket -> n_frames
 
     def close(self):
@@ -1121,50 +944,45 @@ class Pipeline:
     def db_load(self, desc, pts, obj_off):
         """As Context.db_load, for u8[N,32] only (the ORB stage emits 32 bytes: EINVAL for any other width); returns the status."""
         desc = np.ascontiguousarray(desc, np.uint8)
-        B = desc.shape[1] if desc.ndim == 2 else 32
         pts = np.ascontiguousarray(pts, np.float32)
-        obj_off = np.asarray(obj_off, np.int64)
-        n_obj = len(obj_off) - 1
-        objs = (TodObject * max(n_obj, 1))()
-        for o in range(n_obj):
-            lo, hi = int(obj_off[o]), int(obj_off[o + 1])
-            objs[o].desc, objs[o].pts_xyz, objs[o].n = desc.ctypes.data + lo * B, pts.ctypes.data + lo * 12, hi - lo
-        return lib().todhip_pipeline_db_load(self._h, objs, C.c_uint32(n_obj), C.c_uint32(B))
+        objs, n_obj, B = _objects(desc, pts, obj_off)
+        return lib().todhip_pipeline_db_load(self._h, objs, n_obj, B)
 
     def db_load_models(self, models):
-        objs = (TodObject * len(models))()
-        for i, m in enumerate(models):
-            objs[i].desc, objs[i].pts_xyz, objs[i].n = m.device()
-        return lib().todhip_pipeline_db_load_device(self._h, objs, C.c_uint32(len(models)), C.c_uint32(32))
+        return lib().todhip_pipeline_db_load_device(self._h, _model_objects(models)[0], len(models), 32)
 
     def set_pattern(self, pattern):
         """The ORB workers' pattern from the next submit on (i8 [256, 4], None = built-in); returns the status (EBUSY while a ticket
         is outstanding)."""
-        pat = None if pattern is None else np.ascontiguousarray(pattern, np.int8)
+        pat = _opt(pattern, np.int8)
         assert pat is None or pat.size == 1024
-        return lib().todhip_pipeline_set_pattern(self._h, None if pat is None else _np_ptr(pat))
+        return lib().todhip_pipeline_set_pattern(self._h, _np_ptr(pat))
 
     def set_cross_check(self, enable):
         """The cross-check behind each step's matcher call, per frame among its n_kp keypoints (todhip_pipeline_set_cross_check).
         Returns the status (EBUSY while a ticket is outstanding)."""
-        return lib().todhip_pipeline_set_cross_check(self._h, C.c_int(1 if enable else 0))
+        return lib().todhip_pipeline_set_cross_check(self._h, 1 if enable else 0)
 
     def select_objects(self, ids):
         """Context.select_objects on the pipeline's matcher, from the next submit on; returns the status (EBUSY while a ticket is
         outstanding)."""
         p, n, keep = _ids_in(ids)
-        return lib().todhip_pipeline_select_objects(self._h, p, C.c_uint32(n))
+        return lib().todhip_pipeline_select_objects(self._h, p, n)
+
+    def _submit(self, name, n_frames, *buffers):
+        """(status, ticket) of a submit call on the buffers (frames, masks where the form has them, depth); remembers an accepted
+        ticket's frame count for wait()"""
+        t = C.c_uint64(0)
+        rc = getattr(lib(), name)(self._h, *buffers, n_frames, C.byref(t))
+        if rc == OK:
+            self._n[t.value] = n_frames
+        return rc, t.value
 
     def submit(self, frames, depth, n_frames=None):
         """Host form: frames u8 [n, H, W(, 3 | 4)], depth f32 | u16 [n, H, W] as numpy arrays. Returns (status, ticket)."""
         fr = np.ascontiguousarray(frames, np.uint8)
         dp = np.ascontiguousarray(depth, np.uint16 if self.params.depth_is_u16 else np.float32)
-        n = len(fr) if n_frames is None else n_frames
-        t = C.c_uint64(0)
-        rc = lib().todhip_pipeline_submit(self._h, _np_ptr(fr), _np_ptr(dp), C.c_uint32(n), C.byref(t))
-        if rc == OK:
-            self._n[t.value] = n
-        return rc, t.value
+        return self._submit("todhip_pipeline_submit", len(fr) if n_frames is None else n_frames, _np_ptr(fr), _np_ptr(dp))
 
     def set_depth_size(self, dH, dW, nearest=False):
         """A depth image is dH x dW from the next submit on ((0, 0): the image's size); returns the status (EINVAL: a geometry
@@ -1174,30 +992,17 @@ class Pipeline:
     def submit_masked(self, frames, masks, depth, n_frames=None):
         """submit with masks u8 [n, H, W] (None: submit). Returns (status, ticket)."""
         fr = np.ascontiguousarray(frames, np.uint8)
-        mk = None if masks is None else np.ascontiguousarray(masks, np.uint8)
+        mk = _opt(masks, np.uint8)
         dp = np.ascontiguousarray(depth, np.uint16 if self.params.depth_is_u16 else np.float32)
-        n = len(fr) if n_frames is None else n_frames
-        t = C.c_uint64(0)
-        rc = lib().todhip_pipeline_submit_masked(self._h, _np_ptr(fr), None if mk is None else _np_ptr(mk), _np_ptr(dp), n, C.byref(t))
-        if rc == OK:
-            self._n[t.value] = n
-        return rc, t.value
+        return self._submit("todhip_pipeline_submit_masked", len(fr) if n_frames is None else n_frames, _np_ptr(fr), _np_ptr(mk), _np_ptr(dp))
 
     def submit_masked_device(self, d_frames, d_masks, d_depth, n_frames):
         """submit_device with d_masks (n x H x W u8 in HBM, None / 0: no masks), read as long as the frames are."""
-        t = C.c_uint64(0)
-        rc = lib().todhip_pipeline_submit_masked_device(self._h, d_frames, d_masks or None, d_depth, n_frames, C.byref(t))
-        if rc == OK:
-            self._n[t.value] = n_frames
-        return rc, t.value
+        return self._submit("todhip_pipeline_submit_masked_device", n_frames, d_frames, d_masks or None, d_depth)
 
     def submit_device(self, d_frames, d_depth, n_frames):
         """Device form (ints from tensor.data_ptr()); the buffers are read until wait() has returned the ticket's results."""
-        t = C.c_uint64(0)
-        rc = lib().todhip_pipeline_submit_device(self._h, C.c_void_p(d_frames), C.c_void_p(d_depth), C.c_uint32(n_frames), C.byref(t))
-        if rc == OK:
-            self._n[t.value] = n_frames
-        return rc, t.value
+        return self._submit("todhip_pipeline_submit_device", n_frames, d_frames, d_depth)
 
     def wait(self, ticket, timeout_ms=0, max_poses=None, max_inliers=None, want_kp=True):
         """Returns (status, result). result (status OK): list per frame of dict(n_kp, kp_xy f32[n_kp, 2] or None, poses = list of pose
@@ -1212,8 +1017,8 @@ class Pipeline:
             self._inl, self._inl_cap = np.zeros(max(cap_i, 1), np.uint32), max(cap_i, 1)
         poses, inl = (Pose * max(cap_p, 1))(), self._inl
         n_poses, n_inl, pose_ptr = C.c_uint32(cap_p), C.c_uint32(cap_i), (C.c_uint32 * (n + 1))()
-        rc = lib().todhip_pipeline_wait(self._h, C.c_uint64(ticket), C.c_uint32(timeout_ms), n_kp, None if kp is None else _np_ptr(kp),
-                                        poses, C.byref(n_poses), pose_ptr, _np_ptr(inl), C.byref(n_inl))
+        rc = lib().todhip_pipeline_wait(self._h, ticket, timeout_ms, n_kp, _np_ptr(kp), poses, C.byref(n_poses), pose_ptr, _np_ptr(inl),
+                                        C.byref(n_inl))
         if rc == ECAPACITY:
             return rc, (n_poses.value, n_inl.value)
         if rc != ETIMEOUT:
@@ -1225,28 +1030,27 @@ class Pipeline:
 
     def stats(self):
         s = PipelineStats()
-        _check(lib().todhip_pipeline_get_stats(self._h, C.byref(s)), "todhip_pipeline_get_stats")
+        _call("todhip_pipeline_get_stats", self._h, C.byref(s))
         return {name: getattr(s, name) for name, _ in PipelineStats._fields_}
 
 
 def bgr_to_gray_device(ctx, d_src, channels, H, W, src_stride, d_gray, gray_stride):
-    _check(lib().todhip_bgr_to_gray_device(ctx._h, C.c_void_p(d_src), C.c_uint32(channels), C.c_uint32(H), C.c_uint32(W),
-                                           C.c_uint32(src_stride), C.c_void_p(d_gray), C.c_uint32(gray_stride)), "todhip_bgr_to_gray_device")
+    _call("todhip_bgr_to_gray_device", ctx._h, d_src, channels, H, W, src_stride, d_gray, gray_stride)
 
 
 def set_cu_partition(latency_cus):
     """Reserve the device's last `latency_cus` compute units for latency streams (todhip_set_cu_partition); 0 = none."""
-    _check(lib().todhip_set_cu_partition(C.c_uint32(latency_cus)), "todhip_set_cu_partition")
+    _call("todhip_set_cu_partition", latency_cus)
 
 
 def stream_create(device=0, latency=False):
     """A HIP stream handle (int) of the given kind, honouring the CU partition (todhip_stream_create)."""
     out = C.c_void_p()
-    _check(lib().todhip_stream_create(C.c_int(device), C.c_int(1 if latency else 0), C.byref(out)), "todhip_stream_create")
+    _call("todhip_stream_create", device, 1 if latency else 0, C.byref(out))
     return out.value
 
 
 def rng_new(seed=1):
     r = Rng()
-    lib().todhip_rng_seed(C.byref(r), C.c_uint32(seed))
+    lib().todhip_rng_seed(C.byref(r), seed)
     return r

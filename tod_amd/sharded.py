@@ -209,42 +209,28 @@ class GpuOps:
             self.dist.all_to_all_single(o, inp.contiguous().view(-1).cpu())
             out.view(-1).copy_(o.to(out.device))
 
+    # (metric, radius search) -> the context's shard call and the settings it takes between (q, n) and the keys; its merge call and the
+    # settings that one takes between (keys, n_shards, n) and the outputs. A radius merge also writes out["in_radius"].
+    FAMILIES = {
+        ("hamming", False): ("match_shard_device", ("k", "radius"), "merge_shards_device", ("k", "radius")),
+        ("hamming", True): ("match_radius_shard_device", ("radius", "max_per_query"), "merge_radius_shards_device", ("max_per_query",)),
+        ("l2", False): ("match_l2_shard_device", ("k",), "merge_l2_shards_device", ("k", "radius")),
+        ("l2", True): ("match_l2_radius_shard_device", ("radius", "max_per_query"), "merge_l2_radius_shards_device", ("max_per_query",)),
+    }
+
     def match_shard(self, q_all, n, keys_out):
         if self.metric == "l2" and q_all.shape[-1] * q_all.element_size() != self.ctx.desc_bytes():   # ShardedMatcher(desc_bytes=256 or 512)
             raise ValueError("query rows of %d bytes against a float DB of %d-byte rows" % (q_all.shape[-1] * q_all.element_size(), self.ctx.desc_bytes()))
-        if self.metric == "l2" and self.max_per_query is not None:
-            self.ctx.match_l2_radius_shard_device(q_all.data_ptr(), n, self.radius, self.max_per_query, keys_out.data_ptr())
-        elif self.metric == "l2":
-            self.ctx.match_l2_shard_device(q_all.data_ptr(), n, self.k, keys_out.data_ptr())
-        elif self.max_per_query is not None:
-            self.ctx.match_radius_shard_device(q_all.data_ptr(), n, self.radius, self.max_per_query, keys_out.data_ptr())
-        else:
-            self.ctx.match_shard_device(q_all.data_ptr(), n, self.k, self.radius, keys_out.data_ptr())
-
-    def _merge_l2(self, keys_mine, n_shards, n, out, stream):
-        on = None if stream is self.compute else stream.cuda_stream
-        if self.max_per_query is not None:
-            self.ctx.merge_l2_radius_shards_device(keys_mine.data_ptr(), n_shards, n, self.max_per_query, out["counts"].data_ptr(),
-                                                   out["matches"].data_ptr(), out["xyz"].data_ptr(), out["in_radius"].data_ptr(), stream=on)
-        else:
-            self.ctx.merge_l2_shards_device(keys_mine.data_ptr(), n_shards, n, self.k, self.radius, out["counts"].data_ptr(),
-                                            out["matches"].data_ptr(), out["xyz"].data_ptr(), stream=on)
+        call, settings, _, _ = self.FAMILIES[self.metric, self.max_per_query is not None]
+        getattr(self.ctx, call)(q_all.data_ptr(), n, *[getattr(self, s) for s in settings], keys_out.data_ptr())
 
     def merge(self, keys_mine, n_shards, n, out, stream):
-        if self.metric == "l2":
-            return self._merge_l2(keys_mine, n_shards, n, out, stream)
-        if self.max_per_query is not None:
-            args = (keys_mine.data_ptr(), n_shards, n, self.max_per_query, out["counts"].data_ptr(), out["matches"].data_ptr(),
-                    out["xyz"].data_ptr(), out["in_radius"].data_ptr())
-            plain, on = self.ctx.merge_radius_shards_device, self.ctx.merge_radius_shards_device_on
-        else:
-            args = (keys_mine.data_ptr(), n_shards, n, self.k, self.radius, out["counts"].data_ptr(), out["matches"].data_ptr(),
-                    out["xyz"].data_ptr())
-            plain, on = self.ctx.merge_shards_device, self.ctx.merge_shards_device_on
-        if stream is self.compute:
-            plain(*args)
-        else:       # the merge only reads the context's immutable tables: it may run beside the next DB pass
-            on(stream.cuda_stream, *args)
+        radius_search = self.max_per_query is not None
+        _, _, call, settings = self.FAMILIES[self.metric, radius_search]
+        outputs = ("counts", "matches", "xyz", "in_radius") if radius_search else ("counts", "matches", "xyz")
+        # the merge only reads the context's immutable tables: on another stream than compute it may run beside the next DB pass
+        getattr(self.ctx, call)(keys_mine.data_ptr(), n_shards, n, *[getattr(self, s) for s in settings],
+                                *[out[o].data_ptr() for o in outputs], stream=None if stream is self.compute else stream.cuda_stream)
 
     def select_objects(self, ids):
         self.compute.synchronize()                      # the context's calls are issued on this stream
