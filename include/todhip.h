@@ -602,7 +602,12 @@ int todhip_verify_batch_device_depth_rescaled(todhip_ctx*, uint32_t n_frames, co
  * a larger image). A pyramid level that rounds to fewer than 63 pixels either way yields nothing; an image without any other level
  * returns 0 keypoints. Outputs up to n_features keypoints: kp_xy (x,y level-0 pixels),
  * kp_aux (size, angle_deg, response, octave) and 32-byte rBRIEF descriptors. *n_out: capacity in, count out.
- * pattern: 256 x 4 int8 (x0,y0,x1,y1) test pairs, or NULL for the built-in seeded pattern. */
+ * pattern: 256 x 4 int8 (x0,y0,x1,y1) test pairs, or NULL for the built-in seeded pattern. Domain: every point (x0,y0) and (x1,y1)
+ * has x^2 + y^2 <= 900. A keypoint lies at least 31 pixels inside its level and a steered point keeps its distance from the centre, so
+ * this is the largest disc whose rotated, rounded points all read pixels of the keypoint's own level; it contains the 31 x 31 patch
+ * (|x|, |y| <= 15) of cv::ORB patterns and the learner's candidates (x^2 + y^2 <= 169). A pattern with a point outside it:
+ * TODHIP_EINVAL before any device work, from every form that takes a `pattern` -- the todhip_orb* forms below,
+ * todhip_model_add_observation[s_device] and todhip_pipeline_set_pattern (at that call, the pipeline's pattern stays as it was). */
 int todhip_orb(todhip_ctx*, const uint8_t* gray, uint32_t H, uint32_t W, uint32_t stride, uint32_t n_features,
                uint32_t n_levels, float scale_factor, const int8_t* pattern, float* kp_xy, float* kp_aux,
                uint8_t* desc, uint32_t* n_out);
@@ -759,7 +764,8 @@ int  todhip_pipeline_wait(todhip_pipeline*, uint64_t ticket, uint32_t timeout_ms
 int  todhip_pipeline_get_stats(todhip_pipeline*, todhip_pipeline_stats* out);
 /* The ORB pattern of the pipeline's ORB workers (256 x 4 int8, copied; NULL = the built-in one), from the next submit on: how a
  * pattern learned by todhip_pattern_learn_* reaches the batched path. The DB must hold descriptors of the same pattern.
- * TODHIP_EBUSY while a ticket is outstanding. */
+ * TODHIP_EBUSY while a ticket is outstanding. A pattern outside the domain stated at todhip_orb (a point with x^2 + y^2 > 900):
+ * TODHIP_EINVAL here, not at the next submit, and the workers' pattern stays what it was. */
 int  todhip_pipeline_set_pattern(todhip_pipeline*, const int8_t* pattern /* 256 x 4; NULL = built-in */);
 /* The size of a depth image, from the next submit on: dH x dW values (uint16 or float as depth_is_u16 says), rescaled to the image
  * as todhip_rescale_depth does (nearest != 0: its nearest mode) -- see the definition above and todhip_verify_device_depth_rescaled.
@@ -797,7 +803,8 @@ int  todhip_bgr_to_gray_device(todhip_ctx*, const void* d_src, uint32_t channels
 typedef struct todhip_model todhip_model;
 int  todhip_model_begin(todhip_ctx*, uint32_t capacity_rows, todhip_model** out);
 /* gray/mask: H x W u8 (mask != 0 = object); depth: H x W float metres (NaN = none) or uint16 millimetres (0 = none),
- * of the image size (other sizes: todhip_rescale_depth first, as Trainer.cpp:142-143 does); K9, R9 row-major; T3. */
+ * of the image size (other sizes: todhip_rescale_depth first, as Trainer.cpp:142-143 does); K9, R9 row-major; T3.
+ * pattern: as at todhip_orb, its domain included (outside it: TODHIP_EINVAL, the model unchanged; the batch form below likewise). */
 int  todhip_model_add_observation(todhip_ctx*, todhip_model*, const uint8_t* gray, const uint8_t* mask, const void* depth,
                                   int depth_is_u16, uint32_t H, uint32_t W, const float* K9, const float* R9, const float* T3,
                                   uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,

@@ -7,11 +7,13 @@
 //   want[l] == 0 iff the level is too small, wherever the share is positive (a share can round to 0: 1 feature over 3 levels);
 //   the shares sum to n_features when the last level's is positive, and so do the wants when no level is too small;
 //   invalid arguments are TODHIP_EINVAL even with cap == 0, which alone is TODHIP_ECAPACITY.
+// Also check_pattern and the pattern domain's reason (pattern_domain below).
 // Prints "<plans compared> <calls refused>"; exits 1 at the first difference.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "orb_plan.h"
@@ -127,7 +129,40 @@ static bool one(uint32_t F, uint32_t H, uint32_t W, uint32_t nf, uint32_t nl, fl
   return true;
 }
 
+// check_pattern: one point moved through all of int8 x int8 at the table's first, a middle and its last position is refused exactly
+// when x^2 + y^2 > 900; and what the domain is for -- a point inside it, steered by any direction (cos, sin) = (m10, m01) / |m| in
+// the float expressions of steer_of and steered_test, rounds to coordinates of magnitude <= 30 < kEdge, so the test reads a pixel of
+// the keypoint's own level.
+static bool pattern_domain() {
+  int8_t pat[1024];
+  default_pattern(pat);
+  if (check_pattern(nullptr) != TODHIP_OK || check_pattern(pat) != TODHIP_OK) return false;
+  for (int slot : {0, 2, 510, 1020, 1022})                       // byte offsets of points: the first test, a middle one, the last
+    for (int x = -128; x <= 127; ++x)
+      for (int y = -128; y <= 127; ++y) {
+        default_pattern(pat);
+        pat[slot] = (int8_t)x; pat[slot + 1] = (int8_t)y;
+        const int want = x * x + y * y <= 900 ? TODHIP_OK : TODHIP_EINVAL;
+        if (check_pattern(pat) != want) { printf("check_pattern: (%d, %d) at byte %d\n", x, y, slot); return false; }
+      }
+  static_assert(kPatternDomainRadius2 == 900 && kPatternRadius2 <= kPatternDomainRadius2 && 2 * 15 * 15 <= kPatternDomainRadius2, "domains");
+  for (int x = -30; x <= 30; ++x)
+    for (int y = -30; y <= 30; ++y) {
+      if (x * x + y * y <= 29 * 29 || x * x + y * y > 900) continue;   // the outer ring
+      for (int m10 = -2000; m10 <= 2000; m10 += 7)
+        for (int m01 = -2000; m01 <= 2000; m01 += 11) {
+          const float fm10 = (float)m10 * 613.f, fm01 = (float)m01 * 577.f;
+          const float nrm = sqrtf(fm10 * fm10 + fm01 * fm01);
+          const float ca = nrm > 0.f ? fm10 / nrm : 1.f, sa = nrm > 0.f ? fm01 / nrm : 0.f;
+          const int rx = (int)rintf((float)x * ca - (float)y * sa), ry = (int)rintf((float)x * sa + (float)y * ca);
+          if (std::abs(rx) > 30 || std::abs(ry) > 30) { printf("steered (%d, %d) by (%d, %d): (%d, %d)\n", x, y, m10, m01, rx, ry); return false; }
+        }
+    }
+  return true;
+}
+
 int main() {
+  if (!pattern_domain()) return 1;
   static_assert(kEdge == 31 && kMaxLevels == 16 && kCtlWords == 512 && kNmsTileW == 64 && kNmsTileH == 16 && kBlurTileW == 128 &&
                 kBlurTileH == 64 && kLevelCountWord == 8, "the restated expressions above spell these out");
   const uint32_t sizes[] = {7, 8, 9, 62, 63, 64, 65, 96, 240, 480, 640, 1080, 1920};

@@ -1,6 +1,6 @@
 """Stage A's resize from tap tables, compass test on four positions per lane and patch moments from four-pixel words, at the
 smallest shapes where each can go wrong, against the CPU restatement (the contract of tests/test_orb_gpu.py: everything bit-exact, the
-angle within 1e-2 degrees):
+angle within 4.9e-4 degrees):
   level rows that end 1, 2 or 3 pixels into a lane's group of four (resize_kernel's byte tail), at level 0 for the FAST groups and at
   level 1 for the resize; levels at or under 62 pixels, which are resized but yield nothing; FAST tiles whose right edge cuts a
   group; noise, where pass 1's survivor list is as full as it gets; a constant image; a row stride; a mask; two geometries

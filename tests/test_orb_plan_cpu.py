@@ -1,7 +1,8 @@
 """Stage A's launch plan (tod_amd/csrc/orb_plan.h) without a GPU: a stand-alone host program, built with
 -fsanitize=address,undefined, compares OrbPlan field by field with the expressions of orb.hip it replaced (the pyramid's level table,
 the argument checks, the buffer capacities, the control block's layout, every grid extent) over a sweep of geometries, and asserts
-the documented rules of the level table and of the statuses (tests/orb_plan_host_test.cpp)."""
+the documented rules of the level table and of the statuses, check_pattern included: which points it refuses, and that a point it
+accepts stays within 30 pixels of the keypoint when steered in float (tests/orb_plan_host_test.cpp)."""
 import os
 import subprocess
 

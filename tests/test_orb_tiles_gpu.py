@@ -2,7 +2,7 @@
 compass test over every position, the exact score over the compacted survivors) and blur_kernel filters 128 x 64 pixel tiles through
 LDS, four pixels to a lane: what can go wrong is a halo, a row that ends inside a group of four pixels, a row pitch that is no
 multiple of four, a survivor list that overflows, and a neighbouring frame read across a slice's end. Every comparison is against the
-CPU restatement: counts, positions, size / response / octave and descriptors bit for bit; the reported angle within 1e-2 degrees,
+CPU restatement: counts, positions, size / response / octave and descriptors bit for bit; the reported angle within 4.9e-4 degrees,
 the contract of every ORB comparison here (tests/test_orb_gpu.py: _equal -- it is atan2f of two libraries, of moments that are
 themselves compared through the descriptors, which are steered by them).
 

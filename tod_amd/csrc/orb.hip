@@ -152,6 +152,9 @@ void record_stages(const OrbPlan& P, const OrbWs* ws, const uint8_t* d_mask, hip
 int orb_device(todhip_ctx* ctx, const OrbIn& in, const OrbParams& par, const OrbOut& out) {
   OrbPlan P;
   if (const int bad = orb_plan(in.F, in.H, in.W, par.n_features, par.n_levels, par.scale_factor, out.cap, &P)) return bad;
+  // where every form's pattern enters: a point outside the domain would steer a test out of the keypoint's level (steered_test reads
+  // blur[(y + y0) * W + x + x0] unchecked). Refused before the workspace, the cached pattern or the graph are touched.
+  if (const int bad = check_pattern(par.pattern)) return bad;
   OrbWs* ws = tod_ws<OrbWs>(ctx);
   hipStream_t st = ctx->stream;
   if (P.want_max == 0) {
@@ -300,6 +303,7 @@ int todhip_orb_masked(todhip_ctx* ctx, const uint8_t* gray, const uint8_t* mask,
   const uint32_t cap = *n_out;
   *n_out = 0;
   if (const int bad = check_args(1, H, W, n_features, n_levels, scale_factor, cap)) return bad;   // before anything is read
+  if (const int bad = check_pattern(pattern)) return bad;
   // the outputs land in pinned host memory, written by the last kernel itself (56 B per keypoint over PCIe): no device-to-host
   // copies and no second synchronization behind orb_device's own
   TOD_HIP(ws->h_kp.reserve((size_t)cap * 56 + 64));

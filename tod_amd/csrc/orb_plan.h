@@ -18,6 +18,10 @@ constexpr int kEdge = 31;
 constexpr int kHalfPatch = 15;
 constexpr int kMaxLevels = 16;
 constexpr int kPatternRadius2 = 13 * 13;   // every pattern point: x^2 + y^2 <= 169, so a rotated, rounded point stays inside the patch
+// The `pattern` argument's domain (include/todhip.h at todhip_orb): x^2 + y^2 <= 900. A keypoint is kEdge = 31 pixels inside its level,
+// a rotation keeps a point's distance from the centre and rintf of a coordinate of magnitude <= 30 (+ a few float roundings) is <= 30,
+// so every steered test reads a pixel of the keypoint's own level; the 31 x 31 square of cv::ORB patterns (|x|, |y| <= 15) is inside.
+constexpr int kPatternDomainRadius2 = 30 * 30;
 
 struct Cand { int x, y, score; float harris; };
 
@@ -78,6 +82,17 @@ inline void features_per_level(uint32_t n_features, uint32_t n_levels, float sca
   }
   const int rest = (int)n_features - sum;
   out[n_levels - 1] = rest > 0 ? (uint32_t)rest : 0u;
+}
+
+// a caller's pattern (256 x 4 int8, or null for the built-in one) inside its domain: checked wherever a pattern enters the library,
+// before anything is launched or stored
+inline int check_pattern(const int8_t* pattern) {
+  if (!pattern) return TODHIP_OK;
+  for (int i = 0; i < 256 * 2; ++i) {
+    const int x = pattern[2 * i], y = pattern[2 * i + 1];
+    if (x * x + y * y > kPatternDomainRadius2) return TODHIP_EINVAL;
+  }
+  return TODHIP_OK;
 }
 
 // what every form refuses before it touches the device or the caller's memory; (level, frame) pairs ride in a grid dimension

@@ -20,6 +20,7 @@
 
 #include "ctx.h"
 #include "depth_rescale.h"
+#include "orb_plan.h"
 
 namespace {
 
@@ -501,6 +502,7 @@ int todhip_pipeline_db_load_device(todhip_pipeline* p, const todhip_object* objs
 
 int todhip_pipeline_set_pattern(todhip_pipeline* p, const int8_t* pattern) {
   if (!p) return TODHIP_EINVAL;
+  if (const int bad = tod_orb::check_pattern(pattern)) return bad;     // here, not at the next submit: the pattern in use stays
   std::lock_guard<std::mutex> lk(p->mu);
   if (p->dead) return TODHIP_EHIP;
   for (const Slot& s : p->slots)

@@ -229,6 +229,7 @@ int todhip_model_add_observation(todhip_ctx* ctx, todhip_model* m, const uint8_t
                                  uint32_t n_features, uint32_t n_levels, float scale_factor, const int8_t* pattern,
                                  uint32_t* n_added) {
   if (!ctx || !m || !gray || !mask || !depth || !K9 || !R9 || !T3 || H < 8 || W < 8 || n_features == 0) return TODHIP_EINVAL;
+  if (const int bad = tod_orb::check_pattern(pattern)) return bad;     // before the view is copied in
   TOD_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t px = (size_t)H * W, dbytes = px * (depth_is_u16 ? 2 : 4);
@@ -281,6 +282,7 @@ int todhip_model_add_observations_device(todhip_ctx* ctx, todhip_model* m, const
   tod::RescaleGeom geom;
   if (!tod::rescale_geometry(dH, dW, H, W, nearest, &geom)) return TODHIP_EINVAL;
   if (const int bad = tod_orb::check_args(n_views, H, W, n_features, n_levels, scale_factor, n_features)) return bad;
+  if (const int bad = tod_orb::check_pattern(pattern)) return bad;
   TOD_HIP(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t rows = (size_t)n_views * n_features;
