@@ -472,6 +472,10 @@ int todhip_cross_check_device(todhip_ctx*, const void* d_q_desc, uint32_t nq, ui
  * TODHIP_EINVAL, and the setting does not change: Q > 0 on a context whose DB is float or is one shard of several. */
 int todhip_set_cross_check(todhip_ctx*, uint32_t frame_queries /* 0 = off, the default */);
 
+/* Lowe's ratio test against ANOTHER OBJECT than the nearest match's -- todhip_other_object_min_device, todhip_ratio_other_apply_device,
+ * todhip_ratio_other_device, todhip_set_ratio_test_other -- is declared and defined in todhip_ratio_other.h, which this header
+ * includes at its end: a host that includes todhip.h has those four calls. */
+
 /* The two filters of the float forms (a DB of desc_bytes == 512). todhip_set_ratio_test and todhip_set_cross_check do not apply to the
  * float forms, whatever the comments above say about "every todhip_match* form": they keep their behaviour on every context (a host
  * that set them on a shared context keeps its results), and the float forms have setters of their own -- todhip_set_l2_ratio_test,
@@ -734,8 +738,9 @@ int  todhip_pipeline_default_params(todhip_pipeline_params* out);
  * device form; the host form's pinned staging and upload buffers are allocated by a slot's first todhip_pipeline_submit. */
 int  todhip_pipeline_create(int device, const todhip_pipeline_params*, todhip_pipeline** out);
 void todhip_pipeline_destroy(todhip_pipeline*);          /* drains what is in flight, joins its threads */
-/* The matcher context, for todhip_set_ratio_test / _set_lsh / _set_matcher_engine / _set_kernel_timing / _set_db_bit_order: only
- * while no ticket is outstanding. It is the pipeline's: do not call the match functions on it and do not destroy it.
+/* The matcher context, for todhip_set_ratio_test / _set_ratio_test_other / _set_lsh / _set_matcher_engine / _set_kernel_timing /
+ * _set_db_bit_order: only while no ticket is outstanding. todhip_set_ratio_test_other reaches every step's todhip_match_device this
+ * way, with no setter of the pipeline's own; the rows behind a frame's n_kp are padded away behind the filter as behind the search. It is the pipeline's: do not call the match functions on it and do not destroy it.
  * todhip_set_db_bit_order(todhip_pipeline_matcher(p), 1) before todhip_pipeline_db_load[_device] orders the pipeline's DB. */
 todhip_ctx* todhip_pipeline_matcher(todhip_pipeline*);
 /* todhip_db_load[_device] into the matcher context (one device, desc_bytes == 32); the spans are kept for the verifier workers.
@@ -985,4 +990,5 @@ int todhip_test_consensus(todhip_ctx*, const float* train_xyz, const float* quer
 #ifdef __cplusplus
 }
 #endif
+#include "todhip_ratio_other.h"
 #endif /* TODHIP_H_ */

@@ -4,7 +4,7 @@ The shared library is the product; this module only loads it and marshals numpy 
 buffers to plain pointers. There is no CPU fallback: if the library or the GPU is missing,
 loading or context creation raises.
 
-Every prototype comes from include/todhip.h: the header is parsed when this module is imported (the import fails without it, or on a
+Every prototype comes from include/todhip.h (and the part of it kept in include/todhip_ratio_other.h): the header is parsed when this module is imported (the import fails without it, or on a
 declaration it cannot read) and lib() sets argtypes and restype of each function it declares, so a signature is written once, there. An argument of the wrong kind -- a ctypes wrapper of another type than the header's, a float for an
 integer, a numpy scalar for a pointer -- therefore raises ctypes.ArgumentError at the call; it is never truncated or reinterpreted.
 Plain Python and numpy integers, bool, None (NULL), byref(...), ctypes arrays and instances of the header's own type pass.
@@ -18,6 +18,8 @@ import numpy as np
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "todhip.h")
+# the part of the C ABI that todhip.h includes at its end: the ratio test against another object
+RATIO_OTHER_HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "todhip_ratio_other.h")
 # TODHIP_LIB_PATH: another build of the same library (the diagnostics builds of tools/*_ablate.sh, an A/B against HEAD) -- loaded
 # instead of, never copied over, the product file
 LIB_PATH = os.environ.get("TODHIP_LIB_PATH") or os.path.join(_PKG, "libtodhip.so")
@@ -111,6 +113,10 @@ def _prototypes(path):
 _PROTOTYPES = _prototypes(HEADER_PATH)
 # every symbol include/todhip.h declares, in its order (tests/test_abi.py checks them and their prototypes against the header text)
 EXPORTS = list(_PROTOTYPES)
+# ... and those of include/todhip_ratio_other.h, read the same way (tests/test_ratio_other_binding_cpu.py checks them as test_abi.py
+# and test_capi_marshal_cpu.py check the list above)
+_RATIO_OTHER_PROTOTYPES = _prototypes(RATIO_OTHER_HEADER_PATH)
+RATIO_OTHER_EXPORTS = list(_RATIO_OTHER_PROTOTYPES)
 
 MAX_TRAIN_BATCH_VIEWS = 64
 
@@ -154,7 +160,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _PROTOTYPES.items():
+        for name, (restype, argtypes) in list(_PROTOTYPES.items()) + list(_RATIO_OTHER_PROTOTYPES.items()):
             f = getattr(L, name, None)            # TODHIP_LIB_PATH may name a build of an older commit: what it lacks stays an AttributeError
             if f is not None:
                 f.restype, f.argtypes = restype, argtypes
@@ -262,7 +268,33 @@ def _pose_list(poses, lo, hi, inl):
                  inliers=inl[poses[i].inlier_begin:poses[i].inlier_end].copy()) for i in range(lo, hi)]
 
 
-class Context:
+class _RatioOtherCalls:
+    """The calls of include/todhip_ratio_other.h on a context: a base of Context, so that a borrowed context (the pipeline's matcher)
+    has them too."""
+
+    def other_object_min_device(self, d_q, nq, d_excl_obj, d_min, d_limit=None, limit_cap=0xFFFFFFFF):
+        """d_min[q] = min(the least Hamming distance from query q to a searched row outside object d_excl_obj[q], d_limit[q],
+        limit_cap), u32, 0xFFFFFFFF where there is no such row and no limit (todhip_other_object_min_device). Device pointers; every
+        word of d_min is written. Runs on any context, also on one shard: the element-wise minimum over the ranks is the whole DB's."""
+        _call("todhip_other_object_min_device", self._h, d_q, nq, d_excl_obj, d_limit, limit_cap, d_min)
+
+    def ratio_other_apply_device(self, ratio, nq, stride, d_other_min, d_counts, d_matches):
+        """counts[q] = 0 where a query's nearest kept match (slot 0) fails (float)d1 < ratio * (float)other_min[q]; 0xFFFFFFFF in
+        other_min always passes (todhip_ratio_other_apply_device)."""
+        _call("todhip_ratio_other_apply_device", self._h, ratio, nq, stride, d_other_min, d_counts, d_matches)
+
+    def ratio_other_device(self, d_q, nq, ratio, stride, d_counts, d_matches):
+        """Lowe's ratio test against the nearest searched row of ANOTHER object than the nearest match's, in place on a fixed-stride
+        device output of an unsharded context (todhip_ratio_other_device). Asynchronous on the context's stream."""
+        _call("todhip_ratio_other_device", self._h, d_q, nq, ratio, stride, d_counts, d_matches)
+
+    def set_ratio_test_other(self, ratio):
+        """match() and match_device() run ratio_other_device behind their finalize step, in front of the cross-check (0 = off, the
+        default). The sharded, radius and float forms ignore it."""
+        _call("todhip_set_ratio_test_other", self._h, ratio)
+
+
+class Context(_RatioOtherCalls):
     """One HIP device + stream (todhip_ctx)."""
 
     def __init__(self, device=0, stream=None):

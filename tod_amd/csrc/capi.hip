@@ -357,6 +357,9 @@ int todhip_match_device(todhip_ctx* ctx, const void* d_q_desc, uint32_t nq, uint
   rc = tod_match_finalize(ctx, ctx->m_keys.as<uint64_t>(), n_lists, nq, k_in, k, radius,
                           reinterpret_cast<uint32_t*>(d_counts), reinterpret_cast<todhip_dmatch*>(d_matches),
                           reinterpret_cast<float*>(d_matches_xyz));
+  if (rc == TODHIP_OK && ctx->ratio_other > 0.f)                         // todhip_set_ratio_test_other: behind the finalize step's radius cut
+    rc = tod_ratio_other(ctx, d_q_desc, nq, ctx->ratio_other, radius, k, reinterpret_cast<uint32_t*>(d_counts),
+                         reinterpret_cast<todhip_dmatch*>(d_matches));
   if (rc == TODHIP_OK && ctx->cross_check_q)                             // todhip_set_cross_check: the filter behind the finalize step
     rc = tod_cross_check(ctx, d_q_desc, nq, ctx->cross_check_q, nullptr, k, reinterpret_cast<uint32_t*>(d_counts),
                          reinterpret_cast<todhip_dmatch*>(d_matches), reinterpret_cast<float*>(d_matches_xyz));
@@ -386,11 +389,11 @@ int todhip_match(todhip_ctx* ctx, const uint8_t* q_desc, uint32_t nq, uint32_t k
   todhip_dmatch* h_m = reinterpret_cast<todhip_dmatch*>(h_counts + nq);
   float* h_xyz = reinterpret_cast<float*>(h_m + nm);
   int rc = TODHIP_OK;
-  if (!ctx->cross_check_q) {
+  if (!ctx->cross_check_q && !(ctx->ratio_other > 0.f)) {
     rc = todhip_match_device(ctx, ctx->m_q.p, nq, k, radius, h_counts, h_m, h_xyz);
     if (rc != TODHIP_OK) return rc;
   } else {
-    // todhip_set_cross_check: the filter reads and compacts the outputs in place -- in device memory, not slot by slot over PCIe --
+    // todhip_set_cross_check, todhip_set_ratio_test_other: the filter reads and compacts the outputs in place -- in device memory, not slot by slot over PCIe --
     // and the filtered image follows in three copies
     rc = todhip_match_device(ctx, ctx->m_q.p, nq, k, radius, ctx->m_counts.p, ctx->m_matches.p, ctx->m_xyz.p);
     if (rc != TODHIP_OK) return rc;

@@ -100,7 +100,7 @@ struct HostBuf {
 // A stage's workspace: defined in the stage's translation unit (struct XWs : TodWs with kSlot = its slot), created on first use by
 // tod_ws<XWs>(ctx), owned by the context. Its destructor is the stage's whole teardown. The slots are released in this order.
 struct TodWs { virtual ~TodWs() {} };
-enum TodWsSlot { kWsVerify, kWsOrb, kWsL2, kWsPnp, kWsLsh, kWsLearn, kWsCompact, kWsRadius, kWsCrossCheck, kWsSlots };
+enum TodWsSlot { kWsVerify, kWsOrb, kWsL2, kWsPnp, kWsLsh, kWsLearn, kWsCompact, kWsRadius, kWsCrossCheck, kWsOther, kWsSlots };
 
 struct todhip_ctx {
   int device = 0;
@@ -136,6 +136,7 @@ struct todhip_ctx {
   K4xSplit k4x;                              // k4x.force: todhip_set_matcher_block_split
   float ratio = 0.f;                         // todhip_set_ratio_test (0 = off)
   uint32_t cross_check_q = 0;                // todhip_set_cross_check: the frame size todhip_match[_device] filter with (0 = off)
+  float ratio_other = 0.f;                   // todhip_set_ratio_test_other (0 = off): the filter todhip_match[_device] run behind finalize
   float l2_ratio = 0.f;                      // todhip_set_l2_ratio_test (0 = off): the float forms' own ratio test
   uint32_t l2_cross_check_q = 0;             // todhip_set_l2_cross_check: the frame size todhip_match_l2[_device] filter with (0 = off)
   // todhip_set_db_bit_order (db_bitorder.hip): the mode the next load uses; the order of the resident shard (stored position p holds
@@ -237,6 +238,10 @@ int tod_match_finalize(todhip_ctx* ctx, const uint64_t* d_keys_all, uint32_t n_s
 // cross_check.hip: todhip_cross_check_device behind its argument checks (what todhip_match[_device] run while todhip_set_cross_check is on)
 int tod_cross_check(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t frame_queries, const uint32_t* frame_nq, uint32_t stride,
                     uint32_t* d_counts, todhip_dmatch* d_matches, float* d_xyz);
+// match_other.hip: todhip_ratio_other_device behind its argument checks (what todhip_match[_device] run while
+// todhip_set_ratio_test_other is on); max_d1: no kept match is further than this (the call's radius; the row width when unknown)
+int tod_ratio_other(todhip_ctx* ctx, const void* d_q, uint32_t nq, float ratio, uint32_t max_d1, uint32_t stride, uint32_t* d_counts,
+                    todhip_dmatch* d_matches);
 // cross_check.hip: todhip_cross_check_l2_device behind its argument checks (what todhip_match_l2[_device] run while
 // todhip_set_l2_cross_check is on); d_q: nq rows of 128 f32
 int tod_cross_check_l2(todhip_ctx* ctx, const void* d_q, uint32_t nq, uint32_t frame_queries, const uint32_t* frame_nq, uint32_t stride,
